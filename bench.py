@@ -9,9 +9,11 @@ per MI355X).  One "step" = one full G+D step = one generator/encoder apply + one
 discriminator apply (n_critic = 2, image_generation.py:640-652) over one synthetic batch of
 ``--batch`` (source, target) pairs per GPU, inputs resident in HBM.  value = pairs/sec over all ranks.
 
-Extra objects on the JSON line (rank 0, N = 1): ``roofline`` for the dominant kernel family (HIP
-events around every launch in a separate instrumented pass of the same step) and ``cpu_baseline``
-(the torch-CPU oracle timed on a bounded sample of the same workload).
+A plain run sets up, warms up, times exactly ``--steps`` steps once and prints the line.  ``--full`` adds what takes runs
+of its own: the median of ``--repeats`` (3) timed regions and, on the line (rank 0, N = 1), ``roofline`` for the dominant
+kernel family (HIP events around every launch in a separate instrumented pass of the same step) and ``cpu_baseline``
+(the torch-CPU oracle timed on a bounded sample of the same workload).  ``--dump-outputs DIR`` starts the last timed step
+from the trainer's seeded initial state (restored untimed) and writes the losses it returned to DIR (dump_outputs).
 """
 import argparse
 import json
@@ -49,7 +51,14 @@ def parse():
   ap.add_argument('--max-ch', type=int, default=256)
   ap.add_argument('--precision', default=None, choices=['bf16', 'fp16', 'fp32'],
                   help='activation storage; default bf16, fp16 for --config 4 (the dtype BASELINE.json names for it)')
-  ap.add_argument('--repeats', type=int, default=3, help='timed regions of --steps steps each; the median is reported')
+  ap.add_argument('--full', action='store_true',
+                  help='also the measurements beyond the headline figure: --repeats timed regions (median reported), the '
+                       'roofline pass and the torch-CPU baseline')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='start the last timed step from the seeded initial state and write the losses it returned to '
+                       'DIR/g_losses.npy and DIR/d_losses.npy (float32)')
+  ap.add_argument('--repeats', type=int, default=None,
+                  help='timed regions of --steps steps each; the median is reported (default 1, 3 under --full)')
   ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
   ap.add_argument('--no-roofline', action='store_true')
   ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -70,6 +79,8 @@ def parse():
     args.precision = 'fp16' if args.config == 4 else 'bf16'
   args.hw = args.hw or hw
   args.batch = args.batch or batch
+  if args.repeats is None:
+    args.repeats = 3 if args.full else 1
   return args
 
 
@@ -136,8 +147,26 @@ def synthetic_batch(batch, hw, dtype, device, rank):
 
 
 def one_step(tr, a, b):
-  tr.run(a, b)      # generator / encoder apply   (n_critic_counter % 2 == 0)
-  tr.run(a, b)      # discriminator apply (GP alphas drawn on device)
+  """-> the (loss, terms) of the two runs, as the trainer returns them."""
+  g = tr.run(a, b)      # generator / encoder apply   (n_critic_counter % 2 == 0)
+  d = tr.run(a, b)      # discriminator apply (GP alphas drawn on device)
+  return g, d
+
+
+def dump_outputs(path, tr, outs):
+  """What one step hands its caller -- Trainer.run's (loss, terms) of the generator run and of the discriminator run -- as
+  float32 vectors: DIR/g_losses.npy and DIR/d_losses.npy, each the run's loss followed by its loss terms in the order of
+  their sorted names.  One vector per run: at the initial state the discriminator's WGAN terms are differences of nearly
+  equal means (~1e-9 beside a total of ~20), so they are compared at the scale of their run, not on their own.
+  main() starts that step from the trainer's seeded initial state, so its inputs are the same on every run and two runs
+  agree to rounding.  The parameters the step leaves are not written: Adam's first update is lr * g / (|g| + eps), so a
+  gradient near zero turns rounding into a difference of up to 2 lr."""
+  import numpy as np
+  os.makedirs(path, exist_ok=True)
+  torch.cuda.synchronize()
+  for kind, (loss, terms) in zip(('g', 'd'), outs):
+    vec = torch.stack([loss.reshape(())] + [terms[k].reshape(()) for k in sorted(terms)])
+    np.save(os.path.join(path, kind + '_losses.npy'), vec.detach().float().cpu().numpy())
 
 
 def roofline_pass(tr, a, b, steps=2):
@@ -451,6 +480,8 @@ def main():
     tr.reducer.always = True
   dtype = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[args.precision]
   a, b = synthetic_batch(args.batch, args.hw, dtype, device, rank)
+  # --dump-outputs: the seeded state the trainer starts from (parameters, optimiser slots, counters, device draws)
+  init_state = tr._snapshot() if args.dump_outputs else None
 
   for _ in range(max(args.warmup, 1)):      # at least one: the first graph-mode step is the capture
     one_step(tr, a, b)
@@ -468,29 +499,44 @@ def main():
   torch.cuda.synchronize()
   tr.reducer.reset_stats()
 
-  def timed_region():
-    """EXACTLY --steps steps between barrier + synchronize on both sides; the MAX over ranks."""
+  last = [None]      # the outputs of the latest timed step
+
+  def timed_region(reset_last=False):
+    """EXACTLY --steps steps between barrier + synchronize on both sides; the MAX over ranks.  ``reset_last``
+    (--dump-outputs): the trainer is put back to its seeded initial state before the last step, untimed, so that step
+    computes from the same inputs on every run (training from random weights amplifies the run-to-run rounding of the
+    kernels' float atomics step by step: after a few steps two runs no longer agree beyond rounding)."""
     if world > 1:
       dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-      one_step(tr, a, b)
+    paused = 0.0
+    for i in range(args.steps):
+      if reset_last and i == args.steps - 1:
+        torch.cuda.synchronize()
+        p0 = time.perf_counter()
+        tr._restore(init_state)
+        torch.cuda.synchronize()
+        paused += time.perf_counter() - p0
+      last[0] = one_step(tr, a, b)
     torch.cuda.synchronize()
     if world > 1:
       dist.barrier()
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
     if world > 1:
       tt = torch.tensor([dt], dtype=torch.float64, device=device)
       dist.all_reduce(tt, op=dist.ReduceOp.MAX)
       dt = float(tt.item())
     return dt
 
-  # the pool's boxes (and one box over time) spread by several per cent: the region is timed --repeats times back to back
-  # and the line reports the MEDIAN region (value, ms_per_step), with the fastest / slowest beside it
-  regions = sorted(timed_region() for _ in range(max(args.repeats, 1)))
+  # the pool's boxes (and one box over time) spread by several per cent: under --full the region is timed --repeats times
+  # back to back and the line reports the MEDIAN region (value, ms_per_step), with the fastest / slowest beside it
+  nreg = max(args.repeats, 1)
+  regions = sorted(timed_region(reset_last=bool(args.dump_outputs) and r == nreg - 1) for r in range(nreg))
   elapsed = regions[len(regions) // 2]
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, tr, last[0])
 
   ms_per_step = 1e3 * elapsed / args.steps
   value = args.batch * world * args.steps / elapsed
@@ -515,7 +561,7 @@ def main():
   if args.hw == 256:
     tf = value * GFLOP_PER_PAIR_256 / 1e3 / world
     out['step_mfma_frac'] = round(tf / BF16_MFMA_PEAK_TFLOPS, 4)       # whole-step fraction of the conv roofline
-  if rank == 0 and world == 1:
+  if rank == 0 and world == 1 and args.full:
     if not args.no_roofline:
       out['roofline'], tables = roofline_pass(tr, a, b)
       out['roofline']['tables'] = write_tables(tables, args.config)

@@ -38,13 +38,16 @@ def test_preprocess_oracle_hits_the_reference_fixture():
   assert {m for m, *_ in seen} == {'PAD', 'CROP', 'RESHAPE'} and len(seen) >= 6
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference tree is only mounted in the build container')
 def test_preprocess_oracle_against_the_live_reference():
+  """The reference's preprocess_image executed on the stand-in (oracle/ref_runner.py), as recorded in
+  tests/golden/reference/ (oracle/recorded.py)."""
   from oracle import ref_runner
+  from oracle.recorded import recorded
   rng = np.random.RandomState(5)
+  rec = recorded('preprocess_live')
   for k, (h, w, mode) in enumerate([(45, 61, 'PAD'), (80, 33, 'CROP'), (25, 25, 'PAD'), (19, 70, 'RESHAPE')]):
     img = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
-    want, dr = ref_runner.run_preprocess(img, 24, mode, True, seed=100 + k)
+    want, dr = rec(ref_runner.run_preprocess, img, 24, mode, True, seed=100 + k)
     ap = dict(dr['applied'])
     got = N.preprocess_image(img, 24, mode, True, flip=dr['flip_uniform'] < 0.5,
                              saturation_first=dr['applied'][0][0] == 'saturation', delta=ap['brightness'],
@@ -52,6 +55,7 @@ def test_preprocess_oracle_against_the_live_reference():
     assert np.abs(got - want).max() < 1e-12
     # apply_with_random_selector: ordering 0 is the only one with brightness first in fast mode
     assert (dr['sel'] == 0) == (dr['applied'][0][0] == 'brightness')
+  rec.close()
 
 
 def test_hsv_round_trip_matches_colorsys():
@@ -185,21 +189,24 @@ def test_preprocess_oracle_hits_the_modes_fixture():
   assert {m for m, _, _ in seen} == {'PAD', 'CROP', 'RESHAPE', 'RANDOM_CROP', 'NONE'} and {c for _, c, _ in seen} == {'rgb', 'yiq', 'bgr', 'gray'}
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference tree is only mounted in the build container')
 def test_preprocess_modes_fixture_is_what_the_reference_computes():
-  """Re-executes preprocessing/danbooru_preprocessing.preprocess_image on the stand-in for every fixture case: same
-  draws, same output."""
+  """preprocessing/danbooru_preprocessing.preprocess_image executed again on the stand-in for every fixture case (recorded
+  in tests/golden/reference/, oracle/recorded.py): same draws, same output."""
   from oracle import ref_runner
+  from oracle.recorded import recorded
   sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
   import make_golden
   g = np.load(MODES)
   assert int(g['n']) == len(make_golden.PREPROCESS_MODE_CASES)
+  rec = recorded('preprocess_modes')
   for i, (h, w, mode, training, seed, cropping, cs) in enumerate(make_golden.PREPROCESS_MODE_CASES):
     c = _mode_case(g, i)
     assert c['img'].shape == (h, w, 3) and (c['mode'], c['cs'], c['training'], c['cropping']) == (mode, cs, training, cropping)
-    res, dr = ref_runner.run_preprocess(c['img'], int(g['hw']), mode, training, seed, do_random_cropping=cropping, color_space=cs)
+    res, dr = rec(ref_runner.run_preprocess, c['img'], int(g['hw']), mode, training, seed, do_random_cropping=cropping,
+                  color_space=cs)
     assert np.abs(res - c['want']).max() == 0.0 and dr['crop'] == c['crop']
     assert (None if dr['mode_crop'] is None else tuple(dr['mode_crop'][:2])) == c['moff']
+  rec.close()
 
 
 def test_crop_draws_and_resize_modes():
@@ -287,14 +294,16 @@ def _tables_to_image(img, rect, mid, crop, hw):
   return N.resize_bilinear_tf1(N.resize_bilinear_tf1(src, mid, mid)[cy:cy + ch, cx:cx + cw], hw, hw)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference tree is only mounted in the build container')
 def test_host_tables_reproduce_the_live_reference_for_every_resize_mode():
   """The tables Preprocessor.pack builds (source rectangle, intermediate size, crop rectangle) fed through a restatement of
   the kernel's table semantics equal the reference's own resize_image / random_crop_image for every mode, evaluation calls
   (no colour ops), with the reference's random draws: PAD, CROP, RESHAPE, RANDOM_CROP, RANDOM_CROP_AND_RESHAPE
-  (--random_crop_and_reshape_initial_crop_hw; preprocessing_util.py:24-27,128-131), with and without --do_random_cropping."""
+  (--random_crop_and_reshape_initial_crop_hw; preprocessing_util.py:24-27,128-131), with and without --do_random_cropping.
+  The reference's results are recorded in tests/golden/reference/ (oracle/recorded.py)."""
   from oracle import ref_runner
+  from oracle.recorded import recorded
   rng = np.random.RandomState(31)
+  rec = recorded('preprocess_tables')
   cases = [(37, 53, 'PAD', False, None), (64, 40, 'CROP', False, None), (20, 33, 'RESHAPE', True, None),
            (60, 70, 'RANDOM_CROP', False, None), (64, 70, 'RANDOM_CROP', True, None), (20, 45, 'RANDOM_CROP', True, None),
            (60, 70, 'RANDOM_CROP_AND_RESHAPE', False, 48), (30, 45, 'RANDOM_CROP_AND_RESHAPE', False, 48),
@@ -304,8 +313,8 @@ def test_host_tables_reproduce_the_live_reference_for_every_resize_mode():
     # a TRAINING call with flip / colour switched off is not available in the reference: compare the geometry on an
     # evaluation call when no cropping is asked for, else undo nothing -- feed gray (no colour ops) and un-flip
     training = cropping
-    res, dr = ref_runner.run_preprocess(img, 32, mode, training, seed=200 + i, do_random_cropping=cropping,
-                                        color_space='gray', initial_crop_hw=c)
+    res, dr = rec(ref_runner.run_preprocess, img, 32, mode, training, seed=200 + i, do_random_cropping=cropping,
+                  color_space='gray', initial_crop_hw=c)
     if training and dr['flip_uniform'] < 0.5:
       res = res[:, ::-1]
     pre = D.Preprocessor(32, device='cpu', resize_mode=mode, is_training=training, do_random_cropping=cropping,
@@ -316,6 +325,7 @@ def test_host_tables_reproduce_the_live_reference_for_every_resize_mode():
     crop = tables[4][0].tolist() if len(tables) == 5 else None
     got = _tables_to_image(img, rect, pre.mid, crop, 32)
     assert np.abs(got - res).max() < 1e-12, (i, mode, np.abs(got - res).max())
+  rec.close()
   with pytest.raises(AssertionError):
     D.Preprocessor(32, device='cpu', resize_mode='RANDOM_CROP_AND_RESHAPE')                        # needs the flag
   with pytest.raises(AssertionError):

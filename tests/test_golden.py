@@ -1,13 +1,13 @@
 """Golden fixtures (tests/golden/*.npz, written by tools/make_golden.py).
 
 The twingan_*.npz model fixtures are REFERENCE-generated: one G+D step of the reference's own graph code
-(/root/reference twingan.py, image_generation.py, nets/pggan*.py, libs/*) executed on the TensorFlow-API stand-in of
+(the reference's twingan.py, image_generation.py, nets/pggan*.py, libs/*) executed on the TensorFlow-API stand-in of
 oracle/tf_shim (oracle/ref_runner.py) -- weights, inputs, the reference's random draws, generated images, every loss
 term, every gradient.  primitives.npz holds single TensorFlow ops restated in float64 NumPy (oracle/np_ops.py).
 
 CPU (not gpu): the float64 oracle reproduces the reference's numbers to 1e-9 (this is what pins the oracle), the
-float32 oracle within fp32 round-off; where /root/reference is mounted the fixtures are re-derived from it and must
-come out bit-identical.
+float32 oracle within fp32 round-off; a second execution of the reference on the fixtures' weights and inputs (recorded
+in tests/golden/reference/, oracle/recorded.py) must come out bit-identical.
 GPU: the HIP path (fp32 direct kernels; bf16 MFMA kernels with a looser bound) hits the same vectors
 through the C ABI.  Tolerances: fp32 primitives rel-L2 <= 1e-5; fp32 whole-network outputs rel-L2 <= 2e-5, losses 1e-4
 relative, whole-model gradients rel-L2 <= 1e-2 (every variable of non-negligible norm <= 3e-2); bf16 outputs rel-L2 <= 5e-2, losses 5e-2.
@@ -141,16 +141,17 @@ def test_oracle_f64_matches_the_reference(name):
       assert np.abs(v.numpy() - g['state_after/' + k]).max() < 1e-12, k
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='the reference tree is only mounted in the build container')
 @pytest.mark.parametrize('name', ['twingan_hw16_c8', 'twingan_hw16_c16_sn_att'])
 def test_fixtures_are_what_the_reference_computes(name):
-  """Re-runs the reference's graph code (oracle/ref_runner.py) on the fixture's weights and inputs."""
+  """The reference's graph code (oracle/ref_runner.py) run again on the fixture's weights and inputs, as recorded in
+  tests/golden/reference/ (oracle/recorded.py)."""
   from oracle import ref_runner
+  from oracle.recorded import own_gradients, replay
   g = load(name)
   cfg = R.Config(**MODELS[name])
   preset = {k[len('param/'):]: v for k, v in g.items() if k.startswith('param/')}
-  ref = ref_runner.run(ref_runner.flags_of(cfg), g['in/sources'], g['in/targets'],
-                       global_step=ref_runner.global_step_of(cfg), seed=0, preset=preset)
+  ref = replay('fixture_' + name, ref_runner.run, ref_runner.flags_of(cfg), g['in/sources'], g['in/targets'],
+               global_step=ref_runner.global_step_of(cfg), seed=0, preset=preset, prune=own_gradients)
   assert set(ref['variables']) - {'global_step'} == set(preset)      # the reference creates exactly these variables
   assert abs(ref['g_loss'] - float(g['loss/g_total'])) < 1e-12 and abs(ref['d_loss'] - float(g['loss/d_total'])) < 1e-12
   for grp in 'gd':

@@ -202,13 +202,17 @@ def test_stage_schedule_matches_pggan_runner():
 
 def test_stage_schedule_matches_what_pggan_runner_sets():
   """tests/golden/stage_driver.json = the per-stage flags pggan_runner.main itself set when it was executed by
-  oracle/ref_runner.run_stage_driver (tools/make_golden.py); where /root/reference is mounted it is run again."""
+  oracle/ref_runner.run_stage_driver (tools/make_golden.py); a second execution, recorded in tests/golden/reference/
+  (oracle/recorded.py), must agree."""
   import json
   import os
   from twingan_amd.runner import stage_schedule
+  from oracle import ref_runner
+  from oracle.recorded import recorded
   with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'stage_driver.json')) as fh:
     cases = json.load(fh)
   assert len(cases) >= 3
+  rec = recorded('stage_driver')
   for c in cases:
     table = {int(k): v for k, v in c['hw_to_batch_size'].items()}
     mine = stage_schedule(c['start_hw'], c['max_hw'], table, c['num_images_per_resolution'])
@@ -217,9 +221,8 @@ def test_stage_schedule_matches_what_pggan_runner_sets():
     # warm start: every stage restores from the previous one, ignoring missing variables exactly when growing
     assert [s['checkpoint_path'] for s in ref] == [None] + [s['name'] for s in ref[:-1]]
     assert all(s['ignore_missing_vars'] == s['is_growing'] for s in ref)
-    if os.path.isdir('/root/reference'):
-      from oracle import ref_runner
-      assert ref_runner.run_stage_driver(c['start_hw'], c['max_hw'], table, c['num_images_per_resolution']) == ref
+    assert rec(ref_runner.run_stage_driver, c['start_hw'], c['max_hw'], table, c['num_images_per_resolution']) == ref
+  rec.close()
 
 
 def test_warm_start_ignores_missing_and_reshaped_vars():
@@ -285,7 +288,7 @@ def test_bench_line_contract():
   c = d['cpu_baseline']
   assert c['kind'] in ('port', 'reference') and c['cores'] >= 1 and c['value'] > 0 and c['unit'] == d['unit'] and c['sample']
   src = open(os.path.join(root, 'bench.py')).read()
-  for flag in ('--gpus', '--steps', '--warmup'):
+  for flag in ('--gpus', '--steps', '--warmup', '--full', '--dump-outputs'):
     assert "'%s'" % flag in src
 
 

@@ -1,6 +1,7 @@
-"""Live pin: where the reference tree is mounted (the build container) its own graph code is executed on the TensorFlow
-stand-in (oracle/ref_runner.py) for configurations beyond the frozen fixtures, and the float64 oracle must reproduce
-every loss term and every gradient.  Skipped on the GPU box, where /root/reference does not exist."""
+"""Pins beyond the frozen fixtures: the reference's own graph code executed on the TensorFlow stand-in
+(oracle/ref_runner.py) for further configurations, and the float64 oracle must reproduce every loss term and every
+gradient.  The runner's results are recorded under tests/golden/reference/ (oracle/recorded.py; TG_RECORD_REFERENCE=1
+executes the reference again and rewrites them), so these tests need nothing outside the repository."""
 import os
 
 import numpy as np
@@ -8,9 +9,7 @@ import pytest
 import torch
 
 from oracle import torch_ref as R
-
-pytestmark = pytest.mark.skipif(not os.path.isdir('/root/reference'),
-                                reason='the reference tree is only mounted in the build container')
+from oracle.recorded import own_gradients, recorded, replay
 
 CASES = {
   'gan': dict(hw=64, max_ch=8, loss='gan'),                                   # cycle-GAN term on (twingan.py:466)
@@ -68,8 +67,8 @@ def test_oracle_matches_live_reference(name):
     emb = (rng.randn(batch, cfg.distill_embed_dim), None if name.endswith('source_only') else rng.randn(batch, cfg.distill_embed_dim))
     cfg.distill_embed_s = torch.from_numpy(emb[0])
     cfg.distill_embed_t = None if emb[1] is None else torch.from_numpy(emb[1])
-  ref = ref_runner.run(ref_runner.flags_of(cfg), s, t, global_step=ref_runner.global_step_of(cfg), seed=1, preset=preset,
-                       eager_updates=stateful, embeddings=emb)
+  ref = replay('live_oracle_' + name, ref_runner.run, ref_runner.flags_of(cfg), s, t, global_step=ref_runner.global_step_of(cfg),
+               seed=1, preset=preset, eager_updates=stateful, embeddings=emb, prune=own_gradients)
   created = {k for k in ref['variables'] if k != 'global_step' and '/moving_' not in k and '/renorm_' not in k}
   assert created == set(preset)
   draws = {}
@@ -132,8 +131,8 @@ def test_pggan_oracle_matches_live_reference(name):
   flags = dict(train_image_size=cfg.hw, pggan_max_num_channels=cfg.max_ch, generator_norm_type=cfg.norm,
                loss_architecture=cfg.loss, wgan_drift_loss_weight=cfg.drift, is_growing=cfg.is_growing,
                max_number_of_steps=ref_runner.GROW_STEPS, grow_start_number_of_steps=0)
-  ref = ref_runner.run_pggan(flags, t, global_step=ref_runner.global_step_of(cfg), seed=2,
-                             preset={k: v.numpy() for k, v in P.items()})
+  ref = replay('live_pggan_' + name, ref_runner.run_pggan, flags, t, global_step=ref_runner.global_step_of(cfg), seed=2,
+               preset={k: v.numpy() for k, v in P.items()}, prune=own_gradients)
   assert set(ref['trainable']) == set(P)
   draws = {}
   for n, v in ref['random']:
@@ -183,7 +182,8 @@ def test_inference_branch_matches_live_reference(norm):
     assert state
   preset = {k: v.numpy() for k, v in list(P.items()) + list(state.items())}
   s, t, sp, tp = (rng.rand(2, 16, 16, 3) for _ in range(4))
-  ref = ref_runner.run(ref_runner.flags_of(cfg), s, t, want_grads=False, preset=preset, feed={'sources_ph': sp, 'targets_ph': tp})
+  ref = replay('live_inference_' + norm, ref_runner.run, ref_runner.flags_of(cfg), s, t, want_grads=False, preset=preset,
+               feed={'sources_ph': sp, 'targets_ph': tp}, drop=('end_points',))
   cfg.bn_state = state
   with torch.no_grad():
     assert np.abs(R.translate(P, torch.from_numpy(sp), cfg, 't').numpy() - ref['custom']['custom_generated_t_style_source']).max() < 1e-9
@@ -203,8 +203,8 @@ def test_ttur_training_runs_match_live_reference():
   flags = dict(ref_runner.flags_of(cfg), learning_rate=cfg.lr, learning_rate_decay_type='fixed', optimizer='adam',
                adam_beta1=cfg.beta1, adam_beta2=cfg.beta2, opt_epsilon=cfg.adam_eps, n_critic=2, use_ttur=True,
                discriminator_learning_rate=cfg.d_lr)
-  ref = ref_runner.run_training(flags, [(s.numpy(), t.numpy()) for s, t in runs], seed=0,
-                                preset={k: v.numpy() for k, v in P.items()})
+  ref = replay('live_ttur', ref_runner.run_training, flags, [(s.numpy(), t.numpy()) for s, t in runs], seed=0,
+               preset={k: v.numpy() for k, v in P.items()})
   opt = R.AdamState(P, cfg)
   for i, ((s, t), h) in enumerate(zip(runs, ref['history'])):
     a = [v for n, v in h['random'] if n == 'alpha']
@@ -224,7 +224,8 @@ def test_warm_start_set_is_slims_model_variables():
   from twingan_amd.params import is_model_variable
   cfg = R.Config(hw=16, max_ch=8, spectral_norm=True, sn_non_disc=True, do_self_attention=True, self_attention_hw=16)
   rng = np.random.RandomState(3)
-  ref = ref_runner.run(ref_runner.flags_of(cfg), rng.rand(2, 16, 16, 3), rng.rand(2, 16, 16, 3), seed=1, want_grads=False)
+  ref = replay('live_warm_start_set', ref_runner.run, ref_runner.flags_of(cfg), rng.rand(2, 16, 16, 3), rng.rand(2, 16, 16, 3),
+               seed=1, want_grads=False)
   in_collection = set(ref['model_variables'])
   names = [k for k in ref['variables'] if k.split('/')[0] in ('generator', 'encoder_content', 'discriminator_s', 'discriminator_t')]
   us = [k for k in names if k.endswith('/u')]
@@ -246,7 +247,8 @@ def test_native_normaliser_variables_are_what_the_reference_creates(norm):
   from twingan_amd.params import ParamStore, declare_twingan, is_model_variable
   rcfg = R.Config(hw=16, max_ch=8, norm=norm)
   rng = np.random.RandomState(5)
-  ref = ref_runner.run(ref_runner.flags_of(rcfg), rng.rand(2, 16, 16, 3), rng.rand(2, 16, 16, 3), seed=1, want_grads=False)
+  ref = replay('live_native_variables_' + norm, ref_runner.run, ref_runner.flags_of(rcfg), rng.rand(2, 16, 16, 3),
+               rng.rand(2, 16, 16, 3), seed=1, want_grads=False)
   store = declare_twingan(ParamStore('cpu'), Config(hw=16, max_ch=8, generator_norm_type=norm)).build(seed=0)
   want = {k: v for k, v in ref['variables'].items() if k != 'global_step'}
   trainable = {k: tuple(store.specs[k]['shape']) for k in store.specs}
@@ -268,7 +270,8 @@ def test_gdrop_layer_matches_live_reference():
   cfg = R.Config(hw=16, max_ch=8, do_dgrop=True, gdrop_strength=0.3)
   P = {k: v.float().double() for k, v in R.init_params(cfg, seed=5, dtype=torch.float64, std='he').items()}
   x = torch.rand(3, 16, 16, 3, generator=torch.Generator().manual_seed(6)).double()
-  ref = ref_runner.run_discriminator(ref_runner.flags_of(cfg), x.numpy(), 'discriminator_s',
+  rec = recorded('live_gdrop_layer')
+  ref = rec(ref_runner.run_discriminator, ref_runner.flags_of(cfg), x.numpy(), 'discriminator_s',
                                      preset={k: v.numpy() for k, v in P.items()}, do_dgrop=True, gdrop_strength=0.3,
                                      is_training=True)
   draws = [v for n, v in ref['random'] if n == 'gdrop']
@@ -279,9 +282,9 @@ def test_gdrop_layer_matches_live_reference():
   plain, _ = R.discriminator(P, x, R.Config(hw=16, max_ch=8), 'discriminator_s')
   assert np.abs(plain.detach().numpy() - ref['prediction']).max() > 1e-2
   # is_training=False: the identity (nets/pggan.py:352)
-  ref_eval = ref_runner.run_discriminator(ref_runner.flags_of(cfg), x.numpy(), 'discriminator_s',
-                                          preset={k: v.numpy() for k, v in P.items()}, do_dgrop=True, gdrop_strength=0.3,
-                                          is_training=False)
+  ref_eval = rec(ref_runner.run_discriminator, ref_runner.flags_of(cfg), x.numpy(), 'discriminator_s',
+                 preset={k: v.numpy() for k, v in P.items()}, do_dgrop=True, gdrop_strength=0.3, is_training=False)
+  rec.close()
   assert not ref_eval['random'] and np.abs(plain.detach().numpy() - ref_eval['prediction']).max() < 1e-12
 
 
@@ -298,9 +301,10 @@ def test_use_gdrop_changes_no_update_and_its_controller_matches_live_reference()
   base = dict(ref_runner.flags_of(cfg), learning_rate=cfg.lr, learning_rate_decay_type='fixed', optimizer='adam',
               adam_beta1=cfg.beta1, adam_beta2=cfg.beta2, opt_epsilon=cfg.adam_eps, n_critic=2)
   out = {}
-  for flag in (False, True):
-    out[flag] = ref_runner.run_training(dict(base, use_gdrop=flag, gdrop_lim=0.25), [(s.numpy(), t.numpy()) for s, t in runs],
-                                        seed=0, preset={k: v.numpy() for k, v in P0.items()}, global_step=150)
+  with recorded('live_use_gdrop') as rec:
+    for flag in (False, True):
+      out[flag] = rec(ref_runner.run_training, dict(base, use_gdrop=flag, gdrop_lim=0.25), [(s.numpy(), t.numpy()) for s, t in runs],
+                      seed=0, preset={k: v.numpy() for k, v in P0.items()}, global_step=150)
   assert 'gdrop_strength' in out[True]['variables'] and 'gdrop_strength' not in out[False]['variables']
   for k in P0:      # the flag changes no parameter
     assert np.array_equal(out[True]['variables'][k], out[False]['variables'][k]), k

@@ -7,7 +7,7 @@
 #   full              the whole GPU suite, -x (what the driver runs)
 #   record            re-record tests/golden/bench_dispatch_kernels.json from this build (copied to the out dir only)
 #   smoke             __graft_entry__.smoke()
-#   bench[:C]         default bench line of config C (3): roofline + cpu_baseline + per-shape table (shapes_cC.json)
+#   bench[:C]         bench --full line of config C (3): roofline + cpu_baseline + per-shape table (shapes_cC.json)
 #   quick[:C]         bench line without roofline / cpu baseline
 #   prof[:C]          rocprofv3 --kernel-trace --stats of a short bench run -> prof_cC/ (kernel trace deleted)
 #   ab:<VAR=v,...>    interleaved same-box A/B, ROUNDS (2) rounds: default environment vs the given variables (config 3)
@@ -51,7 +51,7 @@ for step in "$@"; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?" >> $OUT/smoke.log; tail -1 $OUT/smoke.log ;;
     bench)
       c=${arg:-3}
-      TG_DUMP_SHAPES=$REPO/$OUT/shapes_c$c.json timeout 600 python bench.py --config $c > $OUT/bench_c$c.log 2> $OUT/bench_c$c.err; echo "exit $?" >> $OUT/bench_c$c.log
+      TG_DUMP_SHAPES=$REPO/$OUT/shapes_c$c.json timeout 600 python bench.py --full --config $c > $OUT/bench_c$c.log 2> $OUT/bench_c$c.err; echo "exit $?" >> $OUT/bench_c$c.log
       head -c 400 $OUT/bench_c$c.log; echo ;;
     quick)
       c=${arg:-3}

@@ -14,7 +14,7 @@ if [ "$2" != "skip-tests" ]; then
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
   echo "smoke exit $?" >> $OUT/smoke.log
 fi
-timeout 900 python bench.py > $OUT/bench.log 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 echo "bench exit $?" >> $OUT/bench.log
 timeout 300 python bench.py --no-graph --steps 3 --warmup 1 --no-roofline --no-cpu-baseline > $OUT/bench_eager.log 2> $OUT/bench_eager.err
 echo "bench exit $?" >> $OUT/bench_eager.log
