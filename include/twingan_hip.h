@@ -607,6 +607,20 @@ int tg_preprocess_images(const void* packed, const int64_t* offsets, const int* 
 int tg_preprocess_images_crop(const void* packed, const int64_t* offsets, const int* rect, const int* crop, const float* aug,
                               void* out, int n, int hw, int mid, int color_space, int dtype, void* stream);
 
+/* MS-SSIM between image batches (libs/ms_ssim.py:115-171 msssim; per level :39-110 _SSIMForMultiScale with the window of
+ * :27-37 _FSpecialGauss -- size min(11, h, w), sigma size * 1.5 / 11 -- and the 2x2 mean of :112 _HoxDownsample).  img1, img2:
+ * [n, h, w, c] NHWC (dtype), c in 1..4, h and w divisible by 2^(levels-1); a pixel enters as value * scale (255 for [0, 1]
+ * images with max_val 255).  weights: HOST array of `levels` exponents (NULL: the paper's five, levels must be 5).  Device
+ * outputs, fp32: score[n] = prod_l max(cs_l, 0)^w_l (l < levels-1) * max(ssim_last, 0)^w_last per pair; ssim, cs
+ * [levels][n] = the unclipped per-level means over the 'valid' maps; mean[1] = the mean of score over the n pairs (the
+ * value msssim returns).  One launch per level (moments in LDS, the next level's pair written by the same launch into
+ * ws), tile sums added in a fixed order: results are bit-reproducible and a pair's numbers do not depend on the rest of the
+ * batch.  ws: tg_msssim_workspace_bytes(...) bytes, 16-byte aligned (0 = unsupported shape).  No host synchronisation. */
+size_t tg_msssim_workspace_bytes(int n, int h, int w, int c, int levels);
+int tg_msssim(const void* img1, const void* img2, int n, int h, int w, int c, int dtype, float scale, float max_val, float k1,
+              float k2, const float* weights, int levels, float* score, float* ssim, float* cs, float* mean, void* ws,
+              size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

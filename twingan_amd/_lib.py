@@ -72,6 +72,9 @@ SIGNATURES = {
     'tg_comm_destroy': (c_int, [_P]),
     'tg_preprocess_images': (c_int, [_P, _P, _P, _FP, _P, c_int, c_int, c_int, _P]),
     'tg_preprocess_images_crop': (c_int, [_P, _P, _P, _P, _FP, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    'tg_msssim_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'tg_msssim': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, POINTER(c_float), c_int,
+                          _FP, _FP, _FP, _FP, _P, c_size_t, _P]),
     'tg_conv2d_fwd_pool_supported': (c_int, [_D]),
     'tg_conv2d_fwd_pool': (c_int, [_D, _P, _P, _FP, _P, _P, _P]),
     'tg_conv2d_fwd_pool_signs': (c_int, [_D, _P, _P, _FP, _P, _P, _P]),

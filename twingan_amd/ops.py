@@ -2971,3 +2971,36 @@ def abs_diff_mean(a, b, weight=1.0):
 
 def gradient_penalty(g, lam):
   return GradPenaltyFn.apply(g, float(lam))
+
+
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # libs/ms_ssim.py:153 (they do not sum to 1; as the paper)
+
+
+def msssim(img1, img2, max_val=255., scale=1., weights=None, k1=0.01, k2=0.03, return_mean=False):
+  """MS-SSIM of libs/ms_ssim.py:115-171 between two NHWC batches [B, H, W, C] (fp32 / bf16 / fp16, C in 1..4, H and W
+  divisible by 2^(levels-1)); a pixel enters as value * scale (scale=255 for the model's [0, 1] images).  Returns
+  (score[B], ssim[L, B], cs[L, B]) -- the per-pair score and the unclipped per-level means -- as fp32 tensors on the inputs'
+  device, plus the batch mean [1] (what the reference's msssim returns) with ``return_mean``.  Enqueued on torch's
+  current stream; no autograd, no synchronisation."""
+  if img1.shape != img2.shape:
+    raise _lib.TgError('msssim: input images must have the same shape (%s vs. %s)' % (tuple(img1.shape), tuple(img2.shape)))
+  if img1.dim() != 4:
+    raise _lib.TgError('msssim: input images must have four dimensions [B, H, W, C], not %d' % img1.dim())
+  if img1.dtype != img2.dtype:
+    raise _lib.TgError('msssim: input images must have the same dtype (%s vs. %s)' % (img1.dtype, img2.dtype))
+  img1, img2 = img1.detach(), img2.detach()
+  _chk(img1, img2)
+  b, h, w, c = img1.shape
+  wts = tuple(float(v) for v in (weights if weights is not None else MSSSIM_WEIGHTS))
+  levels = len(wts)
+  dev = img1.device
+  score = torch.empty(b, dtype=torch.float32, device=dev)
+  ssim = torch.empty(levels, b, dtype=torch.float32, device=dev)
+  cs = torch.empty(levels, b, dtype=torch.float32, device=dev)
+  mean_ = torch.empty(1, dtype=torch.float32, device=dev)
+  nbytes = _lib.load().tg_msssim_workspace_bytes(b, h, w, c, levels)      # 0 for a shape the kernel refuses: tg_msssim says why
+  ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev)
+  call('tg_msssim', _p(img1), _p(img2), b, h, w, c, _dt(img1), float(scale), float(max_val), float(k1), float(k2),
+       (ctypes.c_float * levels)(*wts), levels, _p(score), _p(ssim), _p(cs), _p(mean_), _p(ws), nbytes, _stream(),
+       work=('msssim', 0, 2 * img1.numel() * img1.element_size()))
+  return (score, ssim, cs, mean_) if return_mean else (score, ssim, cs)
