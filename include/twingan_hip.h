@@ -238,13 +238,17 @@ int tg_conv2d_pack_weights(const TgConvDesc* d, const float* w_hwio, int mode, v
  * dispatch ends in the whole-image kernel (3x3 over 8x8 maps) the elements are stored in MFMA-fragment order instead
  * ([row / 32][k / 16][tap][row % 32][k % 16]: one contiguous KB per wave load).  tg_conv2d_pack_layout tells which
  * (0 = the [row][tap][k] order above, 1 = fragment order): a host that caches packs by (weight, mode) must not share one
- * between descriptors whose layouts differ (twingan_amd/ops.py PackCache keys on it). */
+ * between descriptors whose layouts differ (twingan_amd/ops.py PackCache keys on it).  For a grouped descriptor
+ * (groups > 1) the layout is the one of the launch that reads the pack: the whole batch where a kernel takes the grouped
+ * call as one launch, n / groups images where the entry point launches once per group. */
 int tg_conv2d_pack_layout(const TgConvDesc* d, int mode);
 
 /* All packs of an optimiser group in ONE launch (the step re-packs ~60 weights after every Adam apply; one
  * launch per pack is launch-latency bound).  The caller builds a job table in HOST memory with
  * tg_pack_table_fill (job j of njobs; *total_blocks accumulates the grid size, start it at 0), copies its
- * tg_pack_table_bytes(njobs) bytes to the device once, and calls tg_conv2d_pack_weights_multi every step. */
+ * tg_pack_table_bytes(njobs) bytes to the device once, and calls tg_conv2d_pack_weights_multi every step.  A grouped
+ * descriptor takes one job per weight set: pass the grouped descriptor itself (so that the job writes the element order
+ * tg_conv2d_pack_weights writes for it) with w_hwio / out_bf16 pointing at that set's master / pack. */
 size_t tg_pack_table_bytes(int njobs);
 int tg_pack_table_fill(const TgConvDesc* d, const float* w_hwio, int mode, void* out_bf16, int job, void* table_host,
                        int32_t* total_blocks);

@@ -2265,3 +2265,503 @@ def test_latent_layer_as_a_gemm_equals_the_padded_valid_conv(ops, dtype, monkeyp
   monkeypatch.delenv('TG_STRICT_DISPATCH')
   ref = O.conv2d(xp, wd.detach(), None, 4, 'VALID')
   assert rel_l2(host(y), host(ref)) < (1e-2 if dtype == torch.bfloat16 else 2e-3)
+
+
+# ---------------------------------------------------------------------------------------------- conv dispatch across its batch thresholds
+# Which conv kernel a call lands on depends on the BATCH, not only on the layer ("Dispatch thresholds"): conv_small
+# takes n * hout * wout <= 4096 pixels (and its packs are fragment-ordered, the first-generation kernel's are not), the tile
+# family changes its output block (blocks >= 1024), its sub-tiles per wave (tiles >= 1024) and the kernel itself (tiles >=
+# 2048 with 16 / 32 input channels: weight-resident / thin-output kernels).  The pairs below sit one batch on each side of
+# one such flip.  They are DATA: the tests do not recompute the dispatch arithmetic, they assert with tg_last_kernel() that
+# the two sides ran different kernels, and tests/golden/dispatch_edge_kernels.json pins every symbol
+# (TG_RECORD_EDGE_KERNELS=<path> re-records into <path>).
+import ctypes    # noqa: E402
+import json      # noqa: E402
+import os        # noqa: E402
+
+EDGE_KERNELS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dispatch_edge_kernels.json')
+# the bounds of tests/test_gpu_bench_shapes.py: 16-bit outputs vs the float64 oracle / vs the direct kernel, fp32 outputs
+EDGE_TOL = {torch.bfloat16: (4e-3, 2e-3), torch.float16: (6e-4, 4e-4)}
+EDGE_F32_TOL = 1e-4
+EDGE_DTYPES = {'bf16': torch.bfloat16, 'f16': torch.float16}
+
+EDGE_CASES = [
+    # id, k, padding, hw, cin, cout, n below, n above, entry points whose kernel must differ between the two
+    # conv_small <-> first-generation kernel, and with it the element order of the pack (4096 pixels)
+    ('small_k1_hw8', 1, 'SAME', 8, 32, 32, 64, 65, ('fwd', 'fwd_masked', 'bwd_data', 'bwd_data_masked')),
+    ('small_k3_hw4', 3, 'SAME', 4, 32, 32, 256, 257, ('fwd', 'fwd_masked', 'fwd_stats', 'bwd_data', 'bwd_data_masked')),
+    ('small_k3_hw8_c24', 3, 'SAME', 8, 24, 40, 64, 65, ('fwd', 'fwd_masked', 'bwd_data', 'bwd_data_masked')),      # conv_img refuses cin 24
+    # the dense 4x4 VALID layer is rewritten as a 1x1 conv over 16 cin channels of a 1x1 map: n pixels in BOTH directions
+    ('dense', 4, 'VALID', 4, 8, 8, 4096, 4097, ('fwd', 'fwd_masked', 'bwd_data', 'bwd_data_masked')),
+    # tile family: 32- <-> 64-channel output blocks (1024 blocks, cout > 32)
+    ('tile_bn', 3, 'SAME', 128, 48, 64, 7, 8, ('fwd', 'fwd_masked', 'fwd_stats', 'fwd_pool', 'bwd_data')),
+    # one <-> two sub-tiles per wave (1024 tiles, h % 16 == 0, cin_pad >= 64)
+    ('tile_mt', 3, 'SAME', 128, 64, 32, 7, 8, ('fwd', 'fwd_masked', 'fwd_stats', 'fwd_pool')),
+    # conv_tile_kernel <-> conv_tile_wres_kernel / conv_thin16_kernel (2048 tiles, cin_pad 16 / 32)
+    ('tile_wres16', 3, 'SAME', 128, 16, 32, 15, 16, ('fwd', 'fwd_masked', 'fwd_stats', 'fwd_pool', 'bwd_data', 'bwd_data_masked')),
+    ('tile_wres32', 3, 'SAME', 128, 32, 32, 15, 16, ('fwd', 'fwd_masked', 'fwd_stats', 'fwd_pool', 'bwd_data', 'bwd_data_masked')),
+    ('tile_thin16', 3, 'SAME', 128, 16, 16, 15, 16, ('fwd', 'fwd_masked', 'fwd_stats', 'bwd_data', 'bwd_data_masked')),
+    ('tile_k1_wres', 1, 'SAME', 128, 32, 32, 15, 16, ('fwd', 'fwd_masked', 'bwd_data', 'bwd_data_masked')),
+]
+
+
+def _last_kernel():
+  from twingan_amd import _lib
+  return _lib.load().tg_last_kernel().decode()
+
+
+class _Direct:
+  """Forces the direct (one thread per output) algorithm inside the block."""
+
+  def __enter__(self):
+    import twingan_amd.ops as O
+    self.O, self.saved = O, O._mfma_ok
+    O._mfma_ok = lambda *a: False
+
+  def __exit__(self, *a):
+    self.O._mfma_ok = self.saved
+
+
+def _edge_operands(seed, n, k, hin, ho, cin, cout, dtype, groups=1):
+  """16-bit activations, an fp32 master kernel holding 16-bit values (its pack is then exact), a bias."""
+  g = torch.Generator().manual_seed(seed)
+  x = torch.randn(n, hin, hin, cin, generator=g).to(dtype).to(dev())
+  gy = torch.randn(n, ho, ho, cout, generator=g).to(dtype).to(dev())
+  lead = (groups,) if groups > 1 else ()
+  w = (torch.randn(lead + (k, k, cin, cout), generator=g) / (k * k * cin) ** 0.5).to(dtype).float().to(dev()).contiguous()
+  b = (torch.randn(lead + (cout,), generator=g) * 0.1).to(dev())
+  return x, gy, w, b
+
+
+def _edge_wgrad_oracle(x, gy, k, pad):
+  """oracle/np_ops.py conv2d_bwd_weight; its one-BLAS-product-per-tap form (the same float64 sums, held to it by
+  tests/test_oracle.py) where the einsum form would take minutes."""
+  if x.size * gy.shape[3] * k * k <= 1 << 28:
+    return N.conv2d_bwd_weight(x, gy, (k, k), pad)
+  return N.conv2d_bwd_weight_gemm(x, gy, (k, k), pad)
+
+
+def _edge_partials(st, y, what):
+  """sum over chunks of the conv's statistics partials == (sum y, sum y^2) per image and channel of the tensor it wrote."""
+  n, h, w, c = y.shape
+  part = st.part.view(n, st.chunks, 2, c).double().sum(dim=1)
+  yd = y.double().view(n, h * w, c)
+  s1, s2 = yd.sum(dim=1), (yd * yd).sum(dim=1)
+  e1 = float(((part[:, 0] - s1).abs() / (s2 * h * w).sqrt().clamp_min(1e-30)).max())
+  e2 = float((part[:, 1] / s2.clamp_min(1e-30) - 1).abs().max())
+  assert e1 < 2e-6 and e2 < 2e-6, ('statistics partials', what, e1, e2)
+
+
+def _edge_symbols_check(case_id, dname, rec):
+  """rec {entry point: {n: kernel symbol}} of one (case, dtype) against the recorded table (or into it)."""
+  dst = os.environ.get('TG_RECORD_EDGE_KERNELS')
+  if dst:
+    table = {}
+    if os.path.exists(dst):
+      with open(dst) as fh:
+        table = json.load(fh)
+    table.setdefault(case_id, {})[dname] = rec
+    with open(dst, 'w') as fh:
+      json.dump(table, fh, indent=1, sort_keys=True)
+    return
+  assert os.path.exists(EDGE_KERNELS_PATH), 'record with TG_RECORD_EDGE_KERNELS=tests/golden/dispatch_edge_kernels.json'
+  with open(EDGE_KERNELS_PATH) as fh:
+    want = json.load(fh).get(case_id, {}).get(dname)
+  assert want == rec, ('dispatch moved', case_id, dname, rec, want)
+
+
+def _edge_straddles(cid, rec, flips, n_lo, n_hi):
+  for ep in flips:
+    lo, hi = rec[ep][str(n_lo)], rec[ep][str(n_hi)]
+    assert lo != hi, '%s %s: n = %d and n = %d no longer straddle a dispatch threshold, both ran %s' % (cid, ep, n_lo, n_hi, lo)
+
+
+def _edge_single(O, spec, pad, x, gy, w, b, dtype, rec, what):
+  """Every conv entry point on one batch: first and last image against the float64 oracle on the same rounded operands, the
+  whole tensor against the direct kernel, fp32 gradients against the oracle over the whole batch."""
+  from twingan_amd._lib import TG_EPI_BIAS, TG_EPI_LRELU
+  otol, dtol = EDGE_TOL[dtype]
+  rnd = bf16_round if dtype == torch.bfloat16 else f16_round
+  n, hin, _, cin = x.shape
+  ho, cout, k = gy.shape[1], gy.shape[3], spec.kh
+  sel = sorted({0, n - 1})
+  wn, bn, xs, gs = host(w), host(b), host(x[sel]), host(gy[sel])
+  epi = TG_EPI_BIAS | TG_EPI_LRELU
+
+  def note(ep):
+    rec.setdefault(ep, {})[str(n)] = _last_kernel()
+
+  def close(got, ref, tol, name):
+    e = rel_l2(got, ref)
+    print('[edge %s n%d] %s %.3e (bound %.1e)' % (what, n, name, e, tol))
+    assert e < tol, (what, n, name, e, tol)
+
+  # ---- forward: plain, bias + LeakyReLU, with the mask epilogue, with the statistics epilogue
+  lin = N.conv2d_gemm(xs, wn, pad)
+  y0 = O.conv_fwd_raw(x, w, None, spec, 0)
+  note('fwd')
+  close(host(y0[sel]), lin, otol, 'fwd')
+  with _Direct():
+    yd = O.conv_fwd_raw(x, w, None, spec, 0)
+  close(host(y0), host(yd), dtol, 'fwd vs direct')      # linear part: LeakyReLU would amplify a 1-ulp flip across zero
+  y1 = O.conv_fwd_raw(x, w, b, spec, epi)
+  close(host(y1[sel]), N.leaky_relu(lin + bn), otol, 'fwd bias lrelu')
+  ym = O.conv_fwd_masked_raw(x, w, gy, spec)             # gy has the output's shape: any tensor serves as the mask source
+  note('fwd_masked')
+  close(host(ym[sel]), lin * np.where(gs > 0, 1.0, 0.2), otol, 'fwd_masked')
+  with _Direct():
+    ymd = O.conv_fwd_masked_raw(x, w, gy, spec)
+  close(host(ym), host(ymd), 2 * dtol, 'fwd_masked vs direct')      # the direct path rounds once more before the mask
+  if k == 3:
+    ys, st = O.conv_fwd_stats_raw(x, w, spec)
+    note('fwd_stats')
+    close(host(ys[sel]), lin, otol, 'fwd_stats')
+    close(host(ys), host(yd), dtol, 'fwd_stats vs direct')
+    if st is not None:
+      _edge_partials(st, ys, what)
+    del ys
+  del ym, ymd
+
+  # ---- block ends (3x3 SAME shapes of the tile kernels): pooled output, sign bytes, the backward-data that unpools
+  if k == 3 and pad == 'SAME' and hin >= 16:
+    z, zp = O.conv_fwd_pool_raw(x, w, b, spec, epi)
+    note('fwd_pool')
+    close(host(z[sel]), N.leaky_relu(lin + bn), otol, 'fwd_pool z')
+    close(host(z), host(y1), dtol, 'fwd_pool z vs plain forward')
+    close(host(zp), host(z.float().view(n, ho // 2, 2, ho // 2, 2, cout).mean(dim=(2, 4))), dtol, 'fwd_pool pooled')
+    assert O.conv_fwd_pool_signs_supported(x, w, spec, epi), ('no sign-bit variant', what, n)
+    sg, zp2 = O.conv_fwd_pool_signs_raw(x, w, b, spec, epi)
+    note('fwd_pool_signs')
+    assert torch.equal(zp2, zp), ('fwd_pool_signs pooled', what, n)
+    bits = (z > 0).view(n, ho, ho, cout // 8, 8).to(torch.int32)
+    want_bytes = (bits << torch.arange(8, device=z.device, dtype=torch.int32)).sum(dim=-1).to(torch.uint8)
+    assert torch.equal(sg, want_bytes), ('fwd_pool_signs bits', what, n, int((sg != want_bytes).sum()))
+    if cout % 32 == 0:      # the unpooling kernels stage 32-channel chunks of the incoming gradient
+      gzp = gy[:, ::2, ::2, :].contiguous()
+      out = O.conv_bwd_data_unpool_raw(gzp, sg, w, x, tuple(x.shape), spec, True)
+      assert out is not None, ('unpool refused', what, n)
+      note('bwd_data_unpool')
+      g2, _ = O.lrelu_pool_bwd_signs(gzp, sg, spec.alpha, None, False)
+      assert torch.equal(out[1], g2), ('unpool kept gradient', what, n)
+      close(host(out[0]), host(O.conv_bwd_data_masked_raw(g2, w, x, spec)), dtol, 'unpool vs two launches')
+      up = host(gzp[sel]).repeat(2, axis=1).repeat(2, axis=2) * 0.25 * np.where(host(z[sel]) > 0, 1.0, 0.2)
+      ref = N.conv2d_bwd_data_gemm(rnd(up), wn, (hin, hin), pad) * np.where(xs > 0, 1.0, 0.2)
+      close(host(out[0][sel]), ref, otol, 'unpool')
+      del out, g2
+    del z, zp, sg, zp2
+  del y0, y1, yd
+
+  # ---- backward-data, plain and with the producer's LeakyReLU mask in the epilogue
+  ref = N.conv2d_bwd_data_gemm(gs, wn, (hin, hin), pad)
+  gx = O.conv_bwd_data_raw(gy, w, tuple(x.shape), spec)
+  note('bwd_data')
+  close(host(gx[sel]), ref, otol, 'bwd_data')
+  with _Direct():
+    gd = O.conv_bwd_data_raw(gy, w, tuple(x.shape), spec)
+  close(host(gx), host(gd), dtol, 'bwd_data vs direct')
+  gm = O.conv_bwd_data_masked_raw(gy, w, x, spec)
+  note('bwd_data_masked')
+  close(host(gm[sel]), ref * np.where(xs > 0, 1.0, 0.2), otol, 'bwd_data_masked')
+  close(host(gm), host(O.lrelu_bwd_raw(gd, x, 0.2)), 2 * dtol, 'bwd_data_masked vs direct')      # two roundings apart
+  del gx, gd, gm
+
+  # ---- filter gradient (fp32), alone and with the bias gradient riding along
+  want_gw = _edge_wgrad_oracle(host(x), host(gy), k, pad)
+  gw = O.conv_bwd_weight_raw(x, gy, spec)
+  note('bwd_weight')
+  close(host(gw), want_gw, EDGE_F32_TOL, 'bwd_weight')
+  gb = torch.zeros(cout, dtype=torch.float32, device=x.device)
+  gw = O.conv_bwd_weight_raw(x, gy, spec, gbias=gb)
+  note('bwd_weight_bias')
+  close(host(gw), want_gw, EDGE_F32_TOL, 'bwd_weight_bias')
+  close(host(gb), host(gy).sum(axis=(0, 1, 2)), EDGE_F32_TOL, 'bwd_weight_bias bias')
+
+
+@pytest.mark.parametrize('dname', sorted(EDGE_DTYPES))
+@pytest.mark.parametrize('case', EDGE_CASES, ids=[c[0] for c in EDGE_CASES])
+def test_conv_entry_points_on_both_sides_of_a_dispatch_threshold(ops, case, dname):
+  """One layer at two batches that straddle one batch threshold of the conv dispatch: every entry point is right on both
+  sides (oracle, direct kernel), the two sides DID run different kernels (a pair that no longer straddles its threshold
+  fails here and says so), and every symbol is the recorded one."""
+  import twingan_amd.ops as O
+  cid, k, pad, hw, cin, cout, n_lo, n_hi, flips = case
+  dtype = EDGE_DTYPES[dname]
+  spec = O.ConvSpec(k, pad)
+  ho = hw if pad == 'SAME' else hw - k + 1
+  x, gy, w, b = _edge_operands(900 + EDGE_CASES.index(case), n_hi, k, hw, ho, cin, cout, dtype)
+  rec = {}
+  for n in (n_lo, n_hi):
+    _edge_single(O, spec, pad, x[:n], gy[:n], w, b, dtype, rec, cid)
+  _edge_straddles(cid, rec, flips, n_lo, n_hi)
+  _edge_symbols_check(cid, dname, rec)
+
+
+UPCAT_EDGE_CASES = [
+    # id, hw (output), c0, c1, cout, n below, n above, entry points whose kernel must differ
+    ('upcat_32_32_mt_wres', 64, 32, 32, 32, 31, 32, ('upcat_fwd', 'upcat_bwd_data')),      # forward: sub-tiles; backward: weight-resident
+    ('upcat_64_64_bn', 64, 64, 64, 64, 15, 16, ('upcat_bwd_data',)),                        # backward: 64-channel blocks
+    ('upcat_64_64_mt', 64, 64, 64, 64, 31, 32, ('upcat_fwd',)),
+    ('upcat_32_32_thin16', 128, 32, 32, 16, 15, 16, ('upcat_fwd',)),                        # forward: thin-output kernel
+    ('upcat_32_32_upboth', 128, 32, 32, 16, 7, 8, ('upcat_fwd', 'upcat_bwd_data')),         # backward: both halves in one block
+    ('upcat_64_64_wres', 128, 64, 64, 32, 7, 8, ('upcat_fwd', 'upcat_bwd_data')),
+]
+
+
+@pytest.mark.parametrize('dname', sorted(EDGE_DTYPES))
+@pytest.mark.parametrize('case', UPCAT_EDGE_CASES, ids=[c[0] for c in UPCAT_EDGE_CASES])
+def test_upcat_conv_on_both_sides_of_a_dispatch_threshold(ops, case, dname):
+  """conv3x3(concat(up2(x0), skip)) read from its two sources, its backward-data with the concat adjoint in the epilogue and
+  its filter gradient, at two batches that straddle a threshold of dispatch_tile_upcat / dispatch_tile_upbwd."""
+  import twingan_amd.ops as O
+  cid, hw, c0, c1, cout, n_lo, n_hi, flips = case
+  dtype = EDGE_DTYPES[dname]
+  otol, dtol = EDGE_TOL[dtype]
+  spec = O.ConvSpec(3, 'SAME')
+  g = torch.Generator().manual_seed(950 + UPCAT_EDGE_CASES.index(case))
+  x0a = torch.randn(n_hi, hw // 2, hw // 2, c0, generator=g).to(dtype).to(dev())
+  x1a = torch.randn(n_hi, hw, hw, c1, generator=g).to(dtype).to(dev())
+  gya = torch.randn(n_hi, hw, hw, cout, generator=g).to(dtype).to(dev())
+  w = (torch.randn(3, 3, c0 + c1, cout, generator=g) / (9 * (c0 + c1)) ** 0.5).to(dtype).float().to(dev()).contiguous()
+  wn = host(w)
+  rec = {}
+
+  def close(got, ref, tol, name, n):
+    e = rel_l2(got, ref)
+    print('[edge %s n%d] %s %.3e (bound %.1e)' % (cid, n, name, e, tol))
+    assert e < tol, (cid, n, name, e, tol)
+
+  def cat_of(i):      # the materialised input of image i
+    return np.concatenate([host(x0a[i:i + 1]).repeat(2, axis=1).repeat(2, axis=2), host(x1a[i:i + 1])], axis=3)
+
+  for n in (n_lo, n_hi):
+    x0, x1, gy = x0a[:n].contiguous(), x1a[:n].contiguous(), gya[:n].contiguous()
+    assert O.upcat_conv_supported(x0, x1, w)
+    sel = sorted({0, n - 1})
+    cat = np.concatenate([cat_of(i) for i in sel])
+    y = O.upcat_conv(x0, x1, w, 0, ())
+    rec.setdefault('upcat_fwd', {})[str(n)] = _last_kernel()
+    close(host(y[sel]), N.conv2d_gemm(cat, wn), otol, 'upcat fwd', n)
+    xcat = O.upsample2x_concat(x0, x1, 0, ())
+    with _Direct():
+      yd = O.conv_fwd_raw(xcat, w, None, spec, 0)
+    close(host(y), host(yd), dtol, 'upcat fwd vs direct', n)
+    ys, st = O.upcat_conv_stats(x0, x1, w, 0, ())
+    rec.setdefault('upcat_fwd_stats', {})[str(n)] = _last_kernel()
+    close(host(ys), host(yd), dtol, 'upcat fwd_stats vs direct', n)
+    if st is not None:
+      _edge_partials(st, ys, cid)
+    del y, ys, yd, xcat
+    # backward-data: 2x2 sums of the first c0 channels into g0, the rest into g1
+    d = O._desc((n, hw, hw, c0 + c1), cout, spec, dtype, 0)
+    g0, g1 = torch.empty_like(x0), torch.empty_like(x1)
+    wpack = O.PackCache.get(w, d, 1)      # held in a local: an uncached pack must outlive the launch
+    O.call('tg_conv2d_upcat_bwd_data', gy.data_ptr(), wpack.data_ptr(), g0.data_ptr(), g1.data_ptr(), n, hw, hw, c0, c1, cout, 0,
+           O._pack_perm(()), O._dt(gy), O._stream())
+    rec.setdefault('upcat_bwd_data', {})[str(n)] = _last_kernel()
+    gc = N.conv2d_bwd_data_gemm(host(gy[sel]), wn, (hw, hw))
+    close(host(g0[sel]), gc[..., :c0].reshape(len(sel), hw // 2, 2, hw // 2, 2, c0).sum(axis=(2, 4)), otol, 'upcat g0', n)
+    close(host(g1[sel]), gc[..., c0:], otol, 'upcat g1', n)
+    with _Direct():
+      gcat = O.conv_bwd_data_raw(gy, w, (n, hw, hw, c0 + c1), spec)
+    r0, r1 = torch.empty_like(g0), torch.empty_like(g1)
+    O.call('tg_upsample2x_concat_bwd', gcat.data_ptr(), r0.data_ptr(), r1.data_ptr(), n, hw // 2, hw // 2, c0, c1, 0,
+           O._pack_perm(()), O._dt(gcat), O._stream())
+    close(host(g0), host(r0), 2 * dtol, 'upcat g0 vs direct', n)      # the composed path rounds the concat-layout gradient first
+    close(host(g1), host(r1), dtol, 'upcat g1 vs direct', n)
+    del g0, g1, r0, r1, gcat
+    # filter gradient
+    wl = w.clone().requires_grad_(True)
+    O.upcat_conv(x0, x1, wl, 0, ()).backward(gy)
+    rec.setdefault('upcat_bwd_weight', {})[str(n)] = _last_kernel()
+    want = sum(N.conv2d_bwd_weight_gemm(cat_of(i), host(gy[i:i + 1]), (3, 3)) for i in range(n))
+    close(host(wl.grad), want, EDGE_F32_TOL, 'upcat bwd_weight', n)
+  _edge_straddles(cid, rec, flips, n_lo, n_hi)
+  _edge_symbols_check(cid, dname, rec)
+
+
+GROUPED_EDGE_CASES = [
+    # id, G, k, padding, hw, cin, cout, n (all groups), forward taken whole, backward-data taken whole, PackCache.refresh check
+    # whole batch and one group both under conv_small's limit: ONE launch that picks the weight set per image
+    ('g2_k1_hw8_under', 2, 1, 'SAME', 8, 32, 32, 64, True, True, False),
+    ('g3_k1_hw8_under', 3, 1, 'SAME', 8, 32, 32, 48, True, True, False),
+    ('g2_k3_hw4_under', 2, 3, 'SAME', 4, 32, 32, 256, True, True, False),
+    ('g3_k3_hw4_under', 3, 3, 'SAME', 4, 32, 32, 240, True, True, False),
+    ('g2_dense_under', 2, 4, 'VALID', 4, 8, 8, 384, True, True, False),
+    # whole batch over, one group under: one launch per group, each on conv_small
+    ('g2_k1_hw8_n96', 2, 1, 'SAME', 8, 32, 32, 96, False, False, True),
+    ('g3_k1_hw8_n96', 3, 1, 'SAME', 8, 32, 32, 96, False, False, False),
+    ('g2_k3_hw4_n264', 2, 3, 'SAME', 4, 32, 32, 264, False, False, False),
+    ('g2_k3_hw4_n384', 2, 3, 'SAME', 4, 32, 32, 384, False, False, True),      # the discriminators' 4x4 layer as a pair at batch 64
+    ('g3_k3_hw4_n600', 3, 3, 'SAME', 4, 32, 32, 600, False, False, False),
+    ('g2_mbstd_c264_n264', 2, 3, 'SAME', 4, 264, 256, 264, False, False, False),      # the minibatch-stddev layer
+    ('g2_dense_n8192', 2, 4, 'VALID', 4, 8, 8, 8192, False, False, True),      # the dense layer: n pixels, forward and backward-data
+    ('g3_dense_n6144', 3, 4, 'VALID', 4, 8, 8, 6144, False, False, False),
+    # whole batch and one group both over: one launch per group on the first-generation kernel
+    ('g2_k1_hw8_over', 2, 1, 'SAME', 8, 32, 32, 130, False, False, False),
+    ('g3_k1_hw8_over', 3, 1, 'SAME', 8, 32, 32, 195, False, False, False),
+    ('g2_k3_hw4_over', 2, 3, 'SAME', 4, 32, 32, 514, False, False, False),
+    ('g2_dense_over', 2, 4, 'VALID', 4, 8, 8, 8194, False, False, False),
+    # tile family: the whole batch reaches the weight-resident kernel's 2048 tiles, one group does not / does / neither
+    ('g2_tile_under', 2, 3, 'SAME', 128, 16, 32, 8, True, True, False),
+    ('g2_tile_n16', 2, 3, 'SAME', 128, 16, 32, 16, False, False, True),
+    ('g3_tile_n24', 3, 3, 'SAME', 128, 16, 32, 24, False, False, False),
+    ('g2_tile_over', 2, 3, 'SAME', 128, 16, 32, 32, False, False, False),
+]
+
+
+@pytest.mark.parametrize('dname', sorted(EDGE_DTYPES))
+@pytest.mark.parametrize('case', GROUPED_EDGE_CASES, ids=[c[0] for c in GROUPED_EDGE_CASES])
+def test_grouped_conv_across_the_dispatch_thresholds(ops, case, dname):
+  """test_grouped_conv_equals_one_call_per_weight_set where the grouped call and its groups sit on different sides of a batch
+  threshold: a grouped call no kernel takes whole is launched once per group on n / G images, and that launch may pick another
+  kernel -- and read another pack layout -- than the whole batch would.  Every entry point equals one call per weight set (bit
+  for bit in the forward / backward-data forms), the forward and the backward-data also match the float64 oracle on the first
+  and last image of every group (so that "grouped == per set" cannot hold by both being wrong), and a registered stacked
+  weight survives PackCache.refresh."""
+  import twingan_amd.ops as O
+  cid, G, k, pad, hw, cin, cout, n, fwd_whole, bwd_whole, refresh = case
+  dtype = EDGE_DTYPES[dname]
+  otol, _ = EDGE_TOL[dtype]
+  spec = O.ConvSpec(k, pad)
+  ho = hw if pad == 'SAME' else hw - k + 1
+  h = n // G
+  x, gy, w2, b2 = _edge_operands(980 + GROUPED_EDGE_CASES.index(case), n, k, hw, ho, cin, cout, dtype, G)
+  epi = O.TG_EPI_BIAS | O.TG_EPI_LRELU
+  rec = {}
+
+  def per_set(fn):
+    return [fn(i, slice(i * h, (i + 1) * h)) for i in range(G)]
+
+  def same(got, parts, name):
+    want = torch.cat(parts)
+    assert got.shape == want.shape, (cid, name)
+    assert torch.equal(got, want), (cid, name, float((got.float() - want.float()).abs().max()), float(want.float().abs().max()))
+
+  def close(got, ref, tol, name):
+    e = rel_l2(got, ref)
+    print('[edge %s] %s %.3e (bound %.1e)' % (cid, name, e, tol))
+    assert e < tol, (cid, name, e, tol)
+
+  def whole(ep, sym, expected):
+    rec[ep] = sym
+    assert sym.endswith(',sets>') == expected, \
+        '%s %s: expected %s, ran %s' % (cid, ep, 'one launch over all weight sets' if expected else 'one launch per group', sym)
+
+  # ---- forward (bias + LeakyReLU) and the forward with the mask epilogue
+  y = O.conv_fwd_raw(x, w2, b2, spec, epi)
+  whole('fwd', _last_kernel(), fwd_whole)
+  same(y, per_set(lambda i, r: O.conv_fwd_raw(x[r].contiguous(), w2[i], b2[i], spec, epi)), 'fwd')
+  ym = O.conv_fwd_masked_raw(x, w2, y, spec)
+  rec['fwd_masked'] = _last_kernel()
+  same(ym, per_set(lambda i, r: O.conv_fwd_masked_raw(x[r].contiguous(), w2[i], y[r].contiguous(), spec)), 'fwd_masked')
+  # ---- backward-data, plain and masked
+  gx = O.conv_bwd_data_raw(gy, w2, tuple(x.shape), spec)
+  whole('bwd_data', _last_kernel(), bwd_whole)
+  same(gx, per_set(lambda i, r: O.conv_bwd_data_raw(gy[r].contiguous(), w2[i], (h,) + tuple(x.shape[1:]), spec)), 'bwd_data')
+  gm = O.conv_bwd_data_masked_raw(gy, w2, x, spec)
+  rec['bwd_data_masked'] = _last_kernel()
+  same(gm, per_set(lambda i, r: O.conv_bwd_data_masked_raw(gy[r].contiguous(), w2[i], x[r].contiguous(), spec)), 'bwd_data_masked')
+  # ---- the oracle on the first and last image of every group
+  for i in range(G):
+    sel = sorted({i * h, (i + 1) * h - 1})
+    wn = host(w2[i])
+    lin = N.conv2d_gemm(host(x[sel]), wn, pad)
+    close(host(y[sel]), N.leaky_relu(lin + host(b2[i])), otol, 'fwd vs oracle, group %d' % i)
+    close(host(ym[sel]), lin * np.where(host(y[sel]) > 0, 1.0, 0.2), otol, 'fwd_masked vs oracle, group %d' % i)
+    ref = N.conv2d_bwd_data_gemm(host(gy[sel]), wn, (hw, hw), pad)
+    close(host(gx[sel]), ref, otol, 'bwd_data vs oracle, group %d' % i)
+    close(host(gm[sel]), ref * np.where(host(x[sel]) > 0, 1.0, 0.2), otol, 'bwd_data_masked vs oracle, group %d' % i)
+  del ym, gm
+  # ---- block ends: pooled output (+ sign bytes), and the backward-data that unpools
+  if k == 3 and pad == 'SAME' and hw >= 16:
+    z, zp = O.conv_fwd_pool_raw(x, w2, b2, spec, epi)
+    rec['fwd_pool'] = _last_kernel()
+    ref = per_set(lambda i, r: O.conv_fwd_pool_raw(x[r].contiguous(), w2[i], b2[i], spec, epi))
+    same(z, [p[0] for p in ref], 'fwd_pool z')
+    same(zp, [p[1] for p in ref], 'fwd_pool pooled')
+    assert O.conv_fwd_pool_signs_supported(x, w2, spec, epi)
+    sg, zp2 = O.conv_fwd_pool_signs_raw(x, w2, b2, spec, epi)
+    rec['fwd_pool_signs'] = _last_kernel()
+    ref = per_set(lambda i, r: O.conv_fwd_pool_signs_raw(x[r].contiguous(), w2[i], b2[i], spec, epi))
+    same(sg, [p[0] for p in ref], 'fwd_pool_signs bits')
+    same(zp2, [p[1] for p in ref], 'fwd_pool_signs pooled')
+    gzp = gy[:, ::2, ::2, :].contiguous()
+    out = O.conv_bwd_data_unpool_raw(gzp, sg, w2, x, tuple(x.shape), spec, True)
+    assert out is not None
+    rec['bwd_data_unpool'] = _last_kernel()
+    ref = per_set(lambda i, r: O.conv_bwd_data_unpool_raw(gzp[r].contiguous(), sg[r].contiguous(), w2[i], x[r].contiguous(),
+                                                          (h,) + tuple(x.shape[1:]), spec, True))
+    same(out[0], [p[0] for p in ref], 'unpool gx')
+    same(out[1], [p[1] for p in ref], 'unpool kept gradient')
+    del z, zp, sg, zp2, out, ref
+  # ---- filter (+ bias) gradients into zeroed stacked sinks: the bound of test_grouped_conv_equals_one_call_per_weight_set
+  tol = 2e-5
+  gw = O.conv_bwd_weight_raw(x, gy, spec, groups=G)
+  ref = torch.stack(per_set(lambda i, r: O.conv_bwd_weight_raw(x[r].contiguous(), gy[r].contiguous(), spec)))
+  assert gw.shape == ref.shape
+  close(host(gw), host(ref), tol, 'bwd_weight')
+  sink, bsink = torch.zeros_like(w2), torch.zeros_like(b2)
+  O.conv_bwd_weight_raw(x, gy, spec, out=sink, gbias=bsink)
+  close(host(sink), host(ref), tol, 'bwd_weight_bias')
+  close(host(bsink), host(gy.float().reshape(G, -1, cout).sum(1)), 1e-3, 'bwd_weight_bias bias')
+  if O.conv_bwd_weight2_raw(x, gy, x, gy, spec, sink, bsink, 3):      # two segments, both grouped
+    close(host(sink), 3.0 * host(ref), tol, 'bwd_weight2')
+  del gw, ref, sink, bsink
+  # ---- a registered stacked weight: packs made by get(), re-made in place by refresh() after the weights moved
+  if refresh:
+    O.PackCache.register(w2)
+    try:
+      O.conv_fwd_raw(x, w2, b2, spec, epi)
+      O.conv_bwd_data_raw(gy, w2, tuple(x.shape), spec)
+      with torch.no_grad():
+        w2.mul_(1.5)
+      O.PackCache.version += 1
+      assert O.PackCache.refresh([w2]) >= 2
+      same(O.conv_fwd_raw(x, w2, b2, spec, epi),
+           per_set(lambda i, r: O.conv_fwd_raw(x[r].contiguous(), w2[i].clone(), b2[i], spec, epi)), 'fwd after refresh')
+      same(O.conv_bwd_data_raw(gy, w2, tuple(x.shape), spec),
+           per_set(lambda i, r: O.conv_bwd_data_raw(gy[r].contiguous(), w2[i].clone(), (h,) + tuple(x.shape[1:]), spec)),
+           'bwd_data after refresh')
+    finally:
+      O.PackCache.unregister(w2)
+  _edge_symbols_check(cid, dname, rec)
+
+
+def _lockstep_cases():
+  out = []
+  for cid, k, pad, hw, cin, cout, n_lo, n_hi, _ in EDGE_CASES:
+    out += [('%s_n%d' % (cid, n), 1, k, pad, hw, hw, cin, cout, n) for n in (n_lo, n_hi)]
+  for cid, G, k, pad, hw, cin, cout, n, _, _, _ in GROUPED_EDGE_CASES:
+    out.append((cid, G, k, pad, hw, hw, cin, cout, n))
+  for n, h, w, cin, cout, k, pad in MFMA_CASES:
+    out.append(('mfma_n%d_%dx%d_c%d_%d_k%d' % (n, h, w, cin, cout, k), 1, k, pad, h, w, cin, cout, n))
+  return out
+
+
+LOCKSTEP_CASES = _lockstep_cases()
+
+
+@pytest.mark.parametrize('case', LOCKSTEP_CASES, ids=[c[0] for c in LOCKSTEP_CASES])
+def test_pack_layout_follows_the_kernel_that_runs(ops, case):
+  """tg_conv2d_pack_layout(desc, mode) re-derives where tg_conv2d_fwd (mode 0) / tg_conv2d_bwd_data (mode 1) will end: it
+  must say "fragment order" exactly when the kernel that then runs is conv_img_kernel or conv_small_kernel, the two that
+  read such packs -- for a grouped descriptor launched once per group, the kernel of the per-group launch."""
+  import twingan_amd.ops as O
+  from twingan_amd import _lib
+  cid, G, k, pad, h, w, cin, cout, n = case
+  spec = O.ConvSpec(k, pad)
+  ho, wo = spec.out_hw(h, w)
+  d = O._desc((n, h, w, cin), cout, spec, torch.bfloat16, 0, G)
+  assert d.algo == _lib.TG_ALGO_MFMA
+  x = torch.zeros(n, h, w, cin, dtype=torch.bfloat16, device=dev())
+  gy = torch.zeros(n, ho, wo, cout, dtype=torch.bfloat16, device=dev())
+  wt = torch.zeros(((G,) if G > 1 else ()) + (k, k, cin, cout), device=dev())
+  for mode in (0, 1):
+    if mode == 0:
+      O.conv_fwd_raw(x, wt, None, spec, 0)
+    else:
+      O.conv_bwd_data_raw(gy, wt, tuple(x.shape), spec)
+    sym = _last_kernel()
+    frag = int(sym.startswith(('conv_img_kernel', 'conv_small_kernel')))
+    assert _lib.load().tg_conv2d_pack_layout(ctypes.byref(d), mode) == frag, \
+        '%s mode %d: pack layout %d, but the pack is read by %s' % (cid, mode, 1 - frag, sym)

@@ -558,3 +558,62 @@ def test_native_normalisers_refuse_what_the_reference_refuses():
   assert norm_var('a/Conv', 'InstanceNorm', 'beta', '') == 'a/Conv/InstanceNorm/beta'
   with pytest.raises(NotImplementedError):
     declare_twingan(ParamStore('cpu'), Config(hw=8, max_ch=8, generator_norm_type='group_norm'))
+
+
+def test_d_conv_keeps_a_stacked_kernel_off_the_pointwise_path(monkeypatch):
+  """pggan._d_conv: the channel counts of a conv kernel are its LAST two dims -- a stacked [2, kh, kw, cin, cout] pair of 1x1
+  kernels (ParamStore.pairs) goes to the grouped conv whatever its width (the pointwise kernels take one weight set), a plain
+  narrow 1x1 kernel still goes to the pointwise kernels."""
+  from twingan_amd import Config, pggan
+  calls = []
+  monkeypatch.setattr(pggan.ops, 'pointwise_conv', lambda x, w, b, lrelu=False: calls.append(('pointwise', tuple(w.shape))))
+  monkeypatch.setattr(pggan.ops, 'conv2d', lambda x, w, b, k, padding, **kw: calls.append(('conv2d', tuple(w.shape))))
+
+  class Params(dict):
+    pairs = {}
+  P = Params()
+  cfg = Config(hw=64, max_ch=16)
+  x = torch.zeros(4, 8, 8, 16)
+  for cin, cout in ((16, 16), (3, 16), (16, 3)):
+    scope = '%s/layer_%d_%d/Conv' % (pggan.PAIR_TOP, cin, cout)
+    P.pairs[scope + '/weights'], P.pairs[scope + '/biases'] = torch.zeros(2, 1, 1, cin, cout), torch.zeros(2, cout)
+    pggan._d_conv(P, scope, x, cfg, k=1)
+    assert calls.pop() == ('conv2d', (2, 1, 1, cin, cout))
+  for cin, cout, want in ((3, 16, 'pointwise'), (16, 3, 'pointwise'), (16, 16, 'conv2d')):
+    scope = 'discriminator_s/layer_%d_%d/Conv' % (cin, cout)
+    P[scope + '/weights'], P[scope + '/biases'] = torch.zeros(1, 1, cin, cout), torch.zeros(cout)
+    pggan._d_conv(P, scope, x, cfg, k=1)
+    assert calls.pop() == (want, (1, 1, cin, cout))
+  assert not calls
+
+
+def test_discriminator_pair_needs_every_tail_layer_stacked(monkeypatch):
+  """pggan.discriminator_pair_supported: the grouped tail reads P.pairs for every conv from PAIR_HW down; ParamStore.build may
+  leave a twin unstacked (sizes, phases), and then the per-domain path must be taken -- not a KeyError in the middle of a
+  step.  pair_tail_scopes lists exactly the scopes the tail asks _d_conv for."""
+  from twingan_amd import Config, pggan
+  from twingan_amd.params import ParamStore, declare_twingan
+  monkeypatch.setattr(pggan, 'USE_DISCRIMINATOR_PAIR', True)
+  cfg = Config(hw=64, max_ch=32)
+  P = declare_twingan(ParamStore('cpu'), cfg).build(seed=0).P
+  scopes = pggan.pair_tail_scopes(cfg, cfg.hw)
+  assert pggan.discriminator_pair_supported(P, cfg, cfg.hw)
+  # the scopes the tail really visits
+  seen = []
+
+  def fake_d_conv(P, scope, x, cfg, k=3, padding='SAME', pool=False, **kw):
+    seen.append(scope)
+    cout = P.pairs[scope + '/weights'].shape[-1]
+    n, h = x.shape[0], x.shape[1] if padding == 'SAME' else x.shape[1] - k + 1
+    return (None, torch.zeros(n, h // 2, h // 2, cout)) if pool else torch.zeros(n, h, h, cout)
+  monkeypatch.setattr(pggan, '_d_conv', fake_d_conv)
+  monkeypatch.setattr(pggan.ops, 'minibatch_state_concat', lambda x, cpad, groups=1: torch.zeros(x.shape[:3] + (cpad,)))
+  net = torch.zeros(4, pggan.PAIR_HW, pggan.PAIR_HW, P.pairs[scopes[0] + '/weights'].shape[-2])
+  pggan.discriminator_before_fc(P, net, cfg, pggan.PAIR_TOP, 2, None, False, from_hw=pggan.PAIR_HW, full_hw=cfg.hw)
+  assert seen == scopes
+  # one tail layer without its stacked view: not supported (and nothing else changes the answer)
+  for name in (scopes[0] + '/weights', scopes[-1] + '/biases'):
+    saved = P.pairs.pop(name)
+    assert not pggan.discriminator_pair_supported(P, cfg, cfg.hw)
+    P.pairs[name] = saved
+    assert pggan.discriminator_pair_supported(P, cfg, cfg.hw)

@@ -465,7 +465,19 @@ bool tg_conv_small_supported(int n, int hout, int wout, int kh, int kw);
 // conv_small (tg_conv2d_fwd_mfma / tg_conv2d_bwd_data_mfma: the tile kernels first, then conv_img, then conv_small) --
 // the two kernels that fetch their weight fragments straight from L2: the layout is a property of the pack that its
 // kernel knows; callers treat packs as opaque.  (conv_small's test involves the batch: n * hout * wout <= 4096.)
-static bool pack_frag(const TgConvDesc* d0, int mode) {
+// A grouped descriptor (groups > 1) that no kernel takes whole is launched once per group on n / groups images (capi.hip):
+// its packs are read by THAT dispatch, so the question is asked of the one-group descriptor -- the whole batch can be over
+// conv_small's limit while one group is under it.
+bool tg_conv2d_grouped_native_mfma(const TgConvDesc* d0, int op);
+static bool pack_frag(const TgConvDesc* dg, int mode) {
+  TgConvDesc d1;
+  const TgConvDesc* d0 = dg;
+  if (dg->groups > 1) {
+    d1 = *dg;
+    if (!tg_conv2d_grouped_native_mfma(dg, mode)) d1.n = dg->n / dg->groups;      // mode 0 / 1 = TG_GRP_FWD / TG_GRP_DGRAD
+    d1.groups = 1;
+    d0 = &d1;
+  }
   TgConvDesc dd;
   const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
   if (!is16(d) || d->algo != TG_ALGO_MFMA || d->kh != d->kw || (d->kh != 3 && d->kh != 1) || d->cin % 8 || d->cout % 8) return false;
@@ -593,7 +605,8 @@ int tg_pack_table_fill(const TgConvDesc* d, const float* w, int mode, void* out,
                        int32_t* total_blocks) {
   TG_CHECK(d && w && out && table_host && total_blocks && job >= 0, TG_EINVAL, "tg_pack_table_fill: bad arguments");
   TG_CHECK(mode == 0 || mode == 1, TG_EINVAL, "tg_pack_table_fill: mode %d", mode);
-  TG_CHECK(d->groups <= 1, TG_EINVAL, "tg_pack_table_fill: one job per weight set (fill each set of a grouped descriptor as its own job)");
+  // a grouped descriptor: ONE weight set's job per call (w / out point at that set's master / pack); the element order is
+  // the grouped call's (pack_frag), the one tg_conv2d_pack_weights writes for the same descriptor
   PackJob j;
   j.w = w;
   j.out = (bf16*)out;

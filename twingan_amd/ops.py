@@ -164,11 +164,10 @@ class PackCache:
       for k in keys:
         ent = cls._packs[k]
         g = max(int(ent[2].groups), 1)
-        d1 = TgConvDesc()
-        ctypes.pointer(d1)[0] = ent[2]
-        d1.groups = 1
+        d1 = ent[2]
         # weight set i of a stacked kernel (params.ParamStore.pairs): its master starts i sets after the first, its pack i
-        # packs after the first; one job per set
+        # packs after the first; one job per set, each filled from the GROUPED descriptor get() packed with (the element
+        # order of a grouped call's packs is the library's to choose: it depends on how that call is launched)
         wset, per = 4 * d1.kh * d1.kw * d1.cin * d1.cout, k[2] // g
         for i in range(g):
           call('tg_pack_table_fill', ctypes.byref(d1), k[0] + i * wset, k[1], ent[1].data_ptr() + i * per * ent[1].element_size(), j,

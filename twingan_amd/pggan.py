@@ -531,7 +531,8 @@ def _d_conv(P, scope, x, cfg, k=3, padding='SAME', pool=False, in_ch=None, sole_
     w = _sn(P, scope, cfg, True)
     b = P[scope + '/biases']
   x = _equalize(x, cfg, k, in_ch)      # in_ch: logical channel count when x is channel-padded (minibatch stddev)
-  if k == 1 and (w.shape[2] <= 4 or w.shape[3] <= 4):
+  # the kernel is [kh, kw, cin, cout] or a stacked [2, kh, kw, cin, cout] pair: the pointwise kernels take one weight set
+  if k == 1 and w.dim() == 4 and (w.shape[-2] <= 4 or w.shape[-1] <= 4):
     return ops.pointwise_conv(x, w, b, lrelu=True)
   # sole_consumer: nothing else reads x, so (when x is the previous conv's LeakyReLU output and no input scaling sits
   # in between) that layer's LeakyReLU backward is folded into this conv's backward-data
@@ -804,13 +805,31 @@ def discriminator(P, source, cfg, top, groups=1, cut_seg=None, block_end_points=
 USE_DISCRIMINATOR_PAIR = __import__('os').environ.get('TG_D_PAIR', '0') == '1'
 
 
+def pair_tail_scopes(cfg, hw):
+  """Scopes (under PAIR_TOP) of the convs discriminator_pair_tail runs for a discriminator over hw x hw images: the two
+  convs of every block from PAIR_HW down and the two after the minibatch stddev (discriminator_before_fc with from_hw)."""
+  max_stage = max_stage_of(hw)
+  max_ch = cfg.max_ch_dis or cfg.max_ch
+  scopes = []
+  for stage in range(max_stage, 0, -1):
+    current_hw = hw // (2 ** (max_stage - stage))
+    if current_hw <= PAIR_HW:
+      name = 'encoder_block_%dx%dx%d' % (current_hw, current_hw, get_num_channels(stage - 1, max_ch))
+      scopes += ['%s/%s/Conv' % (PAIR_TOP, name), '%s/%s/Conv_1' % (PAIR_TOP, name)]
+  blk = 'before_fc_1x1x%d' % max_ch
+  return scopes + ['%s/%s/Conv' % (PAIR_TOP, blk), '%s/%s/Conv_1' % (PAIR_TOP, blk)]
+
+
 def discriminator_pair_supported(P, cfg, hw):
   """Can discriminator_s and discriminator_t run their layers at <= PAIR_HW as grouped launches?  The plain tower only:
-  every option that reads more than (kernel, bias) per layer keeps the per-domain path."""
-  return bool(USE_DISCRIMINATOR_PAIR and getattr(P, 'pairs', None) and hw > PAIR_HW and not cfg.spectral_norm
-              and not cfg.equalized_learning_rate and not cfg.use_res_block and not (cfg.do_dgrop and cfg.is_training)
-              and not (cfg.do_self_attention and cfg.self_attention_hw <= PAIR_HW)
-              and not (cfg.is_growing and hw // 2 <= PAIR_HW))
+  every option that reads more than (kernel, bias) per layer keeps the per-domain path -- and so does a tail in which
+  ParamStore.build could not lay some layer's twin variables out as one stacked tensor (P.pairs)."""
+  if not (USE_DISCRIMINATOR_PAIR and getattr(P, 'pairs', None) and hw > PAIR_HW and not cfg.spectral_norm
+          and not cfg.equalized_learning_rate and not cfg.use_res_block and not (cfg.do_dgrop and cfg.is_training)
+          and not (cfg.do_self_attention and cfg.self_attention_hw <= PAIR_HW)
+          and not (cfg.is_growing and hw // 2 <= PAIR_HW)):
+    return False
+  return all(s + v in P.pairs for s in pair_tail_scopes(cfg, hw) for v in ('/weights', '/biases'))
 
 
 def discriminator_pair(P, source_s, source_t, cfg, groups=1, cut_seg=None, streams=None, meanwhile=None):
