@@ -11,10 +11,16 @@ Tolerances: bf16 outputs (forward, backward-data) rel-L2 <= 4e-3 vs the oracle (
 1.1e-3) on the first and last image of the batch, and <= 2e-3 vs the direct (one-thread-per-output) kernel over the
 WHOLE tensor; fp32 outputs (filter and bias gradients, fp32 accumulation of exact bf16 products) rel-L2 <= 1e-4 vs the
 oracle over the whole batch.  SURVEY.md 8c asks 1e-2 / 3e-2.
+
+Beside every rel-L2 figure stands an ELEMENT-WISE check (tests/elementwise.py: the bounds and their derivation;
+tests/test_elementwise_cpu.py: planted faults that pass the rel-L2 thresholds above and fail it): every element of the
+first, the last and one seeded middle image against the float64 oracle, the tile kernels against the direct kernels over the
+WHOLE batch on the device, the fp32 filter and bias gradients against the oracle.
 """
 import json
 import os
 import re
+import zlib
 
 import numpy as np
 import pytest
@@ -23,6 +29,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import np_ops as N          # noqa: E402  (checker only)
+import elementwise as E                 # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 with open(os.path.join(HERE, 'golden', 'bench_dispatch_shapes.json')) as _fh:
@@ -67,6 +74,45 @@ def _check_partials(st, y, key):
   e1 = float(((part[:, 0] - s1).abs() / (s2 * h * w).sqrt().clamp_min(1e-30)).max())
   e2 = float((part[:, 1] / s2.clamp_min(1e-30) - 1).abs().max())
   assert e1 < 2e-6 and e2 < 2e-6, ('statistics partials', key, e1, e2)
+
+
+def _middle(key, n):
+  """One image of 1 .. n-2, seeded by the case: the images a first / last check never meets."""
+  return 1 + zlib.crc32(('%s:%d' % (key, n)).encode()) % (n - 2)
+
+
+class _Oracle:
+  """float64 oracle values per IMAGE of one layer, computed once whichever entry point or batch size asks: the forward
+  conv and conv(|x|, |w|), the backward-data and conv_bwd_data(|gy|, |w|) (the magnitude terms of the bounds)."""
+
+  def __init__(self, x, gy, wn, pad, hin):
+    self.x, self.gy, self.wn, self.pad, self.hin = x, gy, wn, pad, hin
+    self.cache = {'fwd': {}, 'bwd': {}}
+
+  def _get(self, kind, sel):
+    c = self.cache[kind]
+    miss = [i for i in sel if i not in c]
+    if miss:
+      if kind == 'fwd':
+        a = host(self.x[miss])
+        ref, mag = N.conv2d_gemm(a, self.wn, self.pad), N.conv2d_gemm(np.abs(a), np.abs(self.wn), self.pad)
+      else:
+        a = host(self.gy[miss])
+        ref = N.conv2d_bwd_data_gemm(a, self.wn, (self.hin, self.hin), self.pad)
+        mag = N.conv2d_bwd_data_gemm(np.abs(a), np.abs(self.wn), (self.hin, self.hin), self.pad)
+      for j, i in enumerate(miss):
+        c[i] = (ref[j], mag[j])
+    return np.stack([c[i][0] for i in sel]), np.stack([c[i][1] for i in sel])
+
+  def fwd(self, sel):
+    return self._get('fwd', sel)
+
+  def bwd(self, sel):
+    return self._get('bwd', sel)
+
+
+def _ratio(what, dtype, r):
+  print('[elementwise] %-28s %-8s worst ratio %.3f' % (what, str(dtype).replace('torch.', ''), r))
 
 
 class _Direct:
@@ -130,20 +176,45 @@ def _conv_variants(key, dtype):
   pad = 'VALID' if valid else 'SAME'
 
   # ---- forward: both epilogues (generator / encoder: none; discriminator: bias + LeakyReLU)
+  orc = _Oracle(x, gy, wn, pad, hin)
+  KF, KB = k * k * cin, k * k * cout      # summands of one output element, forward / backward-data
+  bias_abs = bias.abs().view(1, 1, 1, cout)
+
+  def sel3(n):      # first, last and one seeded middle image
+    return sorted({0, n - 1} | ({_middle(key, n)} if n > 2 else set()))
+
+  def fwd_mag(i0, i1, with_bias=False):
+    m = E.conv_mag_device(x[i0:i1], w, pad)
+    return m + bias_abs if with_bias else m
+
+  def bwd_mag(i0, i1):
+    return E.conv_mag_device(gy[i0:i1], w, pad, transpose=True)
+
+  def fwd_bound(ref, mag, epi):
+    # bias add and slope multiply: two more fp32 operations on the sum (K + 2, |bias| joins the magnitudes); LeakyReLU is
+    # 1-Lipschitz, so the bound of the pre-activation carries over
+    return E.conv_bound(ref, mag + np.abs(bn) if epi else mag, KF + 2 if epi else KF, dtype)
+
   for n in (int(v) for v in eps.get('tg_conv2d_fwd', [])):
     sel = sorted({0, n - 1})
-    xs = host(x[sel])
-    lin = N.conv2d_gemm(xs, wn, pad)
-    for epi, ref in ((0, lin), (TG_EPI_BIAS | TG_EPI_LRELU, N.leaky_relu(lin + bn))):
+    s3 = sel3(n)
+    lin3, mag3 = orc.fwd(s3)
+    lin = lin3[[s3.index(i) for i in sel]]
+    for epi, ref, ref3 in ((0, lin, lin3), (TG_EPI_BIAS | TG_EPI_LRELU, N.leaky_relu(lin + bn), N.leaky_relu(lin3 + bn))):
       y = O.conv_fwd_raw(x[:n], w, bias if epi else None, spec, epi)
       note(key, 'tg_conv2d_fwd', str(n))
       e = rel_l2(host(y[sel]), ref)
       assert e < BF16_OUT_TOL, ('fwd', key, n, epi, e)
+      _ratio('conv fwd', dtype, E.assert_elementwise(host(y[s3]), ref3, fwd_bound(ref3, mag3, epi),
+                                                     'fwd %s n%d epi%d images %s' % (key, n, epi, s3)))
       with _Direct():
         yd = O.conv_fwd_raw(x[:n], w, bias if epi else None, spec, epi)
       if epi == 0:      # with LeakyReLU a 1-ulp difference across zero is a 5x jump of the element: linear part only
         e = rel_l2(host(y), host(yd))
         assert e < VS_DIRECT_TOL, ('fwd vs direct', key, n, e)
+      # element by element both epilogues can be compared: |lrelu(a) - lrelu(b)| <= |a - b|
+      _ratio('conv fwd vs direct', dtype, E.assert_pair_device(
+          y, yd, lambda i0, i1: fwd_mag(i0, i1, bool(epi)), KF + 2 if epi else KF, 'fwd vs direct %s n%d epi%d' % (key, n, epi)))
       del y, yd
 
   # ---- forward with the statistics epilogue (every normalised encoder / generator conv): the same tensor as the plain
@@ -153,12 +224,17 @@ def _conv_variants(key, dtype):
     note(key, 'tg_conv2d_fwd_stats', str(n))
     assert st is not None, ('no statistics epilogue', key, n)
     sel = sorted({0, n - 1})
-    e = rel_l2(host(y[sel]), N.conv2d_gemm(host(x[sel]), wn, pad))
+    s3 = sel3(n)
+    lin3, mag3 = orc.fwd(s3)
+    e = rel_l2(host(y[sel]), lin3[[s3.index(i) for i in sel]])
     assert e < BF16_OUT_TOL, ('fwd_stats', key, n, e)
+    _ratio('conv fwd_stats', dtype, E.assert_elementwise(host(y[s3]), lin3, fwd_bound(lin3, mag3, 0),
+                                                         'fwd_stats %s n%d images %s' % (key, n, s3)))
     with _Direct():
       yd = O.conv_fwd_raw(x[:n], w, None, spec, 0)
     e = rel_l2(host(y), host(yd))
     assert e < VS_DIRECT_TOL, ('fwd_stats vs direct', key, n, e)
+    _ratio('conv fwd_stats vs direct', dtype, E.assert_pair_device(y, yd, fwd_mag, KF, 'fwd_stats vs direct %s n%d' % (key, n)))
     _check_partials(st, y, key)
     del y, yd
 
@@ -171,11 +247,22 @@ def _conv_variants(key, dtype):
     z_plain = O.conv_fwd_raw(x[:n], w, bias, spec, epi)
     assert torch.equal(z, z_plain), ('fwd_pool z', key, n)
     sel = sorted({0, n - 1})
-    e = rel_l2(host(z[sel]), N.leaky_relu(N.conv2d_gemm(host(x[sel]), wn, pad) + bn))
+    s3 = sel3(n)
+    lin3, mag3 = orc.fwd(s3)
+    ref3 = N.leaky_relu(lin3 + bn)
+    e = rel_l2(host(z[sel]), ref3[[s3.index(i) for i in sel]])
     assert e < BF16_OUT_TOL, ('fwd_pool', key, n, e)
+    zb = fwd_bound(ref3, mag3, epi)
+    _ratio('conv fwd_pool z', dtype, E.assert_elementwise(host(z[s3]), ref3, zb, 'fwd_pool z %s n%d images %s' % (key, n, s3)))
     want = z.float().view(n, hw // 2, 2, hw // 2, 2, cout).mean(dim=(2, 4))
     e = rel_l2(host(zp), host(want))
     assert e < 2e-3, ('fwd_pool pooled', key, n, e)      # one bf16 rounding of the pooled value
+    # the pooled tensor against the oracle's pool: the mean of four STORED z (each within its own bound), rounded once more
+    pool4 = lambda a: a.reshape(len(s3), hw // 2, 2, hw // 2, 2, cout).mean(axis=(2, 4))
+    pref = pool4(ref3)
+    u_st = E.unit_roundoff(dtype)
+    _ratio('conv fwd_pool pooled', dtype, E.assert_elementwise(
+        host(zp[s3]), pref, u_st * np.abs(pref) + (1 + u_st) * pool4(zb) + E.tiny(dtype), 'fwd_pool pooled %s n%d images %s' % (key, n, s3)))
     # the sign-bit form of the same launch (tg_conv2d_fwd_pool_signs: what the discriminators' first-order passes run):
     # the very same pooled tensor, and bit j of byte q = (z[.., 8q+j] > 0) of the z the plain launch stored
     assert O.conv_fwd_pool_signs_supported(x[:n], w, spec, epi), ('no sign-bit variant', key, n)
@@ -197,15 +284,24 @@ def _conv_variants(key, dtype):
   for ep in ('tg_conv2d_bwd_data', 'tg_conv2d_bwd_data_masked'):
     for n in (int(v) for v in eps.get(ep, [])):
       sel = sorted({0, n - 1})
-      ref = N.conv2d_bwd_data_gemm(host(gy[sel]), wn, (hin, hin), pad)
+      s3 = sel3(n)
+      ref3, mag3 = orc.bwd(s3)
+      kb, extra = KB, None
       if ep.endswith('masked'):
         gx = O.conv_bwd_data_masked_raw(gy[:n], w, x[:n], spec)
-        ref = ref * np.where(host(x[sel]) > 0, 1.0, 0.2)
+        slope = np.where(host(x[s3]) > 0, 1.0, 0.2)      # the mask comes from an INPUT: exact, no alternates
+        ref3, mag3, kb = ref3 * slope, mag3 * slope, KB + 1      # the slope multiply in fp32: one more operation
+        # where the mask is not fusable (capi.hip: "plain backward-data, then the mask in place") the stored value is masked
+        # and stored again: a second rounding, u |ref|, of the elements whose slope is not 1
+        extra = (1 + E.unit_roundoff(dtype)) * E.unit_roundoff(dtype) * np.abs(ref3) * (slope != 1.0)
       else:
         gx = O.conv_bwd_data_raw(gy[:n], w, (n, hin, hin, cin), spec)
+      ref = ref3[[s3.index(i) for i in sel]]
       note(key, ep, str(n))
       e = rel_l2(host(gx[sel]), ref)
       assert e < BF16_OUT_TOL, (ep, key, n, e)
+      _ratio('conv ' + ep[10:], dtype, E.assert_elementwise(host(gx[s3]), ref3, E.conv_bound(ref3, mag3, kb, dtype, extra),
+                                                            '%s %s n%d images %s' % (ep, key, n, s3)))
       with _Direct():
         gd = O.conv_bwd_data_raw(gy[:n], w, (n, hin, hin, cin), spec)
         if ep.endswith('masked'):
@@ -213,6 +309,9 @@ def _conv_variants(key, dtype):
       e = rel_l2(host(gx), host(gd))
       # the direct kernel rounds once more before the mask: 2 roundings apart
       assert e < (2 * VS_DIRECT_TOL if ep.endswith('masked') else VS_DIRECT_TOL), (ep + ' vs direct', key, n, e)
+      # masked: either route may store the unmasked gradient and mask the stored value -- two roundings on each side
+      _ratio('conv %s vs direct' % ep[10:], dtype, E.assert_pair_device(
+          gx, gd, bwd_mag, kb, '%s vs direct %s n%d' % (ep, key, n), roundings=4 if ep.endswith('masked') else 2))
       del gx, gd
 
   # ---- filter gradients (fp32): single batch, with the bias gradient, two segments
@@ -220,6 +319,8 @@ def _conv_variants(key, dtype):
   if wg_eps:
     per = N.conv2d_bwd_weight_gemm(host(x), host(gy), (k, k), pad, per_image=True)      # [64, k, k, cin, cout]
     bsum = host(gy).sum(axis=(1, 2))                                                       # [64, cout]
+    per_mag = N.conv2d_bwd_weight_gemm(np.abs(host(x)), np.abs(host(gy)), (k, k), pad, per_image=True)
+    bmag = np.abs(host(gy)).sum(axis=(1, 2))
     for ep in wg_eps:
       for nn in eps[ep]:
         parts = [int(v) for v in nn.split('+')]
@@ -229,7 +330,7 @@ def _conv_variants(key, dtype):
         if len(parts) == 1:
           gw = O.conv_bwd_weight_raw(x[:n], gy[:n], spec, gbias=gb)
           note(key, ep, nn)
-          bias_ref = bsum[:n].sum(0)
+          bias_ref, bias_mag, bias_n = bsum[:n].sum(0), bmag[:n].sum(0), n
         else:
           a = parts[0]
           gw = torch.zeros((k, k, cin, cout), dtype=torch.float32, device='cuda')
@@ -237,12 +338,17 @@ def _conv_variants(key, dtype):
           ok = O.conv_bwd_weight2_raw(x[:a], gy[:a], x[a:n], gy[a:n], spec, gw, gb, 1 if want_b else 3)
           assert ok, ('two-segment filter gradient refused', key, nn)
           note(key, ep, nn)
-          bias_ref = bsum[:a].sum(0)
+          bias_ref, bias_mag, bias_n = bsum[:a].sum(0), bmag[:a].sum(0), a
         e = rel_l2(host(gw), per[:n].sum(0))
         assert e < F32_OUT_TOL, (ep, key, nn, e)
+        # fp32 sums of exact products over P = n ho wo pixels, any order (split-K slabs, atomics, the two segments)
+        _ratio('conv bwd_weight', dtype, E.assert_elementwise(
+            host(gw), per[:n].sum(0), E.wgrad_bound(per[:n].sum(0), per_mag[:n].sum(0), n * hw * hw), '%s %s n%s' % (ep, key, nn)))
         if want_b:
           e = rel_l2(host(gb), bias_ref)
           assert e < F32_OUT_TOL, (ep + ' bias', key, nn, e)
+          _ratio('conv bias gradient', dtype, E.assert_elementwise(
+              host(gb), bias_ref, E.wgrad_bound(bias_ref, bias_mag, bias_n * hw * hw), '%s bias %s n%s' % (ep, key, nn)))
         del gw
 
 
@@ -275,9 +381,14 @@ def test_upcat_conv_at_bench_shapes(key):
   def cat_of(i):      # the materialised input of image i
     up = np.repeat(np.repeat(host(x0[i:i + 1]), 2, axis=1), 2, axis=2)
     return np.concatenate([up, host(x1[perm[i // gsz] * gsz + i % gsz][None])], axis=3)
-  for i in (0, gsz + 3, n - 1):
-    e = rel_l2(host(y[i:i + 1]), N.conv2d_gemm(cat_of(i), wn))
+  K, dt = 9 * (c0 + c1), torch.bfloat16
+  for i in (0, gsz + 3, _middle(key, n), n - 1):
+    ref = N.conv2d_gemm(cat_of(i), wn)
+    e = rel_l2(host(y[i:i + 1]), ref)
     assert e < BF16_OUT_TOL, ('upcat fwd', key, i, e)
+    mag = N.conv2d_gemm(np.abs(cat_of(i)), np.abs(wn))
+    _ratio('upcat conv fwd', dt, E.assert_elementwise(host(y[i:i + 1]), ref, E.conv_bound(ref, mag, K, dt),
+                                                      'upcat fwd %s image %d' % (key, i)))
   y.backward(gy)
   _note(key, 'tg_conv2d_upcat_bwd_weight', str(n))      # the filter gradient is the last conv launch of the backward
   gyn = host(gy)
@@ -286,16 +397,38 @@ def test_upcat_conv_at_bench_shapes(key):
     ref += N.conv2d_bwd_weight_gemm(cat_of(i), gyn[i:i + 1], (3, 3))
   e = rel_l2(host(w.grad), ref)
   assert e < F32_OUT_TOL, ('upcat wgrad', key, e)
+  wmag = np.zeros_like(wn)
+  for i in range(n):
+    wmag += N.conv2d_bwd_weight_gemm(np.abs(cat_of(i)), np.abs(gyn[i:i + 1]), (3, 3))
+  _ratio('upcat conv bwd_weight', dt, E.assert_elementwise(host(w.grad), ref, E.wgrad_bound(ref, wmag, n * hw * hw),
+                                                           'upcat wgrad %s' % key))
   # input gradients: backward-data over the concat layout, split into the two sources (skip groups summed: every
   # encoder image is read by two generator passes)
   gcat0 = N.conv2d_bwd_data_gemm(gyn[:1], wn, (hw, hw))
   g0_ref = gcat0[..., :c0].reshape(1, hw // 2, 2, hw // 2, 2, c0).sum(axis=(2, 4))
   e = rel_l2(host(x0.grad[:1]), g0_ref)
   assert e < 2 * BF16_OUT_TOL, ('upcat gx0', key, e)
+  # element-wise, image 0 and a middle image.  The fused backward-data sums the 2x2 block (up source) and the two reading
+  # passes (skip source) in its fp32 accumulators and rounds ONCE: K = 4 x 9 cout and 2 x 9 cout summands.  The composed
+  # route (small maps, USE_UPCAT_BWD_FUSED off) stores the concat-layout gradient first: u |g| of every summed element more.
+  KB, u_st = 9 * cout, E.unit_roundoff(dt)
+  composed = not (O.USE_UPCAT_BWD_FUSED and hw >= 16)
+  quad = lambda a: a[..., :c0].reshape(1, hw // 2, 2, hw // 2, 2, c0).sum(axis=(2, 4))
+  for i in (0, _middle(key, n)):
+    gc = N.conv2d_bwd_data_gemm(gyn[i:i + 1], wn, (hw, hw))
+    gm = N.conv2d_bwd_data_gemm(np.abs(gyn[i:i + 1]), np.abs(wn), (hw, hw))
+    extra = u_st * quad(np.abs(gc)) if composed else None
+    _ratio('upcat conv bwd_data up', dt, E.assert_elementwise(
+        host(x0.grad[i:i + 1]), quad(gc), E.conv_bound(quad(gc), quad(gm), 4 * KB, dt, extra), 'upcat gx0 %s image %d' % (key, i)))
   j = 5                                            # skip image 5 (group 0) is read by output groups 1 and 2
   tot = sum(N.conv2d_bwd_data_gemm(gyn[i:i + 1], wn, (hw, hw))[..., c0:] for i in (gsz + j, 2 * gsz + j))
   e = rel_l2(host(x1.grad[j:j + 1]), tot)
   assert e < 2 * BF16_OUT_TOL, ('upcat gx1', key, e)
+  parts = [N.conv2d_bwd_data_gemm(gyn[i:i + 1], wn, (hw, hw))[..., c0:] for i in (gsz + j, 2 * gsz + j)]
+  tmag = sum(N.conv2d_bwd_data_gemm(np.abs(gyn[i:i + 1]), np.abs(wn), (hw, hw))[..., c0:] for i in (gsz + j, 2 * gsz + j))
+  extra = u_st * (np.abs(parts[0]) + np.abs(parts[1])) if composed else None
+  _ratio('upcat conv bwd_data skip', dt, E.assert_elementwise(
+      host(x1.grad[j:j + 1]), tot, E.conv_bound(tot, tmag, 2 * KB, dt, extra), 'upcat gx1 %s skip image %d' % (key, j)))
   # the backward-data kernel that wrote them (concat adjoint in its epilogue), called directly: same bits, and its symbol
   if O.USE_UPCAT_BWD_FUSED:
     d = O._desc((n, hw, hw, c0 + c1), cout, O.ConvSpec(3, 'SAME'), gy.dtype, 0)

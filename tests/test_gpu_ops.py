@@ -4,6 +4,20 @@ Tolerances: fp32 kernels vs the float64 oracle: rel-L2 <= 2e-5 (s
 bf16 kernels vs the oracle evaluated on the same bf16-rounded inputs: rel-L2 <= 1e-2 forward,
 3e-2 gradients; MFMA bf16 kernels vs the direct bf16 kernels (same rounding, different summation
 order): rel-L2 <= 2e-3.
+
+Element-wise parity (the second half of this file and the three dispatch-threshold tests; tests/elementwise.py holds the
+formulas and their derivation, DESIGN.md section 2 the table of the worst ratios per operator family, on the MI355X and over
+the emulated kernels): every element against its own bound, built from the float64 reference and the inputs only --
+  convs            u |ref| + (1 + u) K 2^-24 mag       K summands in fp32, mag the same sum over |operands|
+  fp32 gradients   2^-24 |ref| + P 2^-24 mag            P summed pixels
+  kernel vs kernel r u max(|a|, |b|) + 2 K 2^-24 mag    whole batch, on the device
+  normalisers ...  u |ref| + 16 E32                     E32 = max |float32 restatement - float64| of the literal formula
+  pool, upsample^T u |ref| (16-bit); fp32: + 3 2^-24 sum|x|  a sum of four stored values
+  streaming ops    u |ref| + (1 + u) ops 2^-24 mag      the kernel's own 1-4 fp32 operations
+  copies           array_equal
+with u = 2^-8 (bf16), 2^-11 (fp16), 2^-24 (fp32), `+ tiny` everywhere (2^-25 for fp16: half its subnormal spacing), and
+every further storage rounding the product path defines named where it is added.  Each check prints
+`[elementwise] <family> <dtype> worst ratio <r>` (run with -s).
 """
 import numpy as np
 import pytest
@@ -47,6 +61,36 @@ def tol_for(dtype, grad=False):
   if dtype == torch.float32:
     return F32_TOL
   return BF16_GRAD_TOL if grad else BF16_FWD_TOL
+
+
+# ---------------------------------------------------------------------------------------------- element-wise bookkeeping
+import zlib                  # noqa: E402
+import elementwise as E      # noqa: E402
+
+EW_DTYPES = {'f32': torch.float32, 'bf16': torch.bfloat16, 'f16': torch.float16}
+EW_WORST = {}      # operator family -> dtype -> worst ratio seen in this session (printed with -s: the table of DESIGN.md)
+
+
+def _ew_note(family, dname, ratio):
+  d = EW_WORST.setdefault(family, {})
+  d[dname] = max(d.get(dname, 0.0), float(ratio))
+  print('[elementwise] %-28s %-4s worst ratio %.3f' % (family, dname, ratio))
+
+
+def _ew_dname(dtype):
+  return {torch.float32: 'f32', torch.bfloat16: 'bf16', torch.float16: 'f16'}[dtype]
+
+
+def _with_middle(sel, key, lo, hi):
+  """sel plus one image of lo + 1 .. hi - 2, seeded by the case: the images a first / last check never meets."""
+  return sorted(set(sel) | ({lo + 1 + zlib.crc32(key.encode()) % (hi - lo - 2)} if hi - lo > 2 else set()))
+
+
+def _twice(ref, slope, dtype):
+  """Where a mask is applied to a STORED tensor (capi.hip: "the plain conv, then the mask in place") the masked value is
+  stored again: a second rounding, u |ref|, of the elements whose slope is not 1."""
+  u = E.unit_roundoff(dtype)
+  return (1 + u) * (u * np.abs(ref) + E.tiny(dtype)) * (slope != 1.0)
 
 
 @pytest.fixture(scope='module')
@@ -492,7 +536,12 @@ def test_mbstd_fwd_bwd_bwdbwd(ops, dtype, n, c):
   gtol = tol_for(dtype, True)
   assert rel_l2(host(gx), gxt.detach().numpy()) < gtol
   assert rel_l2(host(ggo)[..., :c + 1], ggot.numpy()) < gtol
-  assert rel_l2(host(gx2), gx2t.numpy()) < (gtol if dtype == torch.float32 else 0.1)
+  if dtype == torch.float32:
+    assert rel_l2(host(gx2), gx2t.numpy()) < gtol
+  else:      # 16-bit second order: every element within u |ref| + 16 E32 (tests/elementwise.py) where a rel-L2 of 0.1 stood
+    r32 = E.mbstd_reference(torch.from_numpy(x), torch.from_numpy(go[..., :c + 1].copy()), torch.from_numpy(v), 1, eps, torch.float32)
+    ref = gx2t.numpy()
+    E.assert_elementwise(host(gx2), ref, E.e32_bound(ref, E.e32(r32[3], ref), dtype), 'mbstd n%d c%d second-order gx2' % (n, c))
 
 
 # ---------------------------------------------------------------------------------------------- dense, losses
@@ -2387,6 +2436,21 @@ def _edge_single(O, spec, pad, x, gy, w, b, dtype, rec, what):
   sel = sorted({0, n - 1})
   wn, bn, xs, gs = host(w), host(b), host(x[sel]), host(gy[sel])
   epi = TG_EPI_BIAS | TG_EPI_LRELU
+  # element-wise (tests/elementwise.py): first, last and one seeded middle image against the oracle, whole batch against the
+  # direct kernel on the device.  sel3 holds sel's images at positions pos.
+  sel3 = _with_middle(sel, '%s:%d' % (what, n), 0, n)
+  pos = [sel3.index(i) for i in sel]
+  dn = _ew_dname(dtype)
+  KF, KB = k * k * cin, k * k * cout
+  x3, g3 = host(x[sel3]), host(gy[sel3])
+  fmag = lambda i0, i1: E.conv_mag_device(x[i0:i1], w, pad)
+  bmag = lambda i0, i1: E.conv_mag_device(gy[i0:i1], w, pad, transpose=True)
+
+  def each(got, ref, bound, name):
+    _ew_note('conv edge ' + name, dn, E.assert_elementwise(got, ref, bound, '%s n%d %s images %s' % (what, n, name, sel3)))
+
+  def pair(a, bb, mag, K, name, roundings=2):
+    _ew_note('conv edge ' + name, dn, E.assert_pair_device(a, bb, mag, K, '%s n%d %s' % (what, n, name), roundings=roundings))
 
   def note(ep):
     rec.setdefault(ep, {})[str(n)] = _last_kernel()
@@ -2397,26 +2461,42 @@ def _edge_single(O, spec, pad, x, gy, w, b, dtype, rec, what):
     assert e < tol, (what, n, name, e, tol)
 
   # ---- forward: plain, bias + LeakyReLU, with the mask epilogue, with the statistics epilogue
-  lin = N.conv2d_gemm(xs, wn, pad)
+  lin3, lmag3 = N.conv2d_gemm(x3, wn, pad), N.conv2d_gemm(np.abs(x3), np.abs(wn), pad)
+  lin = lin3[pos]
   y0 = O.conv_fwd_raw(x, w, None, spec, 0)
   note('fwd')
   close(host(y0[sel]), lin, otol, 'fwd')
+  each(host(y0[sel3]), lin3, E.conv_bound(lin3, lmag3, KF, dtype), 'fwd')
   with _Direct():
     yd = O.conv_fwd_raw(x, w, None, spec, 0)
   close(host(y0), host(yd), dtol, 'fwd vs direct')      # linear part: LeakyReLU would amplify a 1-ulp flip across zero
+  pair(y0, yd, fmag, KF, 'fwd vs direct')
   y1 = O.conv_fwd_raw(x, w, b, spec, epi)
   close(host(y1[sel]), N.leaky_relu(lin + bn), otol, 'fwd bias lrelu')
+  # bias add and slope multiply: two more fp32 operations (K + 2, |bias| joins the magnitudes); LeakyReLU is 1-Lipschitz
+  act3 = N.leaky_relu(lin3 + bn)
+  act_bound = E.conv_bound(act3, lmag3 + np.abs(bn), KF + 2, dtype)
+  each(host(y1[sel3]), act3, act_bound, 'fwd bias lrelu')
   ym = O.conv_fwd_masked_raw(x, w, gy, spec)             # gy has the output's shape: any tensor serves as the mask source
   note('fwd_masked')
   close(host(ym[sel]), lin * np.where(gs > 0, 1.0, 0.2), otol, 'fwd_masked')
+  slope3 = np.where(g3 > 0, 1.0, 0.2)                    # from an input: exact
+  # where the mask is not fusable (capi.hip: "the plain conv, then the mask in place") the stored value is masked and stored
+  # again: a second rounding, u |ref|, of the elements whose slope is not 1
+  twice = lambda ref, slope: _twice(ref, slope, dtype)
+  each(host(ym[sel3]), lin3 * slope3, E.conv_bound(lin3 * slope3, lmag3 * slope3, KF + 1, dtype, twice(lin3 * slope3, slope3)),
+       'fwd_masked')
   with _Direct():
     ymd = O.conv_fwd_masked_raw(x, w, gy, spec)
   close(host(ym), host(ymd), 2 * dtol, 'fwd_masked vs direct')      # the direct path rounds once more before the mask
+  pair(ym, ymd, fmag, KF + 1, 'fwd_masked vs direct', roundings=4)      # two storage roundings on either side at most
   if k == 3:
     ys, st = O.conv_fwd_stats_raw(x, w, spec)
     note('fwd_stats')
     close(host(ys[sel]), lin, otol, 'fwd_stats')
+    each(host(ys[sel3]), lin3, E.conv_bound(lin3, lmag3, KF, dtype), 'fwd_stats')
     close(host(ys), host(yd), dtol, 'fwd_stats vs direct')
+    pair(ys, yd, fmag, KF, 'fwd_stats vs direct')
     if st is not None:
       _edge_partials(st, ys, what)
     del ys
@@ -2427,8 +2507,13 @@ def _edge_single(O, spec, pad, x, gy, w, b, dtype, rec, what):
     z, zp = O.conv_fwd_pool_raw(x, w, b, spec, epi)
     note('fwd_pool')
     close(host(z[sel]), N.leaky_relu(lin + bn), otol, 'fwd_pool z')
+    each(host(z[sel3]), act3, act_bound, 'fwd_pool z')
     close(host(z), host(y1), dtol, 'fwd_pool z vs plain forward')
     close(host(zp), host(z.float().view(n, ho // 2, 2, ho // 2, 2, cout).mean(dim=(2, 4))), dtol, 'fwd_pool pooled')
+    # the pooled tensor: the mean of four STORED z (each within its own bound), rounded once more
+    pool4 = lambda a: a.reshape(len(sel3), ho // 2, 2, ho // 2, 2, cout).mean(axis=(2, 4))
+    u_st = E.unit_roundoff(dtype)
+    each(host(zp[sel3]), pool4(act3), u_st * np.abs(pool4(act3)) + (1 + u_st) * pool4(act_bound) + E.tiny(dtype), 'fwd_pool pooled')
     assert O.conv_fwd_pool_signs_supported(x, w, spec, epi), ('no sign-bit variant', what, n)
     sg, zp2 = O.conv_fwd_pool_signs_raw(x, w, b, spec, epi)
     note('fwd_pool_signs')
@@ -2443,26 +2528,44 @@ def _edge_single(O, spec, pad, x, gy, w, b, dtype, rec, what):
       note('bwd_data_unpool')
       g2, _ = O.lrelu_pool_bwd_signs(gzp, sg, spec.alpha, None, False)
       assert torch.equal(out[1], g2), ('unpool kept gradient', what, n)
-      close(host(out[0]), host(O.conv_bwd_data_masked_raw(g2, w, x, spec)), dtol, 'unpool vs two launches')
-      up = host(gzp[sel]).repeat(2, axis=1).repeat(2, axis=2) * 0.25 * np.where(host(z[sel]) > 0, 1.0, 0.2)
-      ref = N.conv2d_bwd_data_gemm(rnd(up), wn, (hin, hin), pad) * np.where(xs > 0, 1.0, 0.2)
-      close(host(out[0][sel]), ref, otol, 'unpool')
-      del out, g2
+      two = O.conv_bwd_data_masked_raw(g2, w, x, spec)
+      close(host(out[0]), host(two), dtol, 'unpool vs two launches')
+      pair(out[0], two, lambda i0, i1: E.conv_mag_device(g2[i0:i1], w, pad, transpose=True), KB + 1, 'unpool vs two launches',
+           roundings=4)
+      # the oracle on sel3: the unpooled gradient is an MFMA operand, so it IS rounded to the storage type (rnd(up), which the
+      # kept tensor equals bit for bit, asserted above); then backward-data (K = k k cout) and the producer's mask (+ 1)
+      up3 = rnd(host(gzp[sel3]).repeat(2, axis=1).repeat(2, axis=2) * 0.25 * np.where(host(z[sel3]) > 0, 1.0, 0.2))
+      xsl = np.where(x3 > 0, 1.0, 0.2)
+      ref3u = N.conv2d_bwd_data_gemm(up3, wn, (hin, hin), pad) * xsl
+      mag3u = N.conv2d_bwd_data_gemm(np.abs(up3), np.abs(wn), (hin, hin), pad) * xsl
+      close(host(out[0][sel]), ref3u[pos], otol, 'unpool')
+      each(host(out[0][sel3]), ref3u, E.conv_bound(ref3u, mag3u, KB + 1, dtype, twice(ref3u, xsl)), 'unpool')
+      del out, g2, two
     del z, zp, sg, zp2
   del y0, y1, yd
 
   # ---- backward-data, plain and with the producer's LeakyReLU mask in the epilogue
-  ref = N.conv2d_bwd_data_gemm(gs, wn, (hin, hin), pad)
+  ref3 = N.conv2d_bwd_data_gemm(g3, wn, (hin, hin), pad)
+  rmag3 = N.conv2d_bwd_data_gemm(np.abs(g3), np.abs(wn), (hin, hin), pad)
+  ref = ref3[pos]
   gx = O.conv_bwd_data_raw(gy, w, tuple(x.shape), spec)
   note('bwd_data')
   close(host(gx[sel]), ref, otol, 'bwd_data')
+  each(host(gx[sel3]), ref3, E.conv_bound(ref3, rmag3, KB, dtype), 'bwd_data')
   with _Direct():
     gd = O.conv_bwd_data_raw(gy, w, tuple(x.shape), spec)
   close(host(gx), host(gd), dtol, 'bwd_data vs direct')
+  pair(gx, gd, bmag, KB, 'bwd_data vs direct')
   gm = O.conv_bwd_data_masked_raw(gy, w, x, spec)
   note('bwd_data_masked')
   close(host(gm[sel]), ref * np.where(xs > 0, 1.0, 0.2), otol, 'bwd_data_masked')
-  close(host(gm), host(O.lrelu_bwd_raw(gd, x, 0.2)), 2 * dtol, 'bwd_data_masked vs direct')      # two roundings apart
+  xslope3 = np.where(x3 > 0, 1.0, 0.2)
+  each(host(gm[sel3]), ref3 * xslope3, E.conv_bound(ref3 * xslope3, rmag3 * xslope3, KB + 1, dtype, twice(ref3 * xslope3, xslope3)),
+       'bwd_data_masked')
+  gdm = O.lrelu_bwd_raw(gd, x, 0.2)
+  close(host(gm), host(gdm), 2 * dtol, 'bwd_data_masked vs direct')      # two roundings apart
+  pair(gm, gdm, bmag, KB + 1, 'bwd_data_masked vs direct', roundings=4)
+  del gdm
   del gx, gd, gm
 
   # ---- filter gradient (fp32), alone and with the bias gradient riding along
@@ -2470,11 +2573,21 @@ def _edge_single(O, spec, pad, x, gy, w, b, dtype, rec, what):
   gw = O.conv_bwd_weight_raw(x, gy, spec)
   note('bwd_weight')
   close(host(gw), want_gw, EDGE_F32_TOL, 'bwd_weight')
+  gw_alone = gw
   gb = torch.zeros(cout, dtype=torch.float32, device=x.device)
   gw = O.conv_bwd_weight_raw(x, gy, spec, gbias=gb)
   note('bwd_weight_bias')
   close(host(gw), want_gw, EDGE_F32_TOL, 'bwd_weight_bias')
   close(host(gb), host(gy).sum(axis=(0, 1, 2)), EDGE_F32_TOL, 'bwd_weight_bias bias')
+  # fp32 sums over P = n ho wo pixels, any order: both launches' filter gradients, and the bias gradient
+  P = n * ho * ho
+  wbound = E.wgrad_bound(want_gw, _edge_wgrad_oracle(np.abs(host(x)), np.abs(host(gy)), k, pad), P)
+  r = E.assert_elementwise(host(gw), want_gw, wbound, '%s n%d bwd_weight_bias' % (what, n))
+  r = max(r, E.assert_elementwise(host(gw_alone), want_gw, wbound, '%s n%d bwd_weight' % (what, n)))
+  gsum = host(gy).sum(axis=(0, 1, 2))
+  r = max(r, E.assert_elementwise(host(gb), gsum, E.wgrad_bound(gsum, np.abs(host(gy)).sum(axis=(0, 1, 2)), P),
+                                  '%s n%d bias gradient' % (what, n)))
+  _ew_note('conv edge bwd_weight', dn, r)
 
 
 @pytest.mark.parametrize('dname', sorted(EDGE_DTYPES))
@@ -2537,17 +2650,35 @@ def test_upcat_conv_on_both_sides_of_a_dispatch_threshold(ops, case, dname):
     x0, x1, gy = x0a[:n].contiguous(), x1a[:n].contiguous(), gya[:n].contiguous()
     assert O.upcat_conv_supported(x0, x1, w)
     sel = sorted({0, n - 1})
-    cat = np.concatenate([cat_of(i) for i in sel])
+    # element-wise: first, last and one seeded middle image against the oracle, the whole batch against the direct kernel
+    sel3 = _with_middle(sel, '%s:%d' % (cid, n), 0, n)
+    pos = [sel3.index(i) for i in sel]
+    KF, KB, u_st = 9 * (c0 + c1), 9 * cout, E.unit_roundoff(dtype)
+    cat3 = np.concatenate([cat_of(i) for i in sel3])
+    lin3, lmag3 = N.conv2d_gemm(cat3, wn), N.conv2d_gemm(np.abs(cat3), np.abs(wn))
+    fbound = E.conv_bound(lin3, lmag3, KF, dtype)
+
+    def each(got, ref, bound, name):
+      _ew_note('upcat edge ' + name, dname, E.assert_elementwise(got, ref, bound, '%s n%d %s images %s' % (cid, n, name, sel3)))
+
+    def pair(a, b, mag, K, name, roundings=2, extra=None):
+      _ew_note('upcat edge ' + name, dname, E.assert_pair_device(a, b, mag, K, '%s n%d %s' % (cid, n, name), roundings=roundings,
+                                                                 extra=extra))
     y = O.upcat_conv(x0, x1, w, 0, ())
     rec.setdefault('upcat_fwd', {})[str(n)] = _last_kernel()
-    close(host(y[sel]), N.conv2d_gemm(cat, wn), otol, 'upcat fwd', n)
+    close(host(y[sel]), lin3[pos], otol, 'upcat fwd', n)
+    each(host(y[sel3]), lin3, fbound, 'fwd')
     xcat = O.upsample2x_concat(x0, x1, 0, ())
+    fmag = lambda i0, i1: E.conv_mag_device(xcat[i0:i1], w, 'SAME')
     with _Direct():
       yd = O.conv_fwd_raw(xcat, w, None, spec, 0)
     close(host(y), host(yd), dtol, 'upcat fwd vs direct', n)
+    pair(y, yd, fmag, KF, 'fwd vs direct')
     ys, st = O.upcat_conv_stats(x0, x1, w, 0, ())
     rec.setdefault('upcat_fwd_stats', {})[str(n)] = _last_kernel()
     close(host(ys), host(yd), dtol, 'upcat fwd_stats vs direct', n)
+    each(host(ys[sel3]), lin3, fbound, 'fwd_stats')
+    pair(ys, yd, fmag, KF, 'fwd_stats vs direct')
     if st is not None:
       _edge_partials(st, ys, cid)
     del y, ys, yd, xcat
@@ -2558,9 +2689,15 @@ def test_upcat_conv_on_both_sides_of_a_dispatch_threshold(ops, case, dname):
     O.call('tg_conv2d_upcat_bwd_data', gy.data_ptr(), wpack.data_ptr(), g0.data_ptr(), g1.data_ptr(), n, hw, hw, c0, c1, cout, 0,
            O._pack_perm(()), O._dt(gy), O._stream())
     rec.setdefault('upcat_bwd_data', {})[str(n)] = _last_kernel()
-    gc = N.conv2d_bwd_data_gemm(host(gy[sel]), wn, (hw, hw))
+    gc3 = N.conv2d_bwd_data_gemm(host(gy[sel3]), wn, (hw, hw))
+    gm3 = N.conv2d_bwd_data_gemm(np.abs(host(gy[sel3])), np.abs(wn), (hw, hw))
+    gc = gc3[pos]
     close(host(g0[sel]), gc[..., :c0].reshape(len(sel), hw // 2, 2, hw // 2, 2, c0).sum(axis=(2, 4)), otol, 'upcat g0', n)
     close(host(g1[sel]), gc[..., c0:], otol, 'upcat g1', n)
+    # the fused kernel sums the 2x2 block in its fp32 accumulators and rounds once: 4 x 9 cout summands for g0, 9 cout for g1
+    quad = lambda a: a[..., :c0].reshape(len(sel3), hw // 2, 2, hw // 2, 2, c0).sum(axis=(2, 4))
+    each(host(g0[sel3]), quad(gc3), E.conv_bound(quad(gc3), quad(gm3), 4 * KB, dtype), 'bwd_data g0')
+    each(host(g1[sel3]), gc3[..., c0:], E.conv_bound(gc3[..., c0:], gm3[..., c0:], KB, dtype), 'bwd_data g1')
     with _Direct():
       gcat = O.conv_bwd_data_raw(gy, w, (n, hw, hw, c0 + c1), spec)
     r0, r1 = torch.empty_like(g0), torch.empty_like(g1)
@@ -2568,6 +2705,12 @@ def test_upcat_conv_on_both_sides_of_a_dispatch_threshold(ops, case, dname):
            O._pack_perm(()), O._dt(gcat), O._stream())
     close(host(g0), host(r0), 2 * dtol, 'upcat g0 vs direct', n)      # the composed path rounds the concat-layout gradient first
     close(host(g1), host(r1), dtol, 'upcat g1 vs direct', n)
+    # whole batch on the device.  g0: the composed route adds four STORED concat-layout values -- u sum4 |gcat| of its own
+    qd = lambda t: t[..., :c0].reshape(t.shape[0], hw // 2, 2, hw // 2, 2, c0).sum(dim=(2, 4))
+    bmag = lambda i0, i1: E.conv_mag_device(gy[i0:i1], w, 'SAME', transpose=True)
+    pair(g0, r0, lambda i0, i1: qd(bmag(i0, i1)), 4 * KB, 'bwd_data g0 vs direct',
+         extra=lambda i0, i1: (1 + u_st) * (u_st * qd(gcat[i0:i1].float().abs()) + 4 * E.tiny(dtype)))
+    pair(g1, r1, lambda i0, i1: bmag(i0, i1)[..., c0:], KB, 'bwd_data g1 vs direct')
     del g0, g1, r0, r1, gcat
     # filter gradient
     wl = w.clone().requires_grad_(True)
@@ -2575,6 +2718,9 @@ def test_upcat_conv_on_both_sides_of_a_dispatch_threshold(ops, case, dname):
     rec.setdefault('upcat_bwd_weight', {})[str(n)] = _last_kernel()
     want = sum(N.conv2d_bwd_weight_gemm(cat_of(i), host(gy[i:i + 1]), (3, 3)) for i in range(n))
     close(host(wl.grad), want, EDGE_F32_TOL, 'upcat bwd_weight', n)
+    wmag = sum(N.conv2d_bwd_weight_gemm(np.abs(cat_of(i)), np.abs(host(gy[i:i + 1])), (3, 3)) for i in range(n))
+    _ew_note('upcat edge bwd_weight', dname, E.assert_elementwise(host(wl.grad), want, E.wgrad_bound(want, wmag, n * hw * hw),
+                                                                  '%s n%d upcat bwd_weight' % (cid, n)))
   _edge_straddles(cid, rec, flips, n_lo, n_hi)
   _edge_symbols_check(cid, dname, rec)
 
@@ -2662,15 +2808,35 @@ def test_grouped_conv_across_the_dispatch_thresholds(ops, case, dname):
   rec['bwd_data_masked'] = _last_kernel()
   same(gm, per_set(lambda i, r: O.conv_bwd_data_masked_raw(gy[r].contiguous(), w2[i], x[r].contiguous(), spec)), 'bwd_data_masked')
   # ---- the oracle on the first and last image of every group
+  KF, KB = k * k * cin, k * k * cout
+
+  def each(got, ref, bound, name, i, s3):
+    _ew_note('grouped edge ' + name, dname, E.assert_elementwise(got, ref, bound, '%s %s group %d images %s' % (cid, name, i, s3)))
   for i in range(G):
     sel = sorted({i * h, (i + 1) * h - 1})
-    wn = host(w2[i])
-    lin = N.conv2d_gemm(host(x[sel]), wn, pad)
-    close(host(y[sel]), N.leaky_relu(lin + host(b2[i])), otol, 'fwd vs oracle, group %d' % i)
+    # element-wise: first, last and one seeded middle image of EVERY group
+    sel3 = _with_middle(sel, '%s:%d' % (cid, i), i * h, (i + 1) * h)
+    pos = [sel3.index(j) for j in sel]
+    wn, bn = host(w2[i]), host(b2[i])
+    x3, g3 = host(x[sel3]), host(gy[sel3])
+    lin3, lmag3 = N.conv2d_gemm(x3, wn, pad), N.conv2d_gemm(np.abs(x3), np.abs(wn), pad)
+    lin = lin3[pos]
+    close(host(y[sel]), N.leaky_relu(lin + bn), otol, 'fwd vs oracle, group %d' % i)
+    act3 = N.leaky_relu(lin3 + bn)
+    each(host(y[sel3]), act3, E.conv_bound(act3, lmag3 + np.abs(bn), KF + 2, dtype), 'fwd', i, sel3)
     close(host(ym[sel]), lin * np.where(host(y[sel]) > 0, 1.0, 0.2), otol, 'fwd_masked vs oracle, group %d' % i)
-    ref = N.conv2d_bwd_data_gemm(host(gy[sel]), wn, (hw, hw), pad)
+    ysl = np.where(host(y[sel3]) > 0, 1.0, 0.2)      # y is the mask SOURCE of this launch, an input to it: exact
+    each(host(ym[sel3]), lin3 * ysl, E.conv_bound(lin3 * ysl, lmag3 * ysl, KF + 1, dtype, _twice(lin3 * ysl, ysl, dtype)),
+         'fwd_masked', i, sel3)
+    ref3 = N.conv2d_bwd_data_gemm(g3, wn, (hw, hw), pad)
+    rmag3 = N.conv2d_bwd_data_gemm(np.abs(g3), np.abs(wn), (hw, hw), pad)
+    ref = ref3[pos]
     close(host(gx[sel]), ref, otol, 'bwd_data vs oracle, group %d' % i)
+    each(host(gx[sel3]), ref3, E.conv_bound(ref3, rmag3, KB, dtype), 'bwd_data', i, sel3)
     close(host(gm[sel]), ref * np.where(host(x[sel]) > 0, 1.0, 0.2), otol, 'bwd_data_masked vs oracle, group %d' % i)
+    xsl = np.where(x3 > 0, 1.0, 0.2)
+    each(host(gm[sel3]), ref3 * xsl, E.conv_bound(ref3 * xsl, rmag3 * xsl, KB + 1, dtype, _twice(ref3 * xsl, xsl, dtype)),
+         'bwd_data_masked', i, sel3)
   del ym, gm
   # ---- block ends: pooled output (+ sign bytes), and the backward-data that unpools
   if k == 3 and pad == 'SAME' and hw >= 16:
@@ -2704,6 +2870,18 @@ def test_grouped_conv_across_the_dispatch_thresholds(ops, case, dname):
   O.conv_bwd_weight_raw(x, gy, spec, out=sink, gbias=bsink)
   close(host(sink), host(ref), tol, 'bwd_weight_bias')
   close(host(bsink), host(gy.float().reshape(G, -1, cout).sum(1)), 1e-3, 'bwd_weight_bias bias')
+  # fp32 filter and bias gradients of every group against the float64 oracle: sums over P = (n / G) ho wo pixels, any order
+  P = h * ho * ho
+  for i in range(G):
+    xi, gi = host(x[i * h:(i + 1) * h]), host(gy[i * h:(i + 1) * h])
+    want_w = _edge_wgrad_oracle(xi, gi, k, pad)
+    wb = E.wgrad_bound(want_w, _edge_wgrad_oracle(np.abs(xi), np.abs(gi), k, pad), P)
+    r = E.assert_elementwise(host(gw[i]), want_w, wb, '%s bwd_weight group %d' % (cid, i))
+    r = max(r, E.assert_elementwise(host(sink[i]), want_w, wb, '%s bwd_weight_bias group %d' % (cid, i)))
+    gsum = gi.sum(axis=(0, 1, 2))
+    r = max(r, E.assert_elementwise(host(bsink[i]), gsum, E.wgrad_bound(gsum, np.abs(gi).sum(axis=(0, 1, 2)), P),
+                                    '%s bias gradient group %d' % (cid, i)))
+    _ew_note('grouped edge bwd_weight', dname, r)
   if O.conv_bwd_weight2_raw(x, gy, x, gy, spec, sink, bsink, 3):      # two segments, both grouped
     close(host(sink), 3.0 * host(ref), tol, 'bwd_weight2')
   del gw, ref, sink, bsink
@@ -2765,3 +2943,680 @@ def test_pack_layout_follows_the_kernel_that_runs(ops, case):
     frag = int(sym.startswith(('conv_img_kernel', 'conv_small_kernel')))
     assert _lib.load().tg_conv2d_pack_layout(ctypes.byref(d), mode) == frag, \
         '%s mode %d: pack layout %d, but the pack is read by %s' % (cid, mode, 1 - frag, sym)
+
+
+# =====================================================================================================================
+# Element-wise parity of the streaming kernels (norm.hip, reduce.hip, pointwise.hip) at the sizes and edges that reach
+# the branches of their host code.  Every output element against its own bound (tests/elementwise.py: the formulas and
+# their derivation); the references are float64 autograd of the literal formulas, E32 their float32 restatement.
+# =====================================================================================================================
+def _round_to(a, dtype):
+  """numpy / tensor values rounded to the storage type -> float64 torch tensor on the CPU."""
+  t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+  return t.float().to(dtype).double().cpu()
+
+
+def _norm_chunking(n, hw, pool=False):
+  """The host's own arithmetic (norm.hip: norm_chunks, and the streaming pass' ~2048 blocks), restated to NAME the branch a
+  case is for: -> ((chunks, ppb, tail) of pass 1, the same of pass 2)."""
+  floor = 16 if hw <= 64 else 32 if hw <= 256 else 64
+  ch = (1024 + n - 1) // n
+  pp = max((hw + ch - 1) // ch, floor)
+  units = hw // 4 if pool else hw
+  c2 = (2048 + n - 1) // n
+  pp2 = max((units + c2 - 1) // c2, 16 if pool else floor)
+  return ((hw + pp - 1) // pp, pp, hw % pp), ((units + pp2 - 1) // pp2, pp2, units % pp2)
+
+
+NORM_EDGE_CASES = [
+    # id (the branch it is for), n, h, w, c, lrelu, pixel norm, pool, split (None: one domain), mode
+    #   mode 'ret': gradients returned (the separate parameter-gradient kernel); 'sink': added into registered buffers that
+    #   already hold values (16-bit: atomics; fp32: ordered); 'det': the same in deterministic mode (ordered in every type)
+    ('p1_15x64_p2_15x64_pool_15x16', 3, 40, 24, 16, True, True, True, 1, 'ret'),
+    ('hw221_floor32_tail29_split0', 5, 17, 13, 8, True, True, False, 0, 'sink'),
+    ('p1_ppb128_p2_ppb66_tail4_pool_ppb17_tail4_split_n-1', 33, 64, 64, 8, True, True, True, 32, 'ret'),
+    ('p1_ppb128_tail112_p2_ppb65_tail50_split_n', 33, 60, 68, 16, True, True, False, 33, 'sink'),
+    ('n2_255_chunks_pool', 2, 136, 120, 16, True, True, True, 1, 'det'),
+    ('n1_1024_chunks', 1, 256, 256, 16, True, True, False, None, 'ret'),
+    ('n130_hw64_4_chunks_c48_scalar', 130, 8, 8, 48, True, False, False, 65, 'sink'),
+    ('hw64_floor16_c24_scalar', 3, 8, 8, 24, True, False, False, None, 'ret'),
+    ('hw65_floor32_tail1_c24_scalar', 3, 5, 13, 24, True, False, False, 1, 'ret'),
+    ('hw256_floor32_c5_scalar_pool', 3, 16, 16, 5, True, False, True, None, 'ret'),
+    ('hw257_floor64_tail1_c5_scalar', 3, 1, 257, 5, False, False, False, 2, 'sink'),
+    ('hw258_floor64_tail2_c3_scalar', 3, 3, 86, 3, True, False, False, 1, 'det'),
+    ('tail60_pool_tail15_c256', 2, 34, 30, 256, True, True, True, 1, 'ret'),
+    ('tail12_pool_tail3_c512_widest_vector', 3, 18, 22, 512, True, True, True, 2, 'sink'),
+]
+
+
+def _norm_inputs(n, h, w, c, pool, dtype, seed):
+  rng = np.random.RandomState(seed)
+  y = _round_to(rng.randn(n, h, w, c) * 1.5 + 0.7 + 0.5 * rng.randn(1, 1, 1, c), dtype)
+  gz = _round_to(rng.randn(n, h, w, c), dtype)
+  gzp = _round_to(rng.randn(n, h // 2, w // 2, c), dtype) if pool else None
+  par = [torch.from_numpy((o + s * rng.randn(c)).astype(np.float32)).double() for o, s in ((1.0, 0.2), (0.0, 0.1)) * 2]
+  return y, gz, gzp, par
+
+
+def _near_zero(r64, r32):
+  """Where the float64 pre-activation u is inside its own bound, 2^-24 |u| + 16 E32(u): the kernels hold u in fp32 whatever
+  the storage type.  E32(u) is taken over the elements the bound is applied to, |u| < 2^-6, when there are at least 256 of
+  them (the maximum over the whole tensor belongs to the largest |u| and is ten times theirs)."""
+  u, u32 = r64['u'].numpy(), r32['u'].numpy()
+  small = np.abs(u) < 2.0 ** -6
+  e_u = E.e32(u32[small], u[small]) if small.sum() >= 256 else E.e32(u32, u)
+  return np.abs(u) < E.e32_bound(u, e_u, torch.float32)
+
+
+def _seeded(make, refs, lrelu, seed):
+  """The first of seeds seed, seed + 1, ... whose float64 reference ALONE has fewer than 1e-5 of its pre-activations inside
+  their bound (a condition on the inputs, decided before any kernel runs) -> (inputs, r64, r32, near)."""
+  for s in range(seed, seed + 8):
+    inp = make(s)
+    r64, r32 = refs(inp, torch.float64), refs(inp, torch.float32)
+    near = _near_zero(r64, r32) if lrelu else None
+    if near is None or near.mean() < 1e-5:
+      return inp, r64, r32, near
+  raise AssertionError('no seed in [%d, %d) meets the LeakyReLU condition' % (seed, seed + 8))
+
+
+def _check_norm_outputs(what, dname, got, r64, r32, dtype, family, near=None, flip_ref=None, gy_extra=None):
+  """z, zp, gy of a fused normaliser against the float64 reference: u |ref| + 16 E32 per element.
+  zp: the kernels pool the STORED z (norm.hip: "the pool reads the stored (rounded) z", so that the pooled tensor is the pool
+  of the skip tensor whichever kernel wrote it): the mean of four roundings, u mean4 |z|, is that path's own further term.
+  gy takes its LeakyReLU mask from a computed sign: where `near` holds (_near_zero) the other slope is accepted, for at most
+  1e-5 of the elements."""
+  u_st = E.unit_roundoff(dtype)
+  ref = r64['z'].numpy()
+  r = E.assert_elementwise(host(got['z']), ref, E.e32_bound(ref, E.e32(r32['z'].numpy(), ref), dtype), what + ' z')
+  _ew_note(family + ' z', dname, r)
+  if r64['zp'] is not None:
+    n, h, w, c = ref.shape
+    ref = r64['zp'].numpy()
+    zmag = np.abs(r64['z'].numpy()).reshape(n, h // 2, 2, w // 2, 2, c).mean(axis=(2, 4))
+    bound = E.e32_bound(ref, E.e32(r32['zp'].numpy(), ref), dtype) + (1 + u_st) * u_st * zmag
+    _ew_note(family + ' zp', dname, E.assert_elementwise(host(got['zp']), ref, bound, what + ' zp'))
+  ref = r64['gy'].numpy()
+  bound = E.e32_bound(ref, E.e32(r32['gy'].numpy(), ref), dtype)
+  if gy_extra is not None:
+    bound = bound + gy_extra
+  alt = None
+  if near is not None and near.any():
+    alt = flip_ref(torch.from_numpy(near))['gy'].numpy()
+  r = E.assert_elementwise(host(got['gy']), ref, bound, what + ' gy', alt_ref=alt, alt_where=near)
+  _ew_note(family + ' gy', dname, r)
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('case', NORM_EDGE_CASES, ids=[c[0] for c in NORM_EDGE_CASES])
+def test_norm_act_elementwise_at_chunk_edges(ops, case, dname):
+  """ops.norm_act (tg_instance_norm_partials + tg_norm_act_fwd_partials, tg_norm_act_bwd) forward and backward, every element
+  of z, the pooled z, gy and the parameter gradients against float64, at shapes that reach: a tail chunk in pass 1 and in pass
+  2, different chunk counts in the two passes, both sides of the min_ppb steps at hw 64 and 256, the scalar path (c = 3, 5;
+  24 and 48 by the power-of-two rule), the widest vector path (c = 512: 16-bit only, fp32 must refuse it), split at 0, 1,
+  n-1 and n, and the three ways the parameter gradients leave the kernel."""
+  import twingan_amd.ops as O
+  from twingan_amd import _lib
+  name, n, h, w, c, lrelu, pn, pool, split, mode = case
+  dtype = EW_DTYPES[dname]
+  p1, p2 = _norm_chunking(n, h * w, pool)
+  print('[norm chunks] %s: pass 1 (chunks, ppb, tail) %s, pass 2 %s' % (name, p1, p2))
+  assert _lib.load().tg_norm_chunks(n, h, w) == p1[0], 'norm_chunks moved: the case ids of NORM_EDGE_CASES name stale branches'
+  two = split is not None
+
+  def refs(inp, dt, flip=None):
+    y, gz, gzp, par = inp
+    return E.norm_act_reference(y.to(dt), par[0], par[1], gz, par[2] if two else None, par[3] if two else None, split=split,
+                                lrelu=lrelu, pixel_norm=pn, pool=pool, gzp=gzp, flip=flip)
+  inp, r64, r32, near = _seeded(lambda s: _norm_inputs(n, h, w, c, pool, dtype, s), refs, lrelu, 70 + len(name))
+  y, gz, gzp, par = inp
+  yd = y.to(dev()).to(dtype).contiguous().requires_grad_(True)
+  pd = [p.float().to(dev()).requires_grad_(True) for p in (par if two else par[:2])]
+  kw = dict(lrelu=lrelu, pixel_norm=pn, pool=pool)
+  if two:
+    kw.update(gamma2=pd[2], beta2=pd[3], split=split)
+  if c == 512 and dtype == torch.float32:
+    with pytest.raises(_lib.TgError, match='pixel norm needs c'):      # loud, not a fall-back
+      O.norm_act(yd, pd[0], pd[1], **kw)
+    return
+  lib = _lib.load()
+  was = lib.tg_set_deterministic(1) if mode == 'det' else None
+  pre = [torch.from_numpy(np.random.RandomState(5 + i).randn(c).astype(np.float32)).to(dev()) for i in range(len(pd))]
+  sinks = [t.clone() for t in pre]
+  try:
+    if mode != 'ret':
+      for p, s in zip(pd, sinks):
+        O.GradSink.register(p, s)
+    out = O.norm_act(yd, pd[0], pd[1], **kw)
+    z, zp = out if pool else (out, None)
+    gzd = gz.to(dev()).to(dtype)
+    if pool:
+      torch.autograd.backward([z, zp], [gzd, gzp.to(dev()).to(dtype)])
+    else:
+      z.backward(gzd)
+    torch.cuda.synchronize()
+  finally:
+    for p in pd:
+      O.GradSink.unregister(p)
+    if was is not None:
+      lib.tg_set_deterministic(was)
+
+  _check_norm_outputs('norm_act[%s,%s]' % (name, dname), dname, dict(z=z, zp=zp, gy=yd.grad), r64, r32, dtype, 'norm_act',
+                      near, lambda f: refs(inp, torch.float64, f))
+  for i, nm in enumerate(('gamma', 'beta', 'gamma2', 'beta2')[:len(pd)]):
+    ref = r64['grads'][i].numpy()
+    bound = E.e32_bound(ref, E.e32(r32['grads'][i].numpy(), ref), torch.float32)
+    if mode == 'ret':
+      got = host(pd[i].grad)
+    else:      # added into what the buffer held: one more fp32 addition, its rounding named here
+      assert pd[i].grad is None
+      got = host(sinks[i]) - host(pre[i])
+      bound = bound + 2.0 ** -24 * (np.abs(host(pre[i])) + np.abs(ref))
+    r = E.assert_elementwise(got, ref, bound, 'norm_act[%s,%s] %s gradient (%s)' % (name, dname, nm, mode))
+    _ew_note('norm_act parameter grads', dname, r)
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('c,pn', [(24, True), (48, True), (520, True), (520, False), (3, True)])
+def test_norm_act_refuses_what_it_cannot_run(ops, c, pn, dname):
+  """Pixel norm needs c = VN * 2^k <= 64 VN (VN = 8 in 16-bit storage, 4 in fp32); without it c <= 256 on the scalar path,
+  and 520 = 8 * 65 fits neither.  The refusal is an error with the reason in it, never another code path."""
+  import twingan_amd.ops as O
+  from twingan_amd import _lib
+  dtype = EW_DTYPES[dname]
+  y = torch.ones((2, 6, 6, c), dtype=dtype, device=dev())
+  ga, be = torch.ones(c, device=dev()), torch.zeros(c, device=dev())
+  with pytest.raises(_lib.TgError, match='pixel norm needs c|scalar path needs c'):
+    O.norm_act(y, ga, be, lrelu=True, pixel_norm=pn)
+
+
+ROWS_CASES = [('tail12_c32', 4, 18, 22, 32, True, True), ('hw65_c8_pool_unfused', 3, 10, 26, 8, True, True),
+              ('c5_scalar', 3, 5, 13, 5, False, False)]
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('case', ROWS_CASES, ids=[c[0] for c in ROWS_CASES])
+def test_norm_act_per_image_parameters_elementwise(ops, case, dname):
+  """The non-partials route: tg_instance_norm_stats + tg_norm_act_fwd with one parameter row per image (batch renorm's
+  form), its backward writing [n, c] row gradients; the pool is then the stand-alone kernel."""
+  import twingan_amd.ops as O
+  name, n, h, w, c, pn, pool = case
+  dtype = EW_DTYPES[dname]
+
+  def make(seed):
+    rng = np.random.RandomState(seed + 1000)
+    return _norm_inputs(n, h, w, c, pool, dtype, seed)[:3] + (
+        [torch.from_numpy((o + s * rng.randn(n, c)).astype(np.float32)).double() for o, s in ((1.0, 0.2), (0.0, 0.1))],)
+
+  def refs(inp, dt, flip=None):
+    y, gz, gzp, rows = inp
+    return E.norm_act_reference(y.to(dt), rows[0], rows[1], gz, lrelu=True, pixel_norm=pn, pool=pool, gzp=gzp, flip=flip)
+  inp, r64, r32, near = _seeded(make, refs, True, 91)
+  y, gz, gzp, rows = inp
+  yd = y.to(dev()).to(dtype).contiguous().requires_grad_(True)
+  rd = [r.float().to(dev()).requires_grad_(True) for r in rows]
+  stats = O.instance_stats(yd.detach(), 1e-6)
+  # the statistics kernel on its own: mean and rstd per (image, channel), fp32
+  yn = y.numpy().reshape(n, h * w, c)
+  m64, v64 = yn.mean(axis=1), yn.var(axis=1)
+  y32 = y.float()
+  m32 = y32.mean(dim=(1, 2))
+  v32 = ((y32 - m32.view(n, 1, 1, c)) ** 2).mean(dim=(1, 2))
+  r64s, r32s = 1.0 / np.sqrt(v64 + 1e-6), torch.rsqrt(v32 + 1e-6).numpy()
+  r = E.assert_elementwise(host(stats[0]).reshape(n, c), m64, E.e32_bound(m64, E.e32(m32.numpy(), m64), torch.float32),
+                           'instance_stats[%s,%s] mean' % (name, dname))
+  _ew_note('instance_norm_stats', dname, r)
+  r = E.assert_elementwise(host(stats[1]).reshape(n, c), r64s, E.e32_bound(r64s, E.e32(r32s, r64s), torch.float32),
+                           'instance_stats[%s,%s] rstd' % (name, dname))
+  _ew_note('instance_norm_stats', dname, r)
+  out = O.norm_act(yd, rd[0], rd[1], lrelu=True, pixel_norm=pn, pool=pool, stats=stats)
+  z, zp = out if pool else (out, None)
+  if pool:
+    torch.autograd.backward([z, zp], [gz.to(dev()).to(dtype), gzp.to(dev()).to(dtype)])
+  else:
+    z.backward(gz.to(dev()).to(dtype))
+
+  _check_norm_outputs('rows[%s,%s]' % (name, dname), dname, dict(z=z, zp=zp, gy=yd.grad), r64, r32, dtype, 'norm_act rows',
+                      near, lambda f: refs(inp, torch.float64, f))
+  for i, nm in enumerate(('gamma rows', 'beta rows')):
+    ref = r64['grads'][i].numpy()
+    r = E.assert_elementwise(host(rd[i].grad), ref, E.e32_bound(ref, E.e32(r32['grads'][i].numpy(), ref), torch.float32),
+                             'rows[%s,%s] %s gradient' % (name, dname, nm))
+    _ew_note('norm_act rows parameter grads', dname, r)
+
+
+# ------------------------------------------------------------------------------------------------ streaming ops, element by element
+def _f32_ops_bound(ref, mag, ops_, dtype):
+  """A value computed by `ops_` fp32 operations on terms of magnitude `mag`, stored once: u |ref| + (1 + u) ops 2^-24 mag."""
+  return E.conv_bound(ref, mag, ops_, dtype)
+
+
+def _sum4_bound(ref, mag, dtype):
+  """A sum of four stored values (pool, upsample adjoint).  16-bit storage: the fp32 sum of four 16-bit values of one scale is
+  exact, the output is one rounding of it -- u |ref| and nothing else.  fp32 storage: the three additions round, so
+  2^-24 |ref| + 3 2^-24 sum|x| (the one place where this file needs more than the plain rounding for these ops)."""
+  return E.rounded_bound(ref, dtype) if dtype != torch.float32 else _f32_ops_bound(ref, mag, 3, dtype)
+
+
+STREAM_SHAPES = [
+    # id, n, h, w, c
+    ('bench_past_2p24_elements', 17, 256, 256, 16),      # 17.8 M elements: an index held in a float, or 24 bits, would show
+    ('odd_non_square_c5', 3, 10, 14, 5),                 # scalar path, nothing a multiple of anything
+    ('one_past_a_vector_c9', 2, 6, 4, 9),                # 16-bit vectors hold 8, fp32 vectors 4: one channel past both
+    ('c24_three_vectors', 2, 4, 6, 24),
+]
+
+
+def _stream_inputs(shape, dtype, seed, k=1):
+  rng = np.random.RandomState(seed)
+  return [_round_to(torch.from_numpy(rng.standard_normal(shape).astype(np.float32)), dtype) for _ in range(k)]
+
+
+def _up2(a):
+  return a.repeat(2, axis=1).repeat(2, axis=2)
+
+
+def _sum4(a):
+  n, h, w, c = a.shape
+  return a.reshape(n, h // 2, 2, w // 2, 2, c).sum(axis=(2, 4))
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('case', STREAM_SHAPES, ids=[c[0] for c in STREAM_SHAPES])
+def test_pool_and_upsample_elementwise(ops, case, dname):
+  """tg_pool2x2_fwd / _bwd (and the pool of the backward's backward), tg_upsample2x_concat_fwd / _bwd without groups.
+  Copies are exact (array_equal), a multiplication by 0.25 is exact down to the type's smallest numbers, a sum of four stored
+  values is bounded by _sum4_bound: u |ref| alone in 16-bit storage."""
+  name, n, h, w, c = case
+  dtype = EW_DTYPES[dname]
+  x, gyp, v = _stream_inputs((n, h, w, c), dtype, 300, 1) + _stream_inputs((n, h // 2, w // 2, c), dtype, 301, 1) + \
+      _stream_inputs((n, h, w, c), dtype, 302, 1)
+  xd = x.to(dev()).to(dtype).requires_grad_(True)
+  y = ops.avg_pool2(xd)
+  xn = x.numpy()
+  ref = 0.25 * _sum4(xn)
+  _ew_note('pool2x2 fwd', dname, E.assert_elementwise(host(y), ref, _sum4_bound(ref, 0.25 * _sum4(np.abs(xn)), dtype),
+                                                      'avg_pool2 fwd %s %s' % (name, dname)))
+  gyd = gyp.to(dev()).to(dtype).requires_grad_(True)
+  gx, = torch.autograd.grad(y, xd, grad_outputs=gyd, create_graph=True)
+  # an exact scaled copy (a power of two) -- down to the storage type's smallest numbers: bound tiny(dtype) and nothing else
+  _ew_note('pool2x2 bwd', dname, E.assert_elementwise(host(gx), 0.25 * _up2(gyp.numpy()), E.tiny(dtype), 'avg_pool2 bwd %s %s' % (name, dname)))
+  ggy, = torch.autograd.grad(gx, gyd, grad_outputs=v.to(dev()).to(dtype))
+  vn = v.numpy()
+  ref = 0.25 * _sum4(vn)
+  _ew_note('pool2x2 bwd-bwd', dname, E.assert_elementwise(host(ggy), ref, _sum4_bound(ref, 0.25 * _sum4(np.abs(vn)), dtype),
+                                                          'avg_pool2 bwd-bwd %s %s' % (name, dname)))
+  del y, gx, ggy, xd, gyd
+  # upsample + concat: x0 at half resolution, x1 (c + 3 channels: the two halves differ) at full resolution
+  c1 = c + 3
+  x0, = _stream_inputs((n, h // 2, w // 2, c), dtype, 303)
+  x1, go = _stream_inputs((n, h, w, c1), dtype, 304)[0], _stream_inputs((n, h, w, c + c1), dtype, 305)[0]
+  a, b = x0.to(dev()).to(dtype).requires_grad_(True), x1.to(dev()).to(dtype).requires_grad_(True)
+  out = ops.upsample2x_concat(a, b)
+  assert np.array_equal(host(out), np.concatenate([_up2(x0.numpy()), x1.numpy()], axis=3)), ('upsample2x_concat fwd', name, dname)
+  out.backward(go.to(dev()).to(dtype))
+  gon = go.numpy()
+  ref = _sum4(gon[..., :c])
+  _ew_note('upsample2x_concat bwd', dname, E.assert_elementwise(
+      host(a.grad), ref, _sum4_bound(ref, _sum4(np.abs(gon[..., :c])), dtype), 'upsample2x_concat bwd g0 %s %s' % (name, dname)))
+  assert np.array_equal(host(b.grad), gon[..., c:]), ('upsample2x_concat bwd g1 is a copy', name, dname)
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('n,h,w,c0,c1,gsz,perm', [(8, 6, 10, 5, 9, 2, (1, 0, 0, 1)), (12, 4, 4, 16, 8, 4, (0, 1, 1)),
+                                                  (64, 64, 64, 16, 16, 16, (1, 0, 0, 1))])
+def test_upsample_concat_group_permutation_elementwise(ops, dname, n, h, w, c0, c1, gsz, perm):
+  """The skip source shared between passes: output group g reads skip images [perm[g] gsz, (perm[g] + 1) gsz); the backward
+  adds the gradients of every group that read an image in fp32 and stores once."""
+  dtype = EW_DTYPES[dname]
+  n1 = (max(perm) + 1) * gsz
+  x0, = _stream_inputs((n, h, w, c0), dtype, 310)
+  x1, = _stream_inputs((n1, 2 * h, 2 * w, c1), dtype, 311)
+  go, = _stream_inputs((n, 2 * h, 2 * w, c0 + c1), dtype, 312)
+  a, b = x0.to(dev()).to(dtype).requires_grad_(True), x1.to(dev()).to(dtype).requires_grad_(True)
+  out = ops.upsample2x_concat(a, b, gsz, perm)
+  src = [perm[i // gsz] * gsz + i % gsz for i in range(n)]
+  assert np.array_equal(host(out), np.concatenate([_up2(x0.numpy()), x1.numpy()[src]], axis=3))
+  out.backward(go.to(dev()).to(dtype))
+  gon = go.numpy()
+  ref = _sum4(gon[..., :c0])
+  _ew_note('upsample2x_concat bwd', dname, E.assert_elementwise(
+      host(a.grad), ref, _sum4_bound(ref, _sum4(np.abs(gon[..., :c0])), dtype), 'grouped upsample2x_concat g0'))
+  ref1, mag1, cnt = np.zeros(x1.shape), np.zeros(x1.shape), np.zeros(n1, int)
+  for i, s_ in enumerate(src):
+    ref1[s_] += gon[i, ..., c0:]
+    mag1[s_] += np.abs(gon[i, ..., c0:])
+    cnt[s_] += 1
+  _ew_note('upsample2x_concat bwd', dname, E.assert_elementwise(
+      host(b.grad), ref1, _f32_ops_bound(ref1, mag1, int(cnt.max()) - 1 if cnt.max() > 1 else 1, dtype), 'grouped upsample2x_concat g1'))
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('case', STREAM_SHAPES, ids=[c[0] for c in STREAM_SHAPES])
+def test_lrelu_backward_family_elementwise(ops, case, dname):
+  """tg_lrelu_bwd, tg_lrelu_pool_bwd (with and without either gradient, with the bias gradient), tg_lrelu_bwd_bias (the same
+  launcher without a pooled gradient), tg_lrelu_pool_bwd_signs, tg_channel_sum and its ordered form, tg_bias_lrelu_fwd.
+  The masks come from an INPUT tensor (exact).  g * slope is one fp32 multiplication by float32(0.2), gz + 0.25 up(gzp) one
+  fused multiply-add before it: 1 / 2 fp32 operations, then the storage rounding.  The bias gradient is the fp32 sum of the
+  values the kernel STORED (norm.hip: `a[j] += rnd(g)`): the float64 sum of the reference, with the sum of the elements' own
+  bounds added to the summation bound."""
+  import twingan_amd.ops as O
+  from twingan_amd import _lib
+  name, n, h, w, c = case
+  dtype = EW_DTYPES[dname]
+  al = float(np.float32(0.2))
+  gz, z = _stream_inputs((n, h, w, c), dtype, 320, 2)
+  gzp, = _stream_inputs((n, h // 2, w // 2, c), dtype, 321)
+  bias = torch.zeros(c, device=dev())
+  gzd, zd, gzpd = (t.to(dev()).to(dtype).contiguous() for t in (gz, z, gzp))
+  slope = np.where(z.numpy() > 0, 1.0, al)
+  ref = gz.numpy() * slope
+  _ew_note('lrelu_bwd', dname, E.assert_elementwise(host(O.lrelu_bwd_raw(gzd, zd, 0.2)), ref,
+                                                    _f32_ops_bound(ref, np.abs(ref), 1, dtype), 'lrelu_bwd %s %s' % (name, dname)))
+  P = n * h * w
+  for use_gz, use_gzp in ((True, True), (False, True), (True, False)):
+    pre = (gz.numpy() if use_gz else 0.0) + (0.25 * _up2(gzp.numpy()) if use_gzp else 0.0)
+    mag = ((np.abs(gz.numpy()) if use_gz else 0.0) + (0.25 * _up2(np.abs(gzp.numpy())) if use_gzp else 0.0)) * slope
+    ref = pre * slope
+    g, gb = O.lrelu_pool_bwd(gzd if use_gz else None, gzpd if use_gzp else None, zd, 0.2, bias, True)
+    what = 'lrelu_pool_bwd gz=%d gzp=%d %s %s' % (use_gz, use_gzp, name, dname)
+    gbound = _f32_ops_bound(ref, mag, 2, dtype)
+    _ew_note('lrelu_pool_bwd', dname, E.assert_elementwise(host(g), ref, gbound, what))
+    # the bias gradient is the fp32 sum of the STORED g: against the float64 sum of the reference, every summand within its
+    # own element bound (their sum), plus the fp32 summation over P pixels
+    bsum, bmag_ = ref.reshape(-1, c).sum(axis=0), np.abs(ref).reshape(-1, c).sum(axis=0)
+    bbound = E.wgrad_bound(bsum, bmag_, P) + gbound.reshape(-1, c).sum(axis=0)
+    _ew_note('lrelu_pool_bwd bias', dname, E.assert_elementwise(host(gb), bsum, bbound, what + ' bias'))
+    if use_gzp and not use_gz and c % 8 == 0 and dtype != torch.float32:      # the sign-byte form of the same backward
+      bits = (zd > 0).view(n, h, w, c // 8, 8).to(torch.int32)
+      signs = (bits << torch.arange(8, device=zd.device, dtype=torch.int32)).sum(dim=-1).to(torch.uint8).contiguous()
+      g2, gb2 = O.lrelu_pool_bwd_signs(gzpd, signs, 0.2, bias, True)
+      assert torch.equal(g2, g), what + ': sign-byte form differs'
+      _ew_note('lrelu_pool_bwd bias', dname, E.assert_elementwise(host(gb2), bsum, bbound, what + ' signs bias'))
+    del g
+  # tg_lrelu_bwd_bias: the launcher's form without a pooled gradient, written (accumulate = 0) and added (1)
+  for acc in (0, 1):
+    g = torch.empty_like(zd)
+    gb = torch.full((c,), 3.0 if acc else float('nan'), dtype=torch.float32, device=dev())
+    O.call('tg_lrelu_bwd_bias', gzd.data_ptr(), zd.data_ptr(), g.data_ptr(), gb.data_ptr(), P, c, 0.2, acc, O._dt(zd), O._stream())
+    ref = gz.numpy() * slope
+    gbound = _f32_ops_bound(ref, np.abs(ref), 1, dtype)
+    _ew_note('lrelu_bwd_bias', dname, E.assert_elementwise(host(g), ref, gbound, 'lrelu_bwd_bias %s %s' % (name, dname)))
+    bsum = ref.reshape(-1, c).sum(axis=0)
+    bound = E.wgrad_bound(bsum, np.abs(ref).reshape(-1, c).sum(axis=0), P) + gbound.reshape(-1, c).sum(axis=0) + \
+        (2.0 ** -24 * (3.0 + np.abs(bsum)) if acc else 0.0)
+    _ew_note('lrelu_bwd_bias bias', dname, E.assert_elementwise(host(gb) - (3.0 if acc else 0.0), bsum, bound,
+                                                                'lrelu_bwd_bias bias acc=%d %s %s' % (acc, name, dname)))
+  # channel sums: atomic and ordered
+  lib = _lib.load()
+  gs = gz.numpy().reshape(-1, c)
+  for det in (0, 1):
+    was = lib.tg_set_deterministic(det)
+    try:
+      got = O.channel_sum_raw(gzd)
+    finally:
+      lib.tg_set_deterministic(was)
+    _ew_note('channel_sum' + ('_ordered' if det else ''), dname, E.assert_elementwise(
+        host(got), gs.sum(axis=0), E.wgrad_bound(gs.sum(axis=0), np.abs(gs).sum(axis=0), P), 'channel_sum det=%d %s %s' % (det, name, dname)))
+  # bias + LeakyReLU forward (rows of [npix, c])
+  b = torch.from_numpy(np.random.RandomState(322).randn(c).astype(np.float32))
+  out = torch.empty_like(zd)
+  O.call('tg_bias_lrelu_fwd', zd.data_ptr(), b.to(dev()).data_ptr(), out.data_ptr(), P, c, 0.2, O._dt(zd), O._stream())
+  pre = z.numpy() + b.double().numpy()
+  ref = np.where(pre > 0, pre, al * pre)      # continuous in pre: no alternates
+  _ew_note('bias_lrelu_fwd', dname, E.assert_elementwise(
+      host(out), ref, _f32_ops_bound(ref, np.abs(z.numpy()) + np.abs(b.double().numpy()), 2, dtype), 'bias_lrelu_fwd %s %s' % (name, dname)))
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('case', STREAM_SHAPES, ids=[c[0] for c in STREAM_SHAPES])
+def test_axpby_sample_lerp_gdrop_elementwise(ops, case, dname):
+  """tg_axpby (a x + b y: two multiplications and an addition in fp32), tg_sample_lerp (x + alpha[n] (y - x): a subtraction and
+  a fused multiply-add), tg_gdrop (x (noise[n, c] s sqrt(C) + 1): the factor in fp32, one multiplication)."""
+  import twingan_amd.ops as O
+  name, n, h, w, c = case
+  dtype = EW_DTYPES[dname]
+  x, y = _stream_inputs((n, h, w, c), dtype, 330, 2)
+  xd, yd = (t.to(dev()).to(dtype).contiguous() for t in (x, y))
+  xn, yn = x.numpy(), y.numpy()
+  a, b = float(np.float32(0.3)), float(np.float32(-1.7))
+  out = torch.empty_like(xd)
+  O.call('tg_axpby', xd.data_ptr(), yd.data_ptr(), out.data_ptr(), xd.numel(), a, b, O._dt(xd), O._stream())
+  ref = a * xn + b * yn
+  _ew_note('axpby', dname, E.assert_elementwise(host(out), ref, _f32_ops_bound(ref, np.abs(a * xn) + np.abs(b * yn), 3, dtype),
+                                                'axpby %s %s' % (name, dname)))
+  alpha = torch.from_numpy(np.random.RandomState(331).rand(n).astype(np.float32))
+  got = O.sample_lerp(xd, yd, alpha.to(dev()))
+  an = alpha.double().numpy().reshape(n, 1, 1, 1)
+  ref = xn + an * (yn - xn)
+  _ew_note('sample_lerp', dname, E.assert_elementwise(
+      host(got), ref, _f32_ops_bound(ref, np.abs(xn) + an * (np.abs(yn) + np.abs(xn)), 3, dtype), 'sample_lerp %s %s' % (name, dname)))
+  noise = torch.from_numpy(np.random.RandomState(332).randn(n, c).astype(np.float32))
+  cl = c - 1 if c > 4 else c
+  f = noise.double().numpy() * (float(np.float32(0.37)) * float(np.sqrt(np.float32(cl)))) + 1.0
+  got = O.gdrop(xd, 0.37, noise=noise.to(dev()), c_logical=cl)
+  ref = xn * f[:, None, None, :]
+  fmag = np.abs(noise.double().numpy()) * 0.37 * np.sqrt(cl) + 1.0
+  _ew_note('gdrop', dname, E.assert_elementwise(host(got), ref, _f32_ops_bound(ref, np.abs(xn) * fmag[:, None, None, :], 4, dtype),
+                                                'gdrop %s %s' % (name, dname)))
+
+
+# ------------------------------------------------------------------------------------------------ minibatch stddev, element by element
+MBSTD_CASES = [(2, 1, 8), (16, 1, 256), (48, 3, 256), (64, 4, 256), (64, 1, 8), (48, 2, 5), (5, 1, 32)]
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('n,groups,c', MBSTD_CASES)
+def test_mbstd_elementwise_at_the_discriminator_shapes(ops, n, groups, c, dname):
+  """tg_mbstd_fwd / _bwd / _bwd_bwd at the 4 x 4 maps the growing discriminator feeds them (n = 2 ... 64; 1 to 4 batched
+  discriminator calls as groups; c = 256 padded to 264), every element against float64 autograd: u |ref| + 16 E32, first AND
+  second order, in every storage type -- the second-order output of the 16-bit types included (a rel-L2 of 0.1 was all that
+  stood there).  fp32 adds the derived conditioning term of elementwise.mbstd_conditioning (first needed by n = 2 over the
+  emulated kernels: ratio 1.09 of u |ref| + 16 E32 at the one position whose two samples nearly coincide).  The copied
+  channels are exact, the padding is zero.
+  What this does NOT give at n = 2: E32 is one number per tensor, and the second-order gradient there spans orders of
+  magnitude between positions (1 / sigma^3), so 16 E32 exceeds half of |ref| for most elements of gx2 at n = 2 -- that case
+  guards against garbage, not against a wrong term; n >= 5 is where the second-order check bites.  A per-position E32
+  (e32_bound takes an array) would close it and needs a restatement with more than two samples per position to be a bound."""
+  from twingan_amd.params import mbstd_cpad
+  from twingan_amd import _lib
+  dtype = EW_DTYPES[dname]
+  cpad = mbstd_cpad(c)
+  eps = 1e-8 if dtype == torch.float32 else 1e-6
+  rng = np.random.RandomState(400 + n + c)
+  x, v = _round_to(rng.randn(n, 4, 4, c), dtype), _round_to(rng.randn(n, 4, 4, c), dtype)
+  go = _round_to(rng.randn(n, 4, 4, cpad), dtype)
+  xd = x.to(dev()).to(dtype).requires_grad_(True)
+  god = go.to(dev()).to(dtype).requires_grad_(True)
+  out = ops.minibatch_state_concat(xd, cpad, groups)
+  gx, = torch.autograd.grad(out, xd, grad_outputs=god, create_graph=True)
+  ggo, gx2 = torch.autograd.grad(gx, [god, xd], grad_outputs=v.to(dev()).to(dtype))
+  r64 = E.mbstd_reference(x, go[..., :c + 1], v, groups, eps, torch.float64)
+  r32 = E.mbstd_reference(x, go[..., :c + 1], v, groups, eps, torch.float32)
+  o = host(out)
+  assert np.array_equal(o[..., :c], x.numpy()) and np.all(o[..., c + 1:] == 0), 'mbstd copies x and pads with zeros'
+  what = 'mbstd n%d g%d c%d %s ' % (n, groups, c, dname)
+  gg = host(ggo)
+  assert np.all(gg[..., c + 1:] == 0), what + 'second-order gradient of the padding'
+  extra = {}
+  if dtype == torch.float32:      # the derived term replaces nothing in 16-bit storage, where u |ref| + 16 E32 holds as it is
+    ex_gx, ex_T, ex_gx2 = E.mbstd_conditioning(x, go, v, groups, eps)
+    ex_ggo = np.zeros((n, 4, 4, c + 1))
+    ex_ggo[..., c] = np.repeat(ex_T, n // groups).reshape(n, 1, 1)
+    extra = {1: ex_gx, 2: ex_ggo, 3: ex_gx2}
+  for nm, got, i in (('statistic', o[..., c:c + 1], 0), ('gx', host(gx), 1), ('ggo', gg[..., :c + 1], 2), ('gx2', host(gx2), 3)):
+    ref = r64[i][..., c:c + 1] if i == 0 else r64[i]
+    r32i = r32[i][..., c:c + 1] if i == 0 else r32[i]
+    r = E.assert_elementwise(got, ref, E.e32_bound(ref, E.e32(r32i, ref), dtype) + extra.get(i, 0.0), what + nm)
+    _ew_note('mbstd ' + nm, dname, r)
+  if n % 3:
+    with pytest.raises(_lib.TgError, match='not divisible by groups'):
+      ops.minibatch_state_concat(xd.detach(), cpad, 3)
+
+
+# ------------------------------------------------------------------------------------------------ fromRGB / toRGB, element by element
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('cin,cout', [(3, 16), (3, 256), (16, 3), (256, 3), (3, 12), (20, 3)])
+@pytest.mark.parametrize('n,h,w', [(3, 7, 5), (2, 33, 31)])      # 105 and 2046 pixels: no multiple of a block's pixel count
+def test_pointwise_conv_elementwise(ops, n, h, w, cin, cout, dname):
+  """tg_pointwise_conv_fwd (bias + LeakyReLU), its masked form, tg_pointwise_conv_bwd_weight(_bias) and the ordered form, with
+  a pixel count that no block size divides.  Bounds as for the convs with K = cin: the weights hold values of the storage
+  type, so 16-bit products are exact in fp32 (K + 2 operations with the epilogue); fp32 products round once each (2 K + 2).
+  The masked form stores `rnd(x @ W) * mask`: the second rounding of the masked elements is named."""
+  import twingan_amd.ops as O
+  from twingan_amd._lib import TG_EPI_BIAS, TG_EPI_LRELU
+  dtype = EW_DTYPES[dname]
+  u_st = E.unit_roundoff(dtype)
+  rng = np.random.RandomState(500 + cin + cout)
+  x, gy = _round_to(rng.randn(n, h, w, cin), dtype), _round_to(rng.randn(n, h, w, cout), dtype)
+  wt = _round_to(rng.randn(cin, cout) / np.sqrt(cin), dtype)
+  b = torch.from_numpy((rng.randn(cout) * 0.1).astype(np.float32))
+  xd, gyd = x.to(dev()).to(dtype).contiguous(), gy.to(dev()).to(dtype).contiguous()
+  wd, bd = wt.float().to(dev()).contiguous(), b.to(dev())
+  xn, wn, gn, bn = x.numpy(), wt.numpy(), gy.numpy(), b.double().numpy()
+  K = cin if dtype != torch.float32 else 2 * cin
+  lin, mag = xn @ wn, np.abs(xn) @ np.abs(wn)
+  what = 'pointwise %d>%d n%d %dx%d %s ' % (cin, cout, n, h, w, dname)
+  y = O._pw_fwd_raw(xd, wd, bd, False, TG_EPI_BIAS | TG_EPI_LRELU, 0.2)
+  pre = lin + bn
+  ref = np.where(pre > 0, pre, float(np.float32(0.2)) * pre)
+  _ew_note('pointwise fwd', dname, E.assert_elementwise(host(y), ref, E.conv_bound(ref, mag + np.abs(bn), K + 2, dtype), what + 'fwd'))
+  y0 = O._pw_fwd_raw(xd, wd, None, False, 0, 0.2)
+  _ew_note('pointwise fwd', dname, E.assert_elementwise(host(y0), lin, E.conv_bound(lin, mag, K, dtype), what + 'fwd plain'))
+  if cin <= 4:
+    ym = O._pw_fwd_masked_raw(xd, wd, False, gyd, 0.2)
+    slope = np.where(gn > 0, 1.0, float(np.float32(0.2)))
+    ref = lin * slope
+    extra = (1 + u_st) * u_st * np.abs(ref) * (slope != 1.0)
+    _ew_note('pointwise fwd_masked', dname, E.assert_elementwise(host(ym), ref, E.conv_bound(ref, mag * slope, K + 1, dtype, extra),
+                                                                 what + 'fwd_masked'))
+  # filter (+ bias) gradient: fp32 sums over the pixels
+  P = n * h * w
+  ref_w = xn.reshape(-1, cin).T @ gn.reshape(-1, cout)
+  mag_w = np.abs(xn).reshape(-1, cin).T @ np.abs(gn).reshape(-1, cout)
+  ref_b, mag_b = gn.reshape(-1, cout).sum(axis=0), np.abs(gn).reshape(-1, cout).sum(axis=0)
+  Pw = P if dtype != torch.float32 else 2 * P      # fp32 products round once each
+  for acc in (0, 1):
+    base = 3.0 if acc else 0.0
+    addb = 2.0 ** -24 * (3.0 + np.abs(ref_w)) if acc else 0.0      # the addition into what the buffer held
+    gw = torch.full((cin, cout), 3.0 if acc else float('nan'), device=dev())
+    O.call('tg_pointwise_conv_bwd_weight', xd.data_ptr(), gyd.data_ptr(), gw.data_ptr(), P, cin, cout, acc, O._dt(xd), O._stream())
+    _ew_note('pointwise bwd_weight', dname, E.assert_elementwise(host(gw) - base, ref_w, E.wgrad_bound(ref_w, mag_w, Pw) + addb,
+                                                                 what + 'bwd_weight acc=%d' % acc))
+    if cin <= 4:
+      gw = torch.full((cin, cout), 3.0 if acc else float('nan'), device=dev())
+      gb = torch.full((cout,), 3.0 if acc else float('nan'), device=dev())
+      O.call('tg_pointwise_conv_bwd_weight_bias', xd.data_ptr(), gyd.data_ptr(), gw.data_ptr(), gb.data_ptr(), P, cin, cout, acc,
+             O._dt(xd), O._stream())
+      _ew_note('pointwise bwd_weight', dname, E.assert_elementwise(host(gw) - base, ref_w, E.wgrad_bound(ref_w, mag_w, Pw) + addb,
+                                                                   what + 'bwd_weight_bias acc=%d' % acc))
+      addbb = 2.0 ** -24 * (3.0 + np.abs(ref_b)) if acc else 0.0
+      _ew_note('pointwise bias gradient', dname, E.assert_elementwise(host(gb) - base, ref_b, E.wgrad_bound(ref_b, mag_b, P) + addbb,
+                                                                      what + 'bias gradient acc=%d' % acc))
+    ws = torch.empty(256 * cin * cout, dtype=torch.float32, device=dev())
+    gw = torch.full((cin, cout), 3.0 if acc else float('nan'), device=dev())
+    O.call('tg_pointwise_conv_bwd_weight_ordered', xd.data_ptr(), gyd.data_ptr(), gw.data_ptr(), P, cin, cout, acc, ws.data_ptr(),
+           ws.numel(), O._dt(xd), O._stream())
+    _ew_note('pointwise bwd_weight_ordered', dname, E.assert_elementwise(
+        host(gw) - base, ref_w, E.wgrad_bound(ref_w, mag_w, Pw) + addb, what + 'bwd_weight_ordered acc=%d' % acc))
+
+
+# ------------------------------------------------------------------------------------------------ layer norm, conv statistics route
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('n,h,w,c,pool,split', [(5, 17, 13, 8, False, None), (3, 34, 30, 16, True, 1), (4, 18, 22, 32, True, 4),
+                                                (130, 8, 8, 16, False, 0)])
+def test_layer_norm_act_elementwise(ops, n, h, w, c, pool, split, dname):
+  """ops.layer_norm_act (statistics kernel + row arithmetic + the fused per-image-row kernel, and their backwards) at the tail
+  shapes, every element against float64 autograd of the literal formula (moments of each image over (H, W, C), eps 1e-12)."""
+  dtype = EW_DTYPES[dname]
+  two = split is not None
+
+  def refs(inp, dt, flip=None):
+    y, gz, gzp, par = inp
+    return E.norm_act_reference(y.to(dt), par[0], par[1], gz, par[2] if two else None, par[3] if two else None, split=split,
+                                pool=pool, gzp=gzp, eps=1e-12, flip=flip, layer=True)
+  inp, r64, r32, near = _seeded(lambda s: _norm_inputs(n, h, w, c, pool, dtype, s), refs, True, 600 + n)
+  y, gz, gzp, par = inp
+  yd = y.to(dev()).to(dtype).contiguous().requires_grad_(True)
+  pd = [p.float().to(dev()).requires_grad_(True) for p in (par if two else par[:2])]
+  out = ops.layer_norm_act(yd, pd[0], pd[1], pool=pool, gamma2=pd[2] if two else None, beta2=pd[3] if two else None, split=split)
+  z, zp = out if pool else (out, None)
+  if pool:
+    torch.autograd.backward([z, zp], [gz.to(dev()).to(dtype), gzp.to(dev()).to(dtype)])
+  else:
+    z.backward(gz.to(dev()).to(dtype))
+  what = 'layer_norm_act n%d %dx%d c%d %s' % (n, h, w, c, dname)
+  # gy leaves this composition as the SUM of two stored tensors (the fused kernel's gy with the statistics held constant, and
+  # the moments' backward), added by autograd in the storage type: three roundings, u (|direct| + |through the statistics|)
+  # more than the one of a dedicated kernel
+  direct = E.norm_act_reference(y.double(), par[0], par[1], gz, par[2] if two else None, par[3] if two else None, split=split,
+                                pool=pool, gzp=gzp, eps=1e-12, layer=True, detach_stats=True)['gy'].numpy()
+  u_st = E.unit_roundoff(dtype)
+  extra = (1 + u_st) * (u_st * (np.abs(direct) + np.abs(r64['gy'].numpy() - direct)) + 2 * E.tiny(dtype))
+  _check_norm_outputs(what, dname, dict(z=z, zp=zp, gy=yd.grad), r64, r32, dtype, 'layer_norm_act', near,
+                      lambda f: refs(inp, torch.float64, f), gy_extra=extra)
+  for i, nm in enumerate(('gamma', 'beta', 'gamma2', 'beta2')[:len(pd)]):
+    ref = r64['grads'][i].numpy()
+    if pd[i].grad is None:      # a domain without images (split 0 or n) receives no gradient at all
+      assert not ref.any(), (what, nm)
+      continue
+    r = E.assert_elementwise(host(pd[i].grad), ref, E.e32_bound(ref, E.e32(r32['grads'][i].numpy(), ref), torch.float32),
+                             '%s %s gradient' % (what, nm))
+    _ew_note('layer_norm_act parameter grads', dname, r)
+
+
+CONV_STATS_CASES = [
+    # producer, n, hw (of the normalised tensor), cin (upcat: c0 = c1 = cin / 2), cout, pool
+    ('conv', 5, 8, 256, 256, True),        # conv_img: ONE chunk per 8 x 8 image; norm_chunks cuts it in 4
+    ('conv', 3, 16, 256, 256, False),      # tile kernel: 2 tiles per image against 8 chunks
+    ('conv', 2, 16, 40, 24, True),         # ragged channel blocks, the scalar normaliser (no pixel norm at c = 24)
+    ('conv', 3, 64, 64, 64, True),
+    ('upcat', 4, 64, 64, 16, True),        # tg_conv2d_upcat_fwd_stats as the producer
+    ('upcat', 3, 32, 128, 64, False),
+]
+
+
+@pytest.mark.parametrize('dname', ['bf16', 'f16'])
+@pytest.mark.parametrize('producer,n,hw,cin,cout,pool', CONV_STATS_CASES)
+def test_norm_act_fed_by_conv_statistics_elementwise(ops, producer, n, hw, cin, cout, pool, dname):
+  """tg_norm_act_fwd_conv_stats: the normaliser's statistics come from the partial sums the conv's epilogue wrote -- the plain
+  conv's (tg_conv2d_fwd_stats) and the upsample-concat conv's (tg_conv2d_upcat_fwd_stats) -- in the PRODUCER's chunking, which
+  for every case here differs from norm_chunks' (asserted): z and the pooled z element by element against float64 on the
+  tensor the conv stored.  A shape that loses its statistics epilogue fails here; it does not skip."""
+  from twingan_amd import _lib
+  dtype = EW_DTYPES[dname]
+  g = torch.Generator().manual_seed(7)
+  w = (torch.randn(3, 3, cin, cout, generator=g) * (2.0 / (9 * cin)) ** 0.5).to(dev())
+  if producer == 'conv':
+    x = (torch.randn(n, hw, hw, cin, generator=g) + 0.3).to(dtype).to(dev())
+    y, st = ops.conv_fwd_stats_raw(x, w, ops.ConvSpec(3, 'SAME'))
+  else:
+    x0 = (torch.randn(n, hw // 2, hw // 2, cin // 2, generator=g) + 0.3).to(dtype).to(dev())
+    x1 = torch.randn(n, hw, hw, cin // 2, generator=g).to(dtype).to(dev())
+    assert ops.upcat_conv_supported(x0, x1, w)
+    y, st = ops.upcat_conv_stats(x0, x1, w, 0, ())
+  assert st is not None, 'no statistics epilogue for %s n%d hw%d c%d>%d %s' % (producer, n, hw, cin, cout, dname)
+  own = _lib.load().tg_norm_chunks(n, hw, hw)
+  assert own == _norm_chunking(n, hw * hw)[0][0]
+  print('[conv stats] producer chunks %d, norm_chunks %d' % (st.chunks, own))
+  assert st.chunks != own, ('the producer chunks this shape as norm_chunks does: the case no longer tests part_chunks', st.chunks, own)
+  pn = cout % 8 == 0 and (cout // 8) & (cout // 8 - 1) == 0
+  par = [torch.from_numpy((o + s * np.random.RandomState(8 + i).randn(cout)).astype(np.float32)) for i, (o, s) in
+         enumerate(((1.0, 0.2), (0.0, 0.1)))]
+  out = ops.norm_act(y, par[0].to(dev()), par[1].to(dev()), pixel_norm=pn, pool=pool, conv_stats=st)
+  z, zp = out if pool else (out, None)
+  yc = y.double().cpu()
+  zero = torch.zeros(tuple(y.shape), dtype=torch.float64)
+  zerop = torch.zeros((n, hw // 2, hw // 2, cout), dtype=torch.float64)
+  r64, r32 = (E.norm_act_reference(yc.to(dt), par[0].double(), par[1].double(), zero, pixel_norm=pn, pool=pool, gzp=zerop)
+              for dt in (torch.float64, torch.float32))
+  what = 'norm_act conv_stats n%d hw%d c%d %s' % (n, hw, cout, dname)
+  u_st = E.unit_roundoff(dtype)
+  ref = r64['z'].numpy()
+  _ew_note('norm_act conv_stats z', dname, E.assert_elementwise(host(z), ref, E.e32_bound(ref, E.e32(r32['z'].numpy(), ref), dtype),
+                                                                what + ' z'))
+  if pool:
+    refp = r64['zp'].numpy()
+    zmag = np.abs(ref).reshape(n, hw // 2, 2, hw // 2, 2, cout).mean(axis=(2, 4))
+    bound = E.e32_bound(refp, E.e32(r32['zp'].numpy(), refp), dtype) + (1 + u_st) * u_st * zmag
+    _ew_note('norm_act conv_stats zp', dname, E.assert_elementwise(host(zp), refp, bound, what + ' zp'))
