@@ -60,8 +60,8 @@ def compile_one(job):
 
 def build(force=False):
   os.makedirs(OUT, exist_ok=True)
-  common = [os.path.join(CSRC, 'tg_common.h'), os.path.join(ROOT, 'include', 'twingan_hip.h'), os.path.join(HERE, 'hip', 'hip_runtime.h'),
-            os.path.abspath(__file__)]
+  common = [os.path.join(CSRC, 'tg_common.h'), os.path.join(CSRC, 'conv_internal.h'), os.path.join(ROOT, 'include', 'twingan_hip.h'),
+            os.path.join(HERE, 'hip', 'hip_runtime.h'), os.path.abspath(__file__)]
   jobs = []
   for name in SOURCES:
     jobs.append((translate(name), os.path.join(OUT, name + '.o'), [os.path.join(CSRC, name + '.hip')] + common, force))

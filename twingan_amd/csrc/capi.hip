@@ -1,5 +1,5 @@
 // extern "C" entry points that dispatch between algorithms, plus error plumbing.
-#include "tg_common.h"
+#include "conv_internal.h"
 
 static thread_local char tg_err[512] = "";
 
@@ -36,46 +36,6 @@ int tg_zero_async(void* a, size_t a_bytes, void* b, size_t b_bytes, hipStream_t 
   TG_LAUNCH_CHECK("tg_zero_async");
   return TG_OK;
 }
-
-int tg_conv2d_fwd_direct(const TgConvDesc*, const void*, const void*, const float*, void*, hipStream_t);
-int tg_conv2d_bwd_data_direct(const TgConvDesc*, const void*, const void*, void*, hipStream_t);
-int tg_conv2d_bwd_weight_direct(const TgConvDesc*, const void*, const void*, float*, int, hipStream_t, void* ws = nullptr,
-                                size_t ws_bytes = 0);
-size_t tg_conv2d_bwd_weight_workspace_direct(const TgConvDesc*);
-int tg_conv2d_fwd_mfma(const TgConvDesc*, const void*, const void*, const float*, void*, hipStream_t);
-int tg_conv2d_bwd_data_mfma(const TgConvDesc*, const void*, const void*, void*, hipStream_t, const void* mask = nullptr);
-bool tg_conv2d_bwd_data_unpool_supported_mfma(const TgConvDesc*);
-int tg_conv2d_bwd_data_unpool_mfma(const TgConvDesc*, const void*, const void*, const void*, void*, hipStream_t, const void* mask,
-                                   void* gy_out, const void* y_act);
-bool tg_conv2d_bwd_data_mask_fusable_mfma(const TgConvDesc*);
-bool tg_conv2d_fwd_mask_fusable_mfma(const TgConvDesc*);
-int tg_conv2d_fwd_masked_mfma(const TgConvDesc*, const void*, const void*, const void*, void*, hipStream_t);
-size_t tg_conv2d_bwd_weight_workspace_mfma(const TgConvDesc*);
-bool tg_conv2d_bwd_weight2_supported_mfma(const TgConvDesc* d);
-size_t tg_conv2d_bwd_weight2_workspace_mfma(const TgConvDesc* d, int nb);
-int tg_conv2d_bwd_weight2_mfma(const TgConvDesc* d, int nb, const void* xa, const void* gya, const void* xb, const void* gyb,
-                               float* gw, int accumulate, void* ws, size_t ws_bytes, hipStream_t s, float* gbias = nullptr,
-                               int bias_segs = 3);
-bool tg_conv2d_bwd_weight_bias_fused_mfma(const TgConvDesc* d);
-
-bool tg_conv_tile_upcat_supported(int h, int w, int c0, int c1, int cout);
-int tg_conv_tile_upcat_bwd_run(int n, int h, int w, int c0, int c1, int cout, int gsz, unsigned perm, int n1, const void* gy,
-                               const void* wp, void* g0, void* g1, hipStream_t s);
-int tg_conv_tile_upcat_run(int n, int h, int w, int c0, int c1, int cout, int gsz, unsigned perm, const void* x0,
-                           const void* x1, const void* wp, void* y, hipStream_t s, float* stats = nullptr,
-                           int stat_chunks = 0, int* chunks_query = nullptr);
-bool tg_conv2d_fwd_pool_supported_mfma(const TgConvDesc* d);
-int tg_conv2d_fwd_pool_mfma(const TgConvDesc* d, const void* x, const void* wp, const float* bias, void* y, void* ypool,
-                            hipStream_t s, void* ymask = nullptr);
-int tg_conv2d_fwd_stats_chunks_mfma(const TgConvDesc* d);
-int tg_conv2d_fwd_stats_mfma(const TgConvDesc* d, const void* x, const void* wp, void* y, float* partials, int chunks,
-                             hipStream_t s);
-size_t tg_wgrad_tile_workspace(int n, int h, int w, int cin, int cout);
-int tg_wgrad_tile_upcat_run(int n, int h, int w, int c0, int c1, int cout, int gsz, unsigned perm, const void* x0,
-                            const void* x1, const void* gy, float* gw, int accumulate, void* ws, size_t ws_bytes,
-                            hipStream_t s);
-int tg_conv2d_bwd_weight_mfma(const TgConvDesc*, const void*, const void*, float*, int, void*, size_t, hipStream_t,
-                              float* gbias = nullptr);
 
 static int check_desc(const char* who, const TgConvDesc* d) {
   TG_CHECK(d != nullptr, TG_EINVAL, "%s: null descriptor", who);
@@ -129,10 +89,16 @@ inline P* at(P* p, size_t bytes) {
   return p ? reinterpret_cast<P*>(reinterpret_cast<uintptr_t>(p) + bytes) : nullptr;
 }
 inline bool grouped(const TgConvDesc* d) { return d->groups > 1; }
+// Is this grouped call launched once per group?  Not when the MFMA dispatch takes operation `op` (TG_GRP_*) of the
+// descriptor as one launch (tg_conv2d_grouped_native_mfma, conv_mfma.hip) and, for the masked entry points, folds the mask
+// into that launch.
+bool split_groups(const TgConvDesc* d, int op, bool masked = false) {
+  if (!grouped(d)) return false;
+  if (d->algo == TG_ALGO_DIRECT) return true;
+  if (masked && !(op == TG_GRP_FWD ? tg_conv2d_fwd_mask_fusable_mfma(d) : tg_conv2d_bwd_data_mask_fusable_mfma(d))) return true;
+  return !tg_conv2d_grouped_native_mfma(d, op);
+}
 }  // namespace
-// which grouped calls the MFMA dispatch takes as one launch (conv_mfma.hip); TG_GRP_*: the operation
-enum { TG_GRP_FWD = 0, TG_GRP_DGRAD = 1, TG_GRP_WGRAD = 2 };
-bool tg_conv2d_grouped_native_mfma(const TgConvDesc* d, int op);
 
 static thread_local bool tg_elem_is_f16 = false;
 bool tg_elem_f16() { return tg_elem_is_f16; }
@@ -168,7 +134,7 @@ int tg_conv2d_fwd(const TgConvDesc* d, const void* x, const void* w, const float
   if (rc) return rc;
   TG_CHECK(x && w && y, TG_EINVAL, "tg_conv2d_fwd: null pointer");
   TG_CHECK(tg_aligned16(x) && tg_aligned16(w) && tg_aligned16(y), TG_EALIGN, "tg_conv2d_fwd: pointers must be 16 B aligned");
-  if (grouped(d) && !(d->algo != TG_ALGO_DIRECT && tg_conv2d_grouped_native_mfma(d, TG_GRP_FWD))) {
+  if (split_groups(d, TG_GRP_FWD)) {
     const Groups gr(d);
     for (int g = 0; g < gr.G && !rc; ++g)
       rc = tg_conv2d_fwd(&gr.d1, at(x, g * gr.xin), at(w, g * gr.wset[0]), at(bias, g * gr.bias), at(y, g * gr.yout), stream);
@@ -185,7 +151,7 @@ int tg_conv2d_fwd_masked(const TgConvDesc* d, const void* x, const void* w, cons
   TG_CHECK(d->epilogue == 0, TG_EINVAL, "tg_conv2d_fwd_masked: no bias / activation epilogue next to the mask");
   TG_CHECK(tg_aligned16(x) && tg_aligned16(w) && tg_aligned16(y) && tg_aligned16(mask_src), TG_EALIGN,
            "tg_conv2d_fwd_masked: pointers must be 16 B aligned");
-  if (grouped(d) && !(d->algo != TG_ALGO_DIRECT && tg_conv2d_fwd_mask_fusable_mfma(d) && tg_conv2d_grouped_native_mfma(d, TG_GRP_FWD))) {
+  if (split_groups(d, TG_GRP_FWD, true)) {
     const Groups gr(d);
     for (int g = 0; g < gr.G && !rc; ++g)
       rc = tg_conv2d_fwd_masked(&gr.d1, at(x, g * gr.xin), at(w, g * gr.wset[0]), at(mask_src, g * gr.yout), at(y, g * gr.yout), stream);
@@ -205,7 +171,7 @@ int tg_conv2d_bwd_data(const TgConvDesc* d, const void* gy, const void* w, void*
   TG_CHECK(gy && w && gx, TG_EINVAL, "tg_conv2d_bwd_data: null pointer");
   TG_CHECK(tg_aligned16(gy) && tg_aligned16(w) && tg_aligned16(gx), TG_EALIGN,
            "tg_conv2d_bwd_data: pointers must be 16 B aligned");
-  if (grouped(d) && !(d->algo != TG_ALGO_DIRECT && tg_conv2d_grouped_native_mfma(d, TG_GRP_DGRAD))) {
+  if (split_groups(d, TG_GRP_DGRAD)) {
     const Groups gr(d);
     for (int g = 0; g < gr.G && !rc; ++g)
       rc = tg_conv2d_bwd_data(&gr.d1, at(gy, g * gr.yout), at(w, g * gr.wset[1]), at(gx, g * gr.xin), stream);
@@ -222,7 +188,7 @@ int tg_conv2d_bwd_data_masked(const TgConvDesc* d, const void* gy, const void* w
   TG_CHECK(gy && w && gx && x_act, TG_EINVAL, "tg_conv2d_bwd_data_masked: null pointer");
   TG_CHECK(tg_aligned16(gy) && tg_aligned16(w) && tg_aligned16(gx) && tg_aligned16(x_act), TG_EALIGN,
            "tg_conv2d_bwd_data_masked: pointers must be 16 B aligned");
-  if (grouped(d) && !(d->algo != TG_ALGO_DIRECT && tg_conv2d_bwd_data_mask_fusable_mfma(d) && tg_conv2d_grouped_native_mfma(d, TG_GRP_DGRAD))) {
+  if (split_groups(d, TG_GRP_DGRAD, true)) {
     const Groups gr(d);
     for (int g = 0; g < gr.G && !rc; ++g)
       rc = tg_conv2d_bwd_data_masked(&gr.d1, at(gy, g * gr.yout), at(w, g * gr.wset[1]), at(x_act, g * gr.xin), at(gx, g * gr.xin), stream);
@@ -251,7 +217,7 @@ int tg_conv2d_bwd_data_unpool(const TgConvDesc* d, const void* gy_pooled, const 
                (!gy_out || tg_aligned16(gy_out)),
            TG_EALIGN, "tg_conv2d_bwd_data_unpool: pointers must be 16 B aligned");
   TG_CHECK(d->algo != TG_ALGO_DIRECT, TG_ENOSUP, "tg_conv2d_bwd_data_unpool: MFMA path only (tg_conv2d_bwd_data_unpool_supported)");
-  if (grouped(d) && !tg_conv2d_grouped_native_mfma(d, TG_GRP_DGRAD)) {
+  if (split_groups(d, TG_GRP_DGRAD)) {
     const Groups gr(d);      // one group's pooled gradient is a quarter of its gradient, its sign bytes a sixteenth
     const size_t es = d->dtype == TG_F32 ? 4 : 2;
     for (int g = 0; g < gr.G && !rc; ++g)
@@ -271,7 +237,7 @@ int tg_conv2d_bwd_data_unpool_act(const TgConvDesc* d, const void* gy_pooled, co
                (!gy_out || tg_aligned16(gy_out)),
            TG_EALIGN, "tg_conv2d_bwd_data_unpool_act: pointers must be 16 B aligned");
   TG_CHECK(d->algo != TG_ALGO_DIRECT, TG_ENOSUP, "tg_conv2d_bwd_data_unpool_act: MFMA path only (tg_conv2d_bwd_data_unpool_supported)");
-  if (grouped(d) && !tg_conv2d_grouped_native_mfma(d, TG_GRP_DGRAD)) {
+  if (split_groups(d, TG_GRP_DGRAD)) {
     const Groups gr(d);
     for (int g = 0; g < gr.G && !rc; ++g)
       rc = tg_conv2d_bwd_data_unpool_act(&gr.d1, at(gy_pooled, g * (gr.yout / 4)), at(y_act, g * gr.yout), at(w, g * gr.wset[1]),
@@ -311,7 +277,7 @@ int tg_conv2d_bwd_weight2(const TgConvDesc* d, int nb, const void* xa, const voi
   TG_CHECK(xa && gya && xb && gyb && gw && nb > 0, TG_EINVAL, "tg_conv2d_bwd_weight2: bad arguments");
   TG_CHECK(d->algo != TG_ALGO_DIRECT && tg_conv2d_bwd_weight2_supported_mfma(d), TG_ENOSUP,
            "tg_conv2d_bwd_weight2: layer not taken by the tile kernel (query tg_conv2d_bwd_weight2_workspace first)");
-  if (grouped(d) && !tg_conv2d_grouped_native_mfma(d, TG_GRP_WGRAD)) {
+  if (split_groups(d, TG_GRP_WGRAD)) {
     TG_CHECK(nb % d->groups == 0, TG_EINVAL, "tg_conv2d_bwd_weight2: groups %d does not divide the second batch of %d", d->groups, nb);
     const Groups gr(d);
     const size_t part = ws_bytes / gr.G & ~(size_t)255, xb1 = gr.xin / gr.d1.n * (nb / gr.G), yb1 = gr.yout / gr.d1.n * (nb / gr.G);
@@ -360,7 +326,7 @@ int tg_conv2d_fwd_pool(const TgConvDesc* d, const void* x, const void* w_pack, c
   TG_CHECK(tg_aligned16(x) && tg_aligned16(w_pack) && tg_aligned16(y) && tg_aligned16(y_pooled), TG_EALIGN,
            "tg_conv2d_fwd_pool: pointers must be 16 B aligned");
   TG_CHECK(d->algo != TG_ALGO_DIRECT, TG_ENOSUP, "tg_conv2d_fwd_pool: MFMA path only (query tg_conv2d_fwd_pool_supported)");
-  if (grouped(d) && !tg_conv2d_grouped_native_mfma(d, TG_GRP_FWD)) {
+  if (split_groups(d, TG_GRP_FWD)) {
     const Groups gr(d);
     for (int g = 0; g < gr.G && !rc; ++g)
       rc = tg_conv2d_fwd_pool(&gr.d1, at(x, g * gr.xin), at(w_pack, g * gr.wset[0]), at(bias, g * gr.bias), at(y, g * gr.yout),
@@ -378,7 +344,7 @@ int tg_conv2d_fwd_pool_signs(const TgConvDesc* d, const void* x, const void* w_p
   TG_CHECK(tg_aligned16(x) && tg_aligned16(w_pack) && tg_aligned16(y_pooled) && (reinterpret_cast<uintptr_t>(y_signs) & 3u) == 0,
            TG_EALIGN, "tg_conv2d_fwd_pool_signs: pointers must be 16 B aligned (the sign bits: 4 B)");
   TG_CHECK(d->algo != TG_ALGO_DIRECT, TG_ENOSUP, "tg_conv2d_fwd_pool_signs: MFMA path only (query tg_conv2d_fwd_pool_supported)");
-  if (grouped(d) && !tg_conv2d_grouped_native_mfma(d, TG_GRP_FWD)) {
+  if (split_groups(d, TG_GRP_FWD)) {
     const Groups gr(d);
     const size_t es = d->dtype == TG_F32 ? 4 : 2;
     for (int g = 0; g < gr.G && !rc; ++g)
@@ -474,7 +440,7 @@ int tg_conv2d_bwd_weight_bias(const TgConvDesc* d, const void* x, const void* gy
   int rc = check_desc("tg_conv2d_bwd_weight_bias", d);
   if (rc) return rc;
   TG_CHECK(x && gy && gw && gbias, TG_EINVAL, "tg_conv2d_bwd_weight_bias: null pointer");
-  if (grouped(d) && !(d->algo != TG_ALGO_DIRECT && tg_conv2d_grouped_native_mfma(d, TG_GRP_WGRAD))) {
+  if (split_groups(d, TG_GRP_WGRAD)) {
     const Groups gr(d);
     const size_t part = ws_bytes / gr.G & ~(size_t)255;
     for (int g = 0; g < gr.G && !rc; ++g)
@@ -499,7 +465,7 @@ int tg_conv2d_bwd_weight2_bias(const TgConvDesc* d, int nb, const void* xa, cons
   TG_CHECK(d->algo != TG_ALGO_DIRECT && tg_conv2d_bwd_weight2_supported_mfma(d), TG_ENOSUP,
            "tg_conv2d_bwd_weight2_bias: layer not taken by the tile kernel");
   TG_CHECK(bias_segs >= 1 && bias_segs <= 3, TG_EINVAL, "tg_conv2d_bwd_weight2_bias: bias_segs %d", bias_segs);
-  if (grouped(d) && !tg_conv2d_grouped_native_mfma(d, TG_GRP_WGRAD)) {
+  if (split_groups(d, TG_GRP_WGRAD)) {
     TG_CHECK(nb % d->groups == 0, TG_EINVAL, "tg_conv2d_bwd_weight2_bias: groups %d does not divide the second batch of %d", d->groups, nb);
     const Groups gr(d);
     const size_t part = ws_bytes / gr.G & ~(size_t)255, xb1 = gr.xin / gr.d1.n * (nb / gr.G), yb1 = gr.yout / gr.d1.n * (nb / gr.G);
@@ -525,7 +491,7 @@ int tg_conv2d_bwd_weight(const TgConvDesc* d, const void* x, const void* gy, flo
   if (rc) return rc;
   TG_CHECK(x && gy && gw, TG_EINVAL, "tg_conv2d_bwd_weight: null pointer");
   TG_CHECK(tg_aligned16(x) && tg_aligned16(gy), TG_EALIGN, "tg_conv2d_bwd_weight: pointers must be 16 B aligned");
-  if (grouped(d) && !(d->algo != TG_ALGO_DIRECT && tg_conv2d_grouped_native_mfma(d, TG_GRP_WGRAD))) {
+  if (split_groups(d, TG_GRP_WGRAD)) {
     const Groups gr(d);
     const size_t part = ws_bytes / gr.G & ~(size_t)255;
     for (int g = 0; g < gr.G && !rc; ++g)

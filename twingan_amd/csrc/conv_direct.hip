@@ -3,7 +3,7 @@
 // parity path and the on-device cross-check for the MFMA kernels at sizes the CPU oracle cannot
 // reach.  Replaces Conv2D / Conv2DBackpropInput / Conv2DBackpropFilter behind
 // nets/pggan_utils.py:316-320 (reference, TF-1.8 kernels).
-#include "tg_common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -122,8 +122,6 @@ int tg_conv2d_bwd_data_direct(const TgConvDesc* d, const void* gy, const void* w
   TG_LAUNCH_CHECK("tg_conv2d_bwd_data(direct)");
   return TG_OK;
 }
-
-int tg_wgrad_slab_reduce(const float* slab, float* gw, int64_t nw, int nslices, int accumulate, hipStream_t s);
 
 static constexpr int DIRECT_PIX_PER_CHUNK = 2048;
 

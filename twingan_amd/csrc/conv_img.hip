@@ -12,7 +12,7 @@
 //   (wave w: 16-channel chunks w, w+4, ...), one LDS reduction at the end, conv_small's epilogue.
 // Reference call sites replaced: tf.contrib.layers.conv2d at nets/pggan_utils.py:316-320 for those stages and its
 // Conv2DBackpropInput gradient.
-#include "tg_common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -281,8 +281,12 @@ bool tg_conv_img_stats_supported(int n, int hin, int win, int cin, int hout, int
          tg_conv_img_supported(n, hin, win, cin, hout, wout, cout, k, pad_t, pad_l);
 }
 
-int tg_conv_img_run(int n, int hw, int cin, int cout, int epilogue, float alpha, const void* x, const void* wp,
-                    const float* bias, void* y, hipStream_t s, float* stats, const void* mask, int groups, size_t wset_elems) {
+int tg_conv_img_run(const TgConvShape& c, int epilogue, float alpha, const void* x, const void* wp, const float* bias, void* y,
+                    hipStream_t s, const TgConvExtras& ex) {
+  const int n = c.n, hw = c.hin, cin = c.cin, cout = c.cout, groups = ex.groups;
+  float* const stats = ex.stats;
+  const void* const mask = ex.mask;
+  const size_t wset_elems = ex.wset_elems;
   ImgGeom g;
   TG_CHECK(groups <= 1 || (hw == 8 && !stats), TG_ENOSUP, "conv_img: weight-set groups take the 8x8 maps (one image per workgroup)");
   g.npg = groups > 1 ? n / groups : 0;

@@ -17,7 +17,7 @@
 //
 // Reference call sites replaced: tf.contrib.layers.conv2d at nets/pggan_utils.py:316-320 and
 // its TF gradients (Conv2DBackpropInput / Conv2DBackpropFilter).
-#include "tg_common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -392,18 +392,18 @@ void pick_tile(int hout, int wout, Geom* g) {
   g->tiles_y = (hout + th - 1) / th;
 }
 
-int fill_geom(const char* who, int n, int hin, int win, int cin, int hout, int wout, int cout, int kh, int kw, int pad_t,
-              int pad_l, Geom* g) {
-  TG_CHECK(cin % 8 == 0 && cout % 8 == 0, TG_EALIGN, "%s(mfma): cin (%d) and cout (%d) must be multiples of 8", who, cin,
-           cout);
-  TG_CHECK((kh == 1 && kw == 1) || (kh == 3 && kw == 3), TG_ENOSUP, "%s(mfma): kernel %dx%d not supported", who, kh, kw);
-  g->n = n; g->hin = hin; g->win = win; g->cin = cin;
-  g->hout = hout; g->wout = wout; g->cout = cout;
-  g->cin_pad = (cin + 15) / 16 * 16;
-  g->pad_t = pad_t; g->pad_l = pad_l;
-  pick_tile(hout, wout, g);
+int fill_geom(const char* who, const TgConvShape& c, Geom* g) {
+  TG_CHECK(c.cin % 8 == 0 && c.cout % 8 == 0, TG_EALIGN, "%s(mfma): cin (%d) and cout (%d) must be multiples of 8", who, c.cin,
+           c.cout);
+  TG_CHECK((c.kh == 1 && c.kw == 1) || (c.kh == 3 && c.kw == 3), TG_ENOSUP, "%s(mfma): kernel %dx%d not supported", who, c.kh,
+           c.kw);
+  g->n = c.n; g->hin = c.hin; g->win = c.win; g->cin = c.cin;
+  g->hout = c.hout; g->wout = c.wout; g->cout = c.cout;
+  g->cin_pad = (c.cin + 15) / 16 * 16;
+  g->pad_t = c.pad_t; g->pad_l = c.pad_l;
+  pick_tile(c.hout, c.wout, g);
   const int ti = 1 << g->ti_log2;
-  g->tiles_img = (n + ti - 1) / ti;
+  g->tiles_img = (c.n + ti - 1) / ti;
   g->epilogue = 0;
   g->alpha = 1.f;
   return TG_OK;
@@ -441,10 +441,10 @@ int dispatch_fwd(const Geom& g, const bf16* x, const bf16* wp, const float* bias
 
 }  // namespace
 
-// Rewrites "k x k VALID on a k x k input" (1x1 output) as a 1x1 conv over k*k*cin channels: with NHWC
-// activations and HWIO weights both reshapes are free (nets/pggan.py:330-331,495).
 static inline bool is16(const TgConvDesc* d) { return d->dtype == TG_BF16 || d->dtype == TG_F16; }
 
+// Rewrites "k x k VALID on a k x k input" (1x1 output) as a 1x1 conv over k*k*cin channels: with NHWC
+// activations and HWIO weights both reshapes are free (nets/pggan.py:330-331,495).
 static bool as_dense(const TgConvDesc* d, TgConvDesc* o) {
   if (d->hout == 1 && d->wout == 1 && d->hin == d->kh && d->win == d->kw && d->pad_t == 0 && d->pad_l == 0 &&
       (d->kh > 1 || d->kw > 1)) {
@@ -457,38 +457,75 @@ static bool as_dense(const TgConvDesc* d, TgConvDesc* o) {
   return false;
 }
 
-bool tg_conv_tile_supported(int h, int w, int hout, int wout, int kh, int kw, int pad_t, int pad_l);
-bool tg_conv_img_supported(int n, int hin, int win, int cin, int hout, int wout, int cout, int k, int pad_t, int pad_l);
-bool tg_conv_small_supported(int n, int hout, int wout, int kh, int kw);
+// what every kernel newer than the first generation asks of a descriptor, the filter-gradient tile kernels included
+static bool second_gen_ok(const TgConvDesc* d) { return d->algo != TG_ALGO_MFMA_V1 && d->cin % 8 == 0 && d->cout % 8 == 0; }
 
-// Is the pack of (descriptor, mode) fragment-ordered?  Exactly when the dispatch of that direction ends in conv_img or
-// conv_small (tg_conv2d_fwd_mfma / tg_conv2d_bwd_data_mfma: the tile kernels first, then conv_img, then conv_small) --
-// the two kernels that fetch their weight fragments straight from L2: the layout is a property of the pack that its
-// kernel knows; callers treat packs as opaque.  (conv_small's test involves the batch: n * hout * wout <= 4096.)
-// A grouped descriptor (groups > 1) that no kernel takes whole is launched once per group on n / groups images (capi.hip):
-// its packs are read by THAT dispatch, so the question is asked of the one-group descriptor -- the whole batch can be over
-// conv_small's limit while one group is under it.
-bool tg_conv2d_grouped_native_mfma(const TgConvDesc* d0, int op);
-static bool pack_frag(const TgConvDesc* dg, int mode) {
-  TgConvDesc d1;
-  const TgConvDesc* d0 = dg;
-  if (dg->groups > 1) {
-    d1 = *dg;
-    if (!tg_conv2d_grouped_native_mfma(dg, mode)) d1.n = dg->n / dg->groups;      // mode 0 / 1 = TG_GRP_FWD / TG_GRP_DGRAD
-    d1.groups = 1;
-    d0 = &d1;
-  }
+// ---- the one kernel selection ------------------------------------------------------------------------------------------
+// Which kernel family a forward-shaped (TG_GRP_FWD) or backward-data-shaped (TG_GRP_DGRAD) call of a descriptor runs, and
+// the conv as that kernel sees it.  Every entry point, the pack layout and the grouped-call split below read this.
+//  * The pack is fragment-ordered exactly for FAM_IMG / FAM_SMALL, so only under TG_ALGO_MFMA: TG_ALGO_MFMA_V1 always runs
+//    the first-generation kernels, the direct algorithm (which never reaches the *_mfma functions) is "no MFMA call", and
+//    both get the row-major pack.
+//  * conv_small counts the pixels of the kernel's OUTPUT: n * hin * win of the descriptor in the backward-data direction.
+//  * The dense rewrite runs as a 1x1 conv over a 1x1 map: n pixels in both directions.
+//  * A grouped call that is split (tg_conv2d_grouped_native_mfma) is selected on n / groups images: callers pass the
+//    one-group descriptor.
+namespace {
+enum Family { FAM_NONE, FAM_TILE, FAM_IMG, FAM_SMALL, FAM_GEN1 };
+struct ConvSel {
+  Family family;
+  TgConvShape c;
+  bool second_gen() const { return family == FAM_TILE || family == FAM_IMG || family == FAM_SMALL; }
+};
+}  // namespace
+
+static ConvSel select_conv(const TgConvDesc* d0, int dir) {
   TgConvDesc dd;
   const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  if (!is16(d) || d->algo != TG_ALGO_MFMA || d->kh != d->kw || (d->kh != 3 && d->kh != 1) || d->cin % 8 || d->cout % 8) return false;
-  // the conv the kernels see: forward, or the same conv over gy with the rotated pack (mode 1)
-  const bool fw = mode == 0;
-  const int hi = fw ? d->hin : d->hout, wi = fw ? d->win : d->wout, ci = fw ? d->cin : d->cout;
-  const int ho = fw ? d->hout : d->hin, wo = fw ? d->wout : d->win, co = fw ? d->cout : d->cin;
-  const int pt = fw ? d->pad_t : d->kh - 1 - d->pad_t, pl = fw ? d->pad_l : d->kw - 1 - d->pad_l;
-  if (tg_conv_tile_supported(hi, wi, ho, wo, d->kh, d->kw, d->pad_t, d->pad_l)) return false;
-  if (tg_conv_img_supported(d->n, hi, wi, ci, ho, wo, co, d->kh, pt, pl)) return true;
-  return d->pad_t == d->pad_l && tg_conv_small_supported(d->n, ho, wo, d->kh, d->kw);      // conv_small (4x4 maps, dense layers)
+  ConvSel r;
+  if (dir == TG_GRP_FWD)
+    r.c = TgConvShape{d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->kw, d->pad_t, d->pad_l};
+  else
+    r.c = TgConvShape{d->n, d->hout, d->wout, d->cout, d->hin, d->win, d->cin, d->kh, d->kw, d->kh - 1 - d->pad_t,
+                      d->kw - 1 - d->pad_l};
+  const TgConvShape& c = r.c;
+  if (!is16(d) || d->algo == TG_ALGO_DIRECT)
+    r.family = FAM_NONE;
+  else if (!second_gen_ok(d))
+    r.family = FAM_GEN1;
+  else if (tg_conv_tile_supported(c.hin, c.win, c.hout, c.wout, c.kh, c.kw, c.pad_t, c.pad_l))
+    r.family = FAM_TILE;
+  else if (c.kh == c.kw && tg_conv_img_supported(c.n, c.hin, c.win, c.cin, c.hout, c.wout, c.cout, c.kh, c.pad_t, c.pad_l))
+    r.family = FAM_IMG;
+  else if (c.pad_t == c.pad_l && tg_conv_small_supported(c.n, c.hout, c.wout, c.kh, c.kw))
+    r.family = FAM_SMALL;      // 4x4 maps, dense layers, small batches of anything else
+  else
+    r.family = FAM_GEN1;
+  return r;
+}
+
+// Grouped calls (TgConvDesc::groups > 1) the dispatch takes as ONE launch: the kernel picks the weight set from the image
+// index.  Everything else -- filter gradients always -- is launched once per group by the entry point (capi.hip).
+// Grouped unpool and grouped weight-resident tile cases keep tg_conv_tile_grouped_native's conservative answer, even where
+// the tile dispatch would in fact stay on the plain kernel.
+bool tg_conv2d_grouped_native_mfma(const TgConvDesc* d, int op) {
+  if (d->groups < 2 || op == TG_GRP_WGRAD) return false;
+  const ConvSel k = select_conv(d, op);
+  return k.family == FAM_TILE ? tg_conv_tile_grouped_native(k.c) : k.second_gen();
+}
+
+// Is the pack of (descriptor, mode) fragment-ordered?  Exactly when the launch that reads it is conv_img or conv_small --
+// the two kernels that fetch their weight fragments straight from L2: the layout is a property of the pack that its
+// kernel knows; callers treat packs as opaque.  A grouped descriptor that is split is read by the one-group launches: the
+// whole batch can be over conv_small's limit while one group is under it.
+static bool pack_frag(const TgConvDesc* dg, int mode) {
+  TgConvDesc d1 = *dg;
+  if (dg->groups > 1) {
+    if (!tg_conv2d_grouped_native_mfma(dg, mode)) d1.n = dg->n / dg->groups;
+    d1.groups = 1;
+  }
+  const Family f = select_conv(&d1, mode).family;
+  return f == FAM_IMG || f == FAM_SMALL;
 }
 extern "C" int tg_conv2d_pack_layout(const TgConvDesc* d, int mode) { return d && pack_frag(d, mode) ? 1 : 0; }
 
@@ -634,233 +671,132 @@ int tg_conv2d_pack_weights_multi(const void* table_device, int njobs, int total_
   return TG_OK;
 }
 
-bool tg_conv_tile_supported(int h, int w, int hout, int wout, int kh, int kw, int pad_t, int pad_l);
-int tg_conv_tile_run(int n, int h, int w, int cin, int cout, int k, int pad, int epilogue, float alpha, const void* x,
-                     const void* wp, const float* bias, void* y, hipStream_t s, const void* mask = nullptr,
-                     float* stats = nullptr, int stat_chunks = 0, int* chunks_query = nullptr, void* ypool = nullptr,
-                     void* ymask = nullptr, const void* up_src = nullptr, const void* up_signs = nullptr, float up_alpha = 0.f,
-                     void* up_store = nullptr, const void* up_z = nullptr, int groups = 1, size_t wset_elems = 0);
-bool tg_conv_tile_grouped_native(int n, int h, int w, int cin, int cout);
-
-// Grouped calls (TgConvDesc::groups > 1) the dispatch below takes as ONE launch: the kernel picks the weight set from the
-// image index.  op: 0 forward-shaped (forward, masked, pool), 1 backward-data-shaped, 2 filter gradient.  Everything else
-// is launched once per group by the entry point (capi.hip).
-bool tg_conv_img_supported(int n, int hin, int win, int cin, int hout, int wout, int cout, int k, int pad_t, int pad_l);
-bool tg_conv_small_supported(int n, int hout, int wout, int kh, int kw);
-bool tg_conv2d_grouped_native_mfma(const TgConvDesc* d0, int op) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  if (!is16(d) || d->algo == TG_ALGO_MFMA_V1 || d->cin % 8 || d->cout % 8 || d->groups < 2) return false;
-  if (op == 2) return false;      // filter gradients: one launch per group
-  // the conv the kernels see: forward (x -> y) or the same conv over gy with the rotated pack (gy -> gx)
-  const bool fw = op == 0;
-  const int hi = fw ? d->hin : d->hout, wi = fw ? d->win : d->wout, ci = fw ? d->cin : d->cout;
-  const int ho = fw ? d->hout : d->hin, wo = fw ? d->wout : d->win, co = fw ? d->cout : d->cin;
-  const int pt = fw ? d->pad_t : d->kh - 1 - d->pad_t, pl = fw ? d->pad_l : d->kw - 1 - d->pad_l;
-  if (tg_conv_tile_supported(hi, wi, ho, wo, d->kh, d->kw, d->pad_t, d->pad_l)) return tg_conv_tile_grouped_native(d->n, hi, wi, ci, co);
-  if (d->kh == d->kw && tg_conv_img_supported(d->n, hi, wi, ci, ho, wo, co, d->kh, pt, pl)) return true;
-  return d->pad_t == d->pad_l && tg_conv_small_supported(d->n, ho, wo, d->kh, d->kw);
+// the weight sets of a descriptor as the kernels' optional operands (mode 0 forward / 1 backward-data pack)
+static TgConvExtras weight_sets(const TgConvDesc* d, int mode) {
+  TgConvExtras ex;
+  if (d->groups > 1) {
+    TgConvDesc d1 = *d;
+    d1.groups = 1;
+    ex.groups = d->groups;
+    ex.wset_elems = tg_conv2d_pack_elems(&d1, mode);
+  }
+  return ex;
 }
-// weight sets of a descriptor and the elements of one set's pack (mode 0 forward / 1 backward-data operand)
-static int ngroups(const TgConvDesc* d) { return d->groups > 1 ? d->groups : 1; }
-static size_t wset_elems(const TgConvDesc* d, int mode) {
-  if (d->groups <= 1) return 0;
-  TgConvDesc d1 = *d;
-  d1.groups = 1;
-  return tg_conv2d_pack_elems(&d1, mode);
+
+// runs the selected conv: y = epilogue(conv(x, wp)) on the family's kernel, the first-generation kernels otherwise
+static int run_selected(const char* who, const ConvSel& k, int epilogue, float alpha, const void* x, const void* wp,
+                        const float* bias, void* y, hipStream_t s, const TgConvExtras& ex) {
+  switch (k.family) {
+    case FAM_TILE: return tg_conv_tile_run(k.c, epilogue, alpha, x, wp, bias, y, s, ex);
+    case FAM_IMG: return tg_conv_img_run(k.c, epilogue, alpha, x, wp, bias, y, s, ex);
+    case FAM_SMALL: return tg_conv_small_run(k.c, epilogue, alpha, x, wp, bias, y, s, ex);
+    default: break;
+  }
+  TG_CHECK(k.family == FAM_GEN1, TG_ENOSUP, "%s(mfma): 16-bit activations only", who);
+  TG_CHECK(ex.groups <= 1, TG_ENOSUP, "%s(mfma): weight-set groups on a first-generation kernel", who);
+  TG_CHECK(!ex.mask && !ex.stats, TG_ENOSUP, "%s(mfma): no mask / statistics epilogue on a first-generation kernel", who);
+  Geom g;
+  int rc = fill_geom(who, k.c, &g);
+  if (rc) return rc;
+  g.epilogue = epilogue;
+  g.alpha = alpha;
+  if (k.c.kh == 1) return dispatch_fwd<1, 1>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
+  return dispatch_fwd<3, 3>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
+}
+
+int tg_conv2d_fwd_mfma(const TgConvDesc* d, const void* x, const void* wp, const float* bias, void* y, hipStream_t s) {
+  const ConvSel k = select_conv(d, TG_GRP_FWD);
+  TG_CHECK(k.family != FAM_NONE, TG_ENOSUP, "tg_conv2d_fwd(mfma): 16-bit activations only");
+  TG_CHECK(!(d->epilogue & TG_EPI_BIAS) || bias, TG_EINVAL, "tg_conv2d_fwd: bias epilogue without bias pointer");
+  return run_selected("tg_conv2d_fwd", k, d->epilogue, d->lrelu_alpha, x, wp, bias, y, s, weight_sets(d, 0));
 }
 
 // Forward conv that also writes the 2x2 average pool of its output (conv_tile.hip POOL kernels): 3x3 SAME, even h / w,
 // shapes the tile kernels take
-bool tg_conv2d_fwd_pool_supported_mfma(const TgConvDesc* d0) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  if (!is16(d) || d->algo == TG_ALGO_MFMA_V1 || d->kh != 3 || d->cin % 8 || d->cout % 8) return false;
-  return tg_conv_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l);
+bool tg_conv2d_fwd_pool_supported_mfma(const TgConvDesc* d) {
+  const ConvSel k = select_conv(d, TG_GRP_FWD);
+  return k.family == FAM_TILE && k.c.kh == 3;
 }
 
-int tg_conv2d_fwd_pool_mfma(const TgConvDesc* d0, const void* x, const void* wp, const float* bias, void* y, void* ypool,
+int tg_conv2d_fwd_pool_mfma(const TgConvDesc* d, const void* x, const void* wp, const float* bias, void* y, void* ypool,
                             hipStream_t s, void* ymask) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  TG_CHECK(tg_conv2d_fwd_pool_supported_mfma(d0), TG_ENOSUP, "tg_conv2d_fwd_pool: shape not taken (query tg_conv2d_fwd_pool_supported)");
+  TG_CHECK(tg_conv2d_fwd_pool_supported_mfma(d), TG_ENOSUP, "tg_conv2d_fwd_pool: shape not taken (query tg_conv2d_fwd_pool_supported)");
   TG_CHECK(!(d->epilogue & TG_EPI_BIAS) || bias, TG_EINVAL, "tg_conv2d_fwd_pool: bias epilogue without bias pointer");
-  return tg_conv_tile_run(d->n, d->hin, d->win, d->cin, d->cout, d->kh, d->pad_t, d->epilogue, d->lrelu_alpha, x, wp, bias, y,
-                          s, nullptr, nullptr, 0, nullptr, ypool, ymask, nullptr, nullptr, 0.f, nullptr, nullptr, ngroups(d0),
-                          wset_elems(d0, 0));
+  TgConvExtras ex = weight_sets(d, 0);
+  ex.ypool = ypool;
+  ex.ymask = ymask;
+  return tg_conv_tile_run(select_conv(d, TG_GRP_FWD).c, d->epilogue, d->lrelu_alpha, x, wp, bias, y, s, ex);
 }
 
-// Forward conv that also writes the per-workgroup statistics partials of its output (conv_tile.hip STATS kernels).
-// chunks per image of the dispatch this descriptor selects, 0 when that dispatch has no statistics epilogue.
-bool tg_conv_small_supported(int n, int hout, int wout, int kh, int kw);
-bool tg_conv_small_stats_supported(int n, int hin, int win, int hout, int wout, int cout, int k, int pad_t, int pad_l);
-int tg_conv_small_run(int n, int hin, int win, int cin, int hout, int wout, int cout, int k, int pad_t, int pad_l,
-                      int epilogue, float alpha, const void* x, const void* wp, const float* bias, void* y, hipStream_t s,
-                      float* stats = nullptr, const void* mask = nullptr, int groups = 1, size_t wset_elems = 0);
-bool tg_conv_img_supported(int n, int hin, int win, int cin, int hout, int wout, int cout, int k, int pad_t, int pad_l);
-bool tg_conv_img_stats_supported(int n, int hin, int win, int cin, int hout, int wout, int cout, int k, int pad_t, int pad_l);
-int tg_conv_img_run(int n, int hw, int cin, int cout, int epilogue, float alpha, const void* x, const void* wp,
-                    const float* bias, void* y, hipStream_t s, float* stats = nullptr, const void* mask = nullptr, int groups = 1,
-                    size_t wset_elems = 0);
-
-int tg_conv2d_fwd_stats_chunks_mfma(const TgConvDesc* d0) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  if (!is16(d) || d->algo == TG_ALGO_MFMA_V1 || d->kh != 3 || d->cin % 8 || d->cout % 8 || d->epilogue) return 0;
-  if (!tg_conv_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l)) {
-    // 8x8 maps: conv_img holds a whole image per workgroup; 4x4 maps: an image is 16 lanes of conv_small's column block
-    // -- ONE chunk per image (the order of the tests mirrors tg_conv2d_fwd_mfma's dispatch)
-    if (d->kh == d->kw && tg_conv_img_supported(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l))
-      return tg_conv_img_stats_supported(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l) ? 1 : 0;
-    if (d->pad_t == d->pad_l && tg_conv_small_supported(d->n, d->hout, d->wout, d->kh, d->kw))
-      return tg_conv_small_stats_supported(d->n, d->hin, d->win, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l) ? 1 : 0;
-    return 0;
+// Forward conv that also writes the per-workgroup statistics partials of its output: chunks per image of the kernel this
+// descriptor selects, 0 when that kernel has no statistics epilogue.  8x8 maps: conv_img holds a whole image per
+// workgroup; 4x4 maps: an image is 16 lanes of conv_small's column block -- ONE chunk per image.
+int tg_conv2d_fwd_stats_chunks_mfma(const TgConvDesc* d) {
+  const ConvSel k = select_conv(d, TG_GRP_FWD);
+  const TgConvShape& c = k.c;
+  if (c.kh != 3 || d->epilogue) return 0;
+  switch (k.family) {
+    case FAM_TILE: return tg_conv_tile_stats_chunks(c);
+    case FAM_IMG: return tg_conv_img_stats_supported(c.n, c.hin, c.win, c.cin, c.hout, c.wout, c.cout, c.kh, c.pad_t, c.pad_l) ? 1 : 0;
+    case FAM_SMALL: return tg_conv_small_stats_supported(c.n, c.hin, c.win, c.hout, c.wout, c.cout, c.kh, c.pad_t, c.pad_l) ? 1 : 0;
+    default: return 0;
   }
-  int chunks = 0;
-  if (tg_conv_tile_run(d->n, d->hin, d->win, d->cin, d->cout, d->kh, d->pad_t, 0, 0.f, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, 0, &chunks) != TG_OK)
-    return 0;
-  return chunks;
 }
 
-int tg_conv2d_fwd_stats_mfma(const TgConvDesc* d0, const void* x, const void* wp, void* y, float* partials, int chunks,
+int tg_conv2d_fwd_stats_mfma(const TgConvDesc* d, const void* x, const void* wp, void* y, float* partials, int chunks,
                              hipStream_t s) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  TG_CHECK(chunks > 0 && chunks == tg_conv2d_fwd_stats_chunks_mfma(d0), TG_EINVAL,
+  TG_CHECK(chunks > 0 && chunks == tg_conv2d_fwd_stats_chunks_mfma(d), TG_EINVAL,
            "tg_conv2d_fwd_stats: chunks %d does not match tg_conv2d_fwd_stats_chunks()", chunks);
-  if (!tg_conv_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l)) {
-    if (tg_conv_img_supported(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l))
-      return tg_conv_img_run(d->n, d->hin, d->cin, d->cout, 0, d->lrelu_alpha, x, wp, nullptr, y, s, partials);
-    return tg_conv_small_run(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l, 0,
-                             d->lrelu_alpha, x, wp, nullptr, y, s, partials);
-  }
-  return tg_conv_tile_run(d->n, d->hin, d->win, d->cin, d->cout, d->kh, d->pad_t, 0, d->lrelu_alpha, x, wp, nullptr, y, s,
-                          nullptr, partials, chunks, nullptr);
+  TgConvExtras ex;
+  ex.stats = partials;
+  ex.stat_chunks = chunks;
+  return run_selected("tg_conv2d_fwd_stats", select_conv(d, TG_GRP_FWD), 0, d->lrelu_alpha, x, wp, nullptr, y, s, ex);
 }
 
-
-
-int tg_conv2d_fwd_mfma(const TgConvDesc* d0, const void* x, const void* wp, const float* bias, void* y, hipStream_t s) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  TG_CHECK(is16(d), TG_ENOSUP, "tg_conv2d_fwd(mfma): 16-bit activations only");
-  TG_CHECK(!(d->epilogue & TG_EPI_BIAS) || bias, TG_EINVAL, "tg_conv2d_fwd: bias epilogue without bias pointer");
-  if (d->algo != TG_ALGO_MFMA_V1 && d->cin % 8 == 0 && d->cout % 8 == 0 &&
-      tg_conv_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l))
-    return tg_conv_tile_run(d->n, d->hin, d->win, d->cin, d->cout, d->kh, d->pad_t, d->epilogue, d->lrelu_alpha, x, wp,
-                            bias, y, s, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr,
-                            ngroups(d0), wset_elems(d0, 0));
-  if (d->algo != TG_ALGO_MFMA_V1 && d->kh == d->kw &&
-      tg_conv_img_supported(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l))
-    return tg_conv_img_run(d->n, d->hin, d->cin, d->cout, d->epilogue, d->lrelu_alpha, x, wp, bias, y, s, nullptr, nullptr,
-                           ngroups(d0), wset_elems(d0, 0));
-  if (d->algo != TG_ALGO_MFMA_V1 && d->cin % 8 == 0 && d->cout % 8 == 0 && d->pad_t == d->pad_l &&
-      tg_conv_small_supported(d->n, d->hout, d->wout, d->kh, d->kw))
-    return tg_conv_small_run(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l,
-                             d->epilogue, d->lrelu_alpha, x, wp, bias, y, s, nullptr, nullptr, ngroups(d0), wset_elems(d0, 0));
-  TG_CHECK(d0->groups <= 1, TG_ENOSUP, "tg_conv2d_fwd(mfma): weight-set groups on a first-generation kernel");
-  Geom g;
-  int rc = fill_geom("tg_conv2d_fwd", d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->kw, d->pad_t,
-                     d->pad_l, &g);
-  if (rc) return rc;
-  g.epilogue = d->epilogue;
-  g.alpha = d->lrelu_alpha;
-  TG_CHECK(!(d->epilogue & TG_EPI_BIAS) || bias, TG_EINVAL, "tg_conv2d_fwd: bias epilogue without bias pointer");
-  if (d->kh == 1) return dispatch_fwd<1, 1>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
-  return dispatch_fwd<3, 3>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
-}
-
-// Forward conv whose output is multiplied by the LeakyReLU derivative of `mask_src` (same shape as the output): the tile
-// kernels' mask epilogue (built for the masked backward-data) on the forward pack.  Shapes the tile kernels take, no
+// Forward conv whose output is multiplied by the LeakyReLU derivative of `mask_src` (same shape as the output): the mask
+// epilogue of the tile kernels, conv_img and conv_small (built for the masked backward-data) on the forward pack.  No
 // bias / activation epilogue.
-bool tg_conv2d_fwd_mask_fusable_mfma(const TgConvDesc* d0) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  if (!is16(d) || d->algo == TG_ALGO_MFMA_V1 || d->cin % 8 != 0 || d->cout % 8 != 0 || d->epilogue != 0) return false;
-  if (tg_conv_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l)) return true;
-  // 8x8 / 4x4 maps and the dense rewrite: conv_img / conv_small carry the same mask epilogue (tests as tg_conv2d_fwd_mfma's)
-  if (d->kh == d->kw && tg_conv_img_supported(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l))
-    return true;
-  return d->pad_t == d->pad_l && tg_conv_small_supported(d->n, d->hout, d->wout, d->kh, d->kw);
+bool tg_conv2d_fwd_mask_fusable_mfma(const TgConvDesc* d) {
+  return d->epilogue == 0 && select_conv(d, TG_GRP_FWD).second_gen();
 }
 
-int tg_conv2d_fwd_masked_mfma(const TgConvDesc* d0, const void* x, const void* wp, const void* mask_src, void* y, hipStream_t s) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  TG_CHECK(tg_conv2d_fwd_mask_fusable_mfma(d0), TG_ENOSUP, "tg_conv2d_fwd_masked(mfma): mask not fusable here");
-  if (tg_conv_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l))
-    return tg_conv_tile_run(d->n, d->hin, d->win, d->cin, d->cout, d->kh, d->pad_t, 0, d->lrelu_alpha, x, wp, nullptr, y, s,
-                            mask_src, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, ngroups(d0),
-                            wset_elems(d0, 0));
-  if (d->kh == d->kw && tg_conv_img_supported(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l))
-    return tg_conv_img_run(d->n, d->hin, d->cin, d->cout, 0, d->lrelu_alpha, x, wp, nullptr, y, s, nullptr, mask_src, ngroups(d0),
-                           wset_elems(d0, 0));
-  return tg_conv_small_run(d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->pad_t, d->pad_l, 0,
-                           d->lrelu_alpha, x, wp, nullptr, y, s, nullptr, mask_src, ngroups(d0), wset_elems(d0, 0));
+int tg_conv2d_fwd_masked_mfma(const TgConvDesc* d, const void* x, const void* wp, const void* mask_src, void* y, hipStream_t s) {
+  TG_CHECK(tg_conv2d_fwd_mask_fusable_mfma(d), TG_ENOSUP, "tg_conv2d_fwd_masked(mfma): mask not fusable here");
+  TgConvExtras ex = weight_sets(d, 0);
+  ex.mask = mask_src;
+  return run_selected("tg_conv2d_fwd_masked", select_conv(d, TG_GRP_FWD), 0, d->lrelu_alpha, x, wp, nullptr, y, s, ex);
 }
 
 // Can the LeakyReLU backward of the producer of x be folded into this backward-data's epilogue?
-bool tg_conv2d_bwd_data_mask_fusable_mfma(const TgConvDesc* d0) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  if (!is16(d) || d->algo == TG_ALGO_MFMA_V1 || d->cin % 8 != 0 || d->cout % 8 != 0) return false;
-  if (tg_conv_tile_supported(d->hout, d->wout, d->hin, d->win, d->kh, d->kw, d->pad_t, d->pad_l)) return true;
-  // the 8x8 / 4x4 maps and the dense k x k VALID layers (conv_img / conv_small: the same tests as tg_conv2d_bwd_data_mfma)
-  if (d->kh == d->kw && tg_conv_img_supported(d->n, d->hout, d->wout, d->cout, d->hin, d->win, d->cin, d->kh, d->kh - 1 - d->pad_t,
-                                              d->kw - 1 - d->pad_l))
-    return true;
-  return d->pad_t == d->pad_l && tg_conv_small_supported(d->n, d->hin, d->win, d->kh, d->kw);
-}
+bool tg_conv2d_bwd_data_mask_fusable_mfma(const TgConvDesc* d) { return select_conv(d, TG_GRP_DGRAD).second_gen(); }
 
-int tg_conv2d_bwd_data_mfma(const TgConvDesc* d0, const void* gy, const void* wp, void* gx, hipStream_t s,
-                            const void* mask) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  TG_CHECK(is16(d), TG_ENOSUP, "tg_conv2d_bwd_data(mfma): 16-bit activations only");
-  TG_CHECK(!mask || tg_conv2d_bwd_data_mask_fusable_mfma(d0), TG_ENOSUP, "tg_conv2d_bwd_data(mfma): mask not fusable here");
-  if (d->algo != TG_ALGO_MFMA_V1 && d->cin % 8 == 0 && d->cout % 8 == 0 &&
-      tg_conv_tile_supported(d->hout, d->wout, d->hin, d->win, d->kh, d->kw, d->pad_t, d->pad_l))
-    return tg_conv_tile_run(d->n, d->hout, d->wout, d->cout, d->cin, d->kh, d->kh - 1 - d->pad_t, 0,
-                            mask ? d->lrelu_alpha : 1.f, gy, wp, nullptr, gx, s, mask, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, 0.f, nullptr, nullptr, ngroups(d0), wset_elems(d0, 1));
-  // backward-data = the same conv over gy with the rotated pack: in = (hout, wout, cout), out = (hin, win, cin), pad' = k-1-pad
-  if (d->algo != TG_ALGO_MFMA_V1 && d->kh == d->kw &&
-      tg_conv_img_supported(d->n, d->hout, d->wout, d->cout, d->hin, d->win, d->cin, d->kh, d->kh - 1 - d->pad_t,
-                            d->kw - 1 - d->pad_l))
-    return tg_conv_img_run(d->n, d->hout, d->cout, d->cin, 0, mask ? d->lrelu_alpha : 1.f, gy, wp, nullptr, gx, s, nullptr, mask,
-                           ngroups(d0), wset_elems(d0, 1));
-  if (d->algo != TG_ALGO_MFMA_V1 && d->cin % 8 == 0 && d->cout % 8 == 0 && d->pad_t == d->pad_l &&
-      tg_conv_small_supported(d->n, d->hin, d->win, d->kh, d->kw))
-    return tg_conv_small_run(d->n, d->hout, d->wout, d->cout, d->hin, d->win, d->cin, d->kh, d->kh - 1 - d->pad_t,
-                             d->kw - 1 - d->pad_l, 0, mask ? d->lrelu_alpha : 1.f, gy, wp, nullptr, gx, s, nullptr, mask, ngroups(d0),
-                             wset_elems(d0, 1));
-  TG_CHECK(d0->groups <= 1, TG_ENOSUP, "tg_conv2d_bwd_data(mfma): weight-set groups on a first-generation kernel");
-  Geom g;   // a forward conv over gy: in = (hout,wout,cout), out = (hin,win,cin), pad' = k-1-pad
-  int rc = fill_geom("tg_conv2d_bwd_data", d->n, d->hout, d->wout, d->cout, d->hin, d->win, d->cin, d->kh, d->kw,
-                     d->kh - 1 - d->pad_t, d->kw - 1 - d->pad_l, &g);
-  if (rc) return rc;
-  if (d->kh == 1) return dispatch_fwd<1, 1>(g, (const bf16*)gy, (const bf16*)wp, nullptr, (bf16*)gx, s);
-  return dispatch_fwd<3, 3>(g, (const bf16*)gy, (const bf16*)wp, nullptr, (bf16*)gx, s);
+int tg_conv2d_bwd_data_mfma(const TgConvDesc* d, const void* gy, const void* wp, void* gx, hipStream_t s, const void* mask) {
+  const ConvSel k = select_conv(d, TG_GRP_DGRAD);
+  TG_CHECK(k.family != FAM_NONE, TG_ENOSUP, "tg_conv2d_bwd_data(mfma): 16-bit activations only");
+  TG_CHECK(!mask || k.second_gen(), TG_ENOSUP, "tg_conv2d_bwd_data(mfma): mask not fusable here");
+  TgConvExtras ex = weight_sets(d, 1);
+  ex.mask = mask;
+  return run_selected("tg_conv2d_bwd_data", k, 0, mask ? d->lrelu_alpha : 1.f, gy, wp, nullptr, gx, s, ex);
 }
 
 // Backward-data of a discriminator block's last conv straight from the gradient of the POOLED output and the layer's sign
-// bytes (conv_tile.hip UNPOOL kernels): the tile kernels' shapes with 32-channel chunks of the incoming gradient
-bool tg_conv2d_bwd_data_unpool_supported_mfma(const TgConvDesc* d0) {
-  TgConvDesc dd;
-  const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
-  return d == d0 && is16(d) && d->algo != TG_ALGO_MFMA_V1 && d->kh == 3 && d->kw == 3 && d->cin % 8 == 0 && d->cout % 32 == 0 &&
-         d->hout % 2 == 0 && d->wout % 2 == 0 &&
-         tg_conv_tile_supported(d->hout, d->wout, d->hin, d->win, d->kh, d->kw, d->pad_t, d->pad_l);
+// bytes (conv_tile.hip UNPOOL kernels): the tile kernels' 3x3 shapes with 32-channel chunks of the incoming gradient
+bool tg_conv2d_bwd_data_unpool_supported_mfma(const TgConvDesc* d) {
+  const ConvSel k = select_conv(d, TG_GRP_DGRAD);
+  return k.family == FAM_TILE && k.c.kh == 3 && d->cout % 32 == 0 && d->hout % 2 == 0 && d->wout % 2 == 0;
 }
 
 int tg_conv2d_bwd_data_unpool_mfma(const TgConvDesc* d, const void* gy_pooled, const void* y_signs, const void* wp, void* gx,
                                    hipStream_t s, const void* mask, void* gy_out, const void* y_act) {
   TG_CHECK(tg_conv2d_bwd_data_unpool_supported_mfma(d), TG_ENOSUP, "tg_conv2d_bwd_data_unpool: not built for this layer");
-  TG_CHECK(!mask || tg_conv2d_bwd_data_mask_fusable_mfma(d), TG_ENOSUP, "tg_conv2d_bwd_data_unpool: mask not fusable here");
-  return tg_conv_tile_run(d->n, d->hout, d->wout, d->cout, d->cin, d->kh, d->kh - 1 - d->pad_t, 0, mask ? d->lrelu_alpha : 1.f,
-                          nullptr, wp, nullptr, gx, s, mask, nullptr, 0, nullptr, nullptr, nullptr, gy_pooled, y_signs,
-                          d->lrelu_alpha, gy_out, y_act, ngroups(d), wset_elems(d, 1));
+  TgConvExtras ex = weight_sets(d, 1);
+  ex.mask = mask;
+  ex.up_src = gy_pooled;
+  ex.up_signs = y_signs;
+  ex.up_z = y_act;
+  ex.up_alpha = d->lrelu_alpha;
+  ex.up_store = gy_out;
+  return tg_conv_tile_run(select_conv(d, TG_GRP_DGRAD).c, 0, mask ? d->lrelu_alpha : 1.f, nullptr, wp, nullptr, gx, s, ex);
 }
 
 static void wgrad_split(const Geom& g, int* n_ci, int* n_co, int* nslices, int* tiles_per_block, int* total_tiles) {
@@ -874,22 +810,10 @@ static void wgrad_split(const Geom& g, int* n_ci, int* n_co, int* nslices, int* 
   *nslices = (*total_tiles + *tiles_per_block - 1) / *tiles_per_block;
 }
 
-bool tg_wgrad_tile_supported(int h, int w, int hout, int wout, int kh, int kw, int pad_t, int pad_l);
-size_t tg_wgrad_tile_workspace(int n, int h, int w, int cin, int cout);
-int tg_wgrad_tile_run(int n, int h, int w, int cin, int cout, const void* x, const void* gy, float* gw, int accumulate,
-                      void* ws, size_t ws_bytes, hipStream_t s, float* gbias = nullptr);
-
-int tg_wgrad_slab_reduce(const float* slab, float* gw, int64_t nw, int nslices, int accumulate, hipStream_t s);
-
+// the filter-gradient tile kernels: the preconditions of the second generation and their own shape test
 static bool use_wgrad_tile(const TgConvDesc* d) {
-  return d->algo != TG_ALGO_MFMA_V1 && d->cin % 8 == 0 && d->cout % 8 == 0 &&
-         tg_wgrad_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l);
+  return second_gen_ok(d) && tg_wgrad_tile_supported(d->hin, d->win, d->hout, d->wout, d->kh, d->kw, d->pad_t, d->pad_l);
 }
-
-size_t tg_wgrad_tile_workspace2(int na, int nb, int h, int w, int cin, int cout);
-int tg_wgrad_tile_run2(int na, int nb, int h, int w, int cin, int cout, const void* xa, const void* gya, const void* xb,
-                       const void* gyb, float* gw, int accumulate, void* ws, size_t ws_bytes, hipStream_t s,
-                       float* gbias = nullptr, int bias_segs = 3);
 
 // two batches (na, nb images) of one layer: supported when the tile kernel takes the layer
 bool tg_conv2d_bwd_weight2_supported_mfma(const TgConvDesc* d) { return is16(d) && use_wgrad_tile(d); }
@@ -915,9 +839,7 @@ size_t tg_conv2d_bwd_weight_workspace_mfma(const TgConvDesc* d0) {
   const TgConvDesc* d = as_dense(d0, &dd) ? &dd : d0;
   if (use_wgrad_tile(d)) return tg_wgrad_tile_workspace(d->n, d->hin, d->win, d->cin, d->cout);
   Geom g;
-  if (fill_geom("tg_conv2d_bwd_weight", d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->kw, d->pad_t,
-                d->pad_l, &g))
-    return 0;
+  if (fill_geom("tg_conv2d_bwd_weight", select_conv(d0, TG_GRP_FWD).c, &g)) return 0;
   int n_ci, n_co, nslices, tpb, total;
   wgrad_split(g, &n_ci, &n_co, &nslices, &tpb, &total);
   return (size_t)nslices * d->kh * d->kw * d->cin * d->cout * sizeof(float);
@@ -932,8 +854,7 @@ int tg_conv2d_bwd_weight_mfma(const TgConvDesc* d0, const void* x, const void* g
   if (use_wgrad_tile(d))
     return tg_wgrad_tile_run(d->n, d->hin, d->win, d->cin, d->cout, x, gy, gw, accumulate, ws, ws_bytes, s, gbias);
   Geom g;
-  int rc = fill_geom("tg_conv2d_bwd_weight", d->n, d->hin, d->win, d->cin, d->hout, d->wout, d->cout, d->kh, d->kw,
-                     d->pad_t, d->pad_l, &g);
+  int rc = fill_geom("tg_conv2d_bwd_weight", select_conv(d0, TG_GRP_FWD).c, &g);
   if (rc) return rc;
   int n_ci, n_co, nslices, tpb, total;
   wgrad_split(g, &n_ci, &n_co, &nslices, &tpb, &total);

@@ -14,7 +14,7 @@
 //
 // Reference call sites replaced: the 4x4 / 8x8 convs of nets/pggan.py:148-166,289-315,318-335,450-476
 // (tf.contrib.layers.conv2d, nets/pggan_utils.py:316-320) and their Conv2DBackpropInput gradients.
-#include "tg_common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -245,9 +245,13 @@ bool tg_conv_small_stats_supported(int n, int hin, int win, int hout, int wout, 
          tg_conv_small_supported(n, hout, wout, k, k);
 }
 
-int tg_conv_small_run(int n, int hin, int win, int cin, int hout, int wout, int cout, int k, int pad_t, int pad_l,
-                      int epilogue, float alpha, const void* x, const void* wp, const float* bias, void* y,
-                      hipStream_t s, float* stats, const void* mask, int groups, size_t wset_elems) {
+int tg_conv_small_run(const TgConvShape& c, int epilogue, float alpha, const void* x, const void* wp, const float* bias, void* y,
+                      hipStream_t s, const TgConvExtras& ex) {
+  const int n = c.n, hin = c.hin, win = c.win, cin = c.cin, hout = c.hout, wout = c.wout, cout = c.cout, k = c.kh;
+  const int pad_t = c.pad_t, pad_l = c.pad_l, groups = ex.groups;
+  float* const stats = ex.stats;
+  const void* const mask = ex.mask;
+  const size_t wset_elems = ex.wset_elems;
   SmallGeom g;
   TG_CHECK(groups <= 1 || !stats, TG_ENOSUP, "conv_small: no statistics epilogue with weight-set groups");
   g.stats = stats;

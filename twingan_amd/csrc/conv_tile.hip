@@ -19,7 +19,7 @@
 //
 // Reference call sites replaced: tf.contrib.layers.conv2d at nets/pggan_utils.py:316-320 (every
 // E/G/D conv of nets/pggan.py at 16x16 and above) and its Conv2DBackpropInput gradient.
-#include "tg_common.h"
+#include "conv_internal.h"
 #include <cstdlib>
 
 namespace {
@@ -1756,23 +1756,37 @@ int dispatch_tile_upbwd(const TileGeom& g, const bf16* gy, const bf16* wp, hipSt
   return launch_tile<3, 16, 32, 1>(g, gy, wp, nullptr, nullptr, s);
 }
 
+// The block shape dispatch_tile gives a geometry (n, h, w, cout, cin_pad), and the tile count its other rules read.
+struct TilePlan {
+  bool wide;       // 64- instead of 32-channel output blocks
+  int tiles1;      // workgroups of one-sub-tile blocks
+  bool mt2;        // two sub-tiles per wave (256-pixel workgroup tile)
+};
+static TilePlan tile_plan(const TileGeom& g) {
+  TilePlan p;
+  // 64-channel blocks halve the pixel staging per output, but a grid under ~4 workgroups per CU wants 32-channel
+  // blocks (kbench 16x16x256 n16: 15.7 -> 10.6 us; 32x32x128 n48: 21.9 -> 20.2 us; above 1024 blocks 64 wins)
+  p.wide = g.cout > 32 && (g.w / 16) * (g.h / 8) * g.n * ((g.cout + 63) / 64) >= 1024;
+  p.tiles1 = (g.w / 16) * (g.h / 8) * g.n * ((g.cout + (p.wide ? 63 : 31)) / (p.wide ? 64 : 32));
+  // two sub-tiles per wave halve the weight staging per pixel; use them when that still leaves >= 2 workgroups per CU
+  // and the map is tall enough
+  p.mt2 = (g.h % 16 == 0) && p.tiles1 >= 2 * 2 * 256 && g.cin_pad >= 64;
+  return p;
+}
+
 // does dispatch_tile send this geometry to a kernel whose workgroups hold ONE weight slice over several tiles / images
-// (conv_tile_wres, conv_thin16)?  Those do not select a weight set per image.
+// (conv_tile_wres, conv_thin16)?  Those do not select a weight set per image.  Conservative: true for every geometry past
+// the tile count with one 16- / 32-channel chunk, also where dispatch_tile stays on the plain kernel (the unpooling input
+// with 16-channel chunks).
 static bool tile_leaves_plain_kernel(const TileGeom& g) {
-  const bool wide = g.cout > 32 && (g.w / 16) * (g.h / 8) * g.n * ((g.cout + 63) / 64) >= 1024;
-  const int tiles1 = (g.w / 16) * (g.h / 8) * g.n * ((g.cout + (wide ? 63 : 31)) / (wide ? 64 : 32));
-  return tiles1 >= 2048 && (g.cin_pad == 16 || g.cin_pad == 32);
+  return tile_plan(g).tiles1 >= 2048 && (g.cin_pad == 16 || g.cin_pad == 32);
 }
 
 template <int KH>
 int dispatch_tile(const TileGeom& g, const bf16* x, const bf16* wp, const float* bias, bf16* y, hipStream_t s) {
-  // 64-channel blocks halve the pixel staging per output, but a grid under ~4 workgroups per CU wants 32-channel
-  // blocks (kbench 16x16x256 n16: 15.7 -> 10.6 us; 32x32x128 n48: 21.9 -> 20.2 us; above 1024 blocks 64 wins)
-  const bool wide = g.cout > 32 && (g.w / 16) * (g.h / 8) * g.n * ((g.cout + 63) / 64) >= 1024;
-  const int tiles1 = (g.w / 16) * (g.h / 8) * g.n * ((g.cout + (wide ? 63 : 31)) / (wide ? 64 : 32));
-  // two sub-tiles per wave (256-pixel workgroup tile) halve the weight staging per pixel; use them
-  // when that still leaves >= 2 workgroups per CU and the map is tall enough
-  const bool mt2 = (g.h % 16 == 0) && tiles1 >= 2 * 2 * 256 && g.cin_pad >= 64;
+  const TilePlan p = tile_plan(g);
+  const bool wide = p.wide, mt2 = p.mt2;
+  const int tiles1 = p.tiles1;
   // thin layers with many tiles: weights resident in LDS, several tiles per workgroup
   // weight-set groups: the plain tile kernel only (tg_conv_tile_grouped_native answers for this dispatch)
   TG_CHECK(!g.npg || !tile_leaves_plain_kernel(g), TG_ENOSUP, "conv_tile: weight-set groups on a weight-resident / thin-output dispatch");
@@ -1801,45 +1815,48 @@ bool tg_conv_tile_supported(int h, int w, int hout, int wout, int kh, int kw, in
   return (h % 8 == 0) && (w % 16 == 0);
 }
 
-// Does a grouped call of this shape (n = the whole batch) stay on conv_tile_kernel, which picks the weight set per image?
-bool tg_conv_tile_grouped_native(int n, int h, int w, int cin, int cout) {
-  TileGeom g;
+// The geometry of an n x h x w conv with every optional operand off; callers set what their call carries.
+static TileGeom tile_geom(int n, int h, int w, int cin, int cout, int cin_pad, int pad) {
+  TileGeom g = {};
   g.n = n; g.h = h; g.w = w; g.cin = cin; g.cout = cout;
-  g.cin_pad = (cin + 15) / 16 * 16;
-  return !tile_leaves_plain_kernel(g);
+  g.cin_pad = cin_pad;
+  g.pad = pad;
+  g.f16 = tg_elem_f16();      // the descriptor's dtype, noted by the C-ABI entry point
+  return g;
+}
+static TileGeom tile_geom(const TgConvShape& c) { return tile_geom(c.n, c.hin, c.win, c.cin, c.cout, (c.cin + 15) / 16 * 16, c.pad_t); }
+
+// Does a grouped call of this shape (n = the whole batch) stay on conv_tile_kernel, which picks the weight set per image?
+bool tg_conv_tile_grouped_native(const TgConvShape& c) { return !tile_leaves_plain_kernel(tile_geom(c)); }
+
+// chunks per image the statistics variant of this shape's dispatch writes (nothing is launched), 0: it has none
+int tg_conv_tile_stats_chunks(const TgConvShape& c) {
+  TileGeom g = tile_geom(c);
+  int chunks = 0;
+  g.chunks_query = &chunks;
+  const int rc = c.kh == 1 ? dispatch_tile<1>(g, nullptr, nullptr, nullptr, nullptr, nullptr)
+                           : dispatch_tile<3>(g, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return rc == TG_OK ? chunks : 0;
 }
 
-int tg_conv_tile_run(int n, int h, int w, int cin, int cout, int k, int pad, int epilogue, float alpha, const void* x,
-                     const void* wp, const float* bias, void* y, hipStream_t s, const void* mask, float* stats,
-                     int stat_chunks, int* chunks_query, void* ypool, void* ymask, const void* up_src, const void* up_signs,
-                     float up_alpha, void* up_store, const void* up_z, int groups, size_t wset_elems) {
-  TileGeom g;
-  g.n = n; g.h = h; g.w = w; g.cin = cin; g.cout = cout;
-  g.cin_pad = (cin + 15) / 16 * 16;
-  g.pad = pad;
-  g.npg = groups > 1 ? n / groups : 0;
-  g.wgs = groups > 1 ? (unsigned)wset_elems : 0u;
-  g.tiles_x = g.tiles_y = g.nblk = 0;
+int tg_conv_tile_run(const TgConvShape& c, int epilogue, float alpha, const void* x, const void* wp, const float* bias, void* y,
+                     hipStream_t s, const TgConvExtras& ex) {
+  TileGeom g = tile_geom(c);
+  g.npg = ex.groups > 1 ? c.n / ex.groups : 0;
+  g.wgs = ex.groups > 1 ? (unsigned)ex.wset_elems : 0u;
   g.epilogue = epilogue;
   g.alpha = alpha;
-  g.x1 = nullptr;
-  g.c0 = g.gsz = 0;
-  g.perm = 0;
-  g.mask = (const bf16*)mask;
-  g.stats = stats;
-  g.stat_chunks = stat_chunks;
-  g.chunks_query = chunks_query;
-  g.ypool = (bf16*)ypool;
-  g.ymask = (unsigned char*)ymask;
-  g.up_out = g.skip_out = nullptr;
-  g.n1 = 0;
-  g.up_src = (const bf16*)up_src;
-  g.up_signs = (const unsigned char*)up_signs;
-  g.up_z = (const bf16*)up_z;
-  g.up_alpha = up_alpha;
-  g.up_store = (bf16*)up_store;
-  g.f16 = tg_elem_f16();      // the descriptor's dtype, noted by the C-ABI entry point
-  if (k == 1) return dispatch_tile<1>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
+  g.mask = (const bf16*)ex.mask;
+  g.stats = ex.stats;
+  g.stat_chunks = ex.stat_chunks;
+  g.ypool = (bf16*)ex.ypool;
+  g.ymask = (unsigned char*)ex.ymask;
+  g.up_src = (const bf16*)ex.up_src;
+  g.up_signs = (const unsigned char*)ex.up_signs;
+  g.up_z = (const bf16*)ex.up_z;
+  g.up_alpha = ex.up_alpha;
+  g.up_store = (bf16*)ex.up_store;
+  if (c.kh == 1) return dispatch_tile<1>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
   return dispatch_tile<3>(g, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, s);
 }
 
@@ -1851,34 +1868,14 @@ bool tg_conv_tile_upcat_supported(int h, int w, int c0, int c1, int cout) {
 int tg_conv_tile_upcat_run(int n, int h, int w, int c0, int c1, int cout, int gsz, unsigned perm, const void* x0,
                            const void* x1, const void* wp, void* y, hipStream_t s, float* stats, int stat_chunks,
                            int* chunks_query) {      // element format: tg_elem_f16(), set by the C-ABI entry point
-  TileGeom g;
-  g.n = n; g.h = h; g.w = w; g.cin = c0 + c1; g.cout = cout;
-  g.cin_pad = g.cin;
-  g.pad = 1;
-  g.npg = 0;
-  g.wgs = 0;
-  g.tiles_x = g.tiles_y = g.nblk = 0;
-  g.tiles_per_wg = 0;
-  g.epilogue = 0;
-  g.alpha = 0.f;
+  TileGeom g = tile_geom(n, h, w, c0 + c1, cout, c0 + c1, 1);
   g.x1 = (const bf16*)x1;
   g.c0 = c0;
   g.gsz = gsz;
   g.perm = perm;
-  g.mask = nullptr;
   g.stats = stats;
   g.stat_chunks = stat_chunks;
   g.chunks_query = chunks_query;
-  g.ypool = nullptr;
-  g.ymask = nullptr;
-  g.up_out = g.skip_out = nullptr;
-  g.n1 = 0;
-  g.up_src = nullptr;
-  g.up_signs = nullptr;
-  g.up_z = nullptr;
-  g.up_alpha = 0.f;
-  g.up_store = nullptr;
-  g.f16 = tg_elem_f16();
   return dispatch_tile_upcat(g, (const bf16*)x0, (const bf16*)wp, nullptr, (bf16*)y, s);
 }
 
@@ -1886,34 +1883,13 @@ int tg_conv_tile_upcat_run(int n, int h, int w, int c0, int c1, int cout, int gs
 // the input gradient of tg_conv_tile_upcat_run's conv.  wp: the backward-data pack (mode 1) of the conv's kernel.
 int tg_conv_tile_upcat_bwd_run(int n, int h, int w, int c0, int c1, int cout, int gsz, unsigned perm, int n1, const void* gy,
                                const void* wp, void* g0, void* g1, hipStream_t s) {
-  TileGeom g;
-  g.n = n; g.h = h; g.w = w; g.cin = cout; g.cout = c0 + c1;      // a conv over gy: cout -> c0 + c1 channels
-  g.cin_pad = (cout + 15) / 16 * 16;
-  g.pad = 1;
-  g.npg = 0;
-  g.wgs = 0;
-  g.tiles_x = g.tiles_y = g.nblk = 0;
-  g.tiles_per_wg = 0;
-  g.epilogue = 0;
+  TileGeom g = tile_geom(n, h, w, cout, c0 + c1, (cout + 15) / 16 * 16, 1);      // a conv over gy: cout -> c0 + c1 channels
   g.alpha = 1.f;
-  g.x1 = nullptr;
   g.c0 = c0;
   g.gsz = gsz;
   g.perm = perm;
-  g.mask = nullptr;
-  g.stats = nullptr;
-  g.stat_chunks = 0;
-  g.chunks_query = nullptr;
-  g.ypool = nullptr;
-  g.ymask = nullptr;
   g.up_out = (bf16*)g0;
   g.skip_out = (bf16*)g1;
   g.n1 = n1;
-  g.up_src = nullptr;
-  g.up_signs = nullptr;
-  g.up_z = nullptr;
-  g.up_alpha = 0.f;
-  g.up_store = nullptr;
-  g.f16 = tg_elem_f16();
   return dispatch_tile_upbwd(g, (const bf16*)gy, (const bf16*)wp, s);
 }

@@ -23,7 +23,7 @@
 //
 // Reference call site replaced: the Conv2DBackpropFilter gradient of tf.contrib.layers.conv2d
 // (nets/pggan_utils.py:316-320).
-#include "tg_common.h"
+#include "conv_internal.h"
 
 // launches conv_wgrad_tile_kernel<TW, BIAS, F16, NW> in the element format of the current call (tg_elem_f16)
 #define TG_WG_LAUNCH(TW_, BIAS_, NW_, ...)                                                        \
@@ -1092,8 +1092,6 @@ void wg_split(int n, int h, int w, int cin, int cout, WgGeom* g, int* nslices, i
 }
 
 }  // namespace
-
-int tg_wgrad_slab_reduce(const float* slab, float* gw, int64_t nw, int nslices, int accumulate, hipStream_t s);
 
 namespace {
 bool wg_thin(int h, int w, int cin, int cout) {
