@@ -476,6 +476,10 @@ int tg_gp_penalty(const float* sumsq, float* loss, float* coef, int batch, float
  * lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the caller.  Flat fp32 buffers of `numel`
  * elements; grad_scale multiplies g first (1/loss_scale).  theta_bf16 (may be NULL) receives the
  * rounded copy of the updated parameters (cast-on-read shadow, deployment/model_deploy.py:146-183).
+ * The shadow is always bfloat16 (round to nearest even), whatever the storage type of the step -- the
+ * fp16 path has no fp16 form of it -- and nothing in the package consumes it: the trainer passes NULL
+ * (twingan.py Trainer._adam) and refreshes its 16-bit weight packs from the fp32 parameters
+ * (ops.PackCache).  The tests pin what it holds.
  * lr_t_dev (may be NULL): device fp32 [1] that overrides lr_t -- lets a captured hipGraph replay the
  * step with a fresh bias-corrected rate.  tg_adam_tick advances the shared optimiser step counter on
  * the device (one counter for G and D applies, image_generation.py:554-561) and writes that rate.

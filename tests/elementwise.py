@@ -27,6 +27,17 @@ from the output under test, and is derived, not tuned:
                     pairwise (error ~ log N), the kernels sum chunks linearly and meet in atomics (up to ~ sqrt N of that).
   exact ops         (upsample, concat, cast, sign bytes) stay array_equal in the tests.
 
+Attention, softmax, the batched GEMM, the scalar reductions and Adam (their derivations sit in the docstrings of the
+functions below; every count names the kernel operation it stands for):
+  attention_fwd_bound / attention_lse_bound   flash forward: P rounded to 16 bit (u), the exponent's fp32 error eps, the fp32
+                    accumulation over len keys, the fp16 subnormal pack (2^-25 per key)
+  attention_bwd_bounds   dQ, dK, dV of the flash backward: u_out |ref| + R u mag + A 2^-24 mag + 2^-25 S, with the forward's own
+                    bounds of lse and O carried in (they are this kernel's inputs)
+  gemm_bound        conv_bound with K = k + 2 (the alpha multiply, the accumulate add) and the rounding of a stored 16-bit C
+  softmax kernels   e32_bound, each kernel on the operands it reads (the stored p is an operand of the two backwards)
+  reduction_bound   L 2^-24 sum|terms|, L the longest chain of additions the launch geometry allows
+  adam_step_bounds  one step in float64 from the fp32 state, every fp32 operation of the kernel counted once
+
 LeakyReLU masks taken from a COMPUTED sign: an element may match `alt_ref` (the reference evaluated with the other slope)
 only where `alt_where` holds (the float64 pre-activation is smaller than its own bound), and at most `alt_cap` of the
 tensor's elements may take that route.
@@ -304,3 +315,338 @@ def assert_pair_device(a, b, mag, K, what, roundings=2, chunk=8, extra=None):
     box, wi, ga, gb, bd, rw = rep
     raise AssertionError(_describe(box, tuple(a.shape), wi, ga, gb, bd, nbad, a.numel(), what + ' (first failing chunk)', 0, rw))
   return worst
+
+
+# ------------------------------------------------------------------------------------------------ batched GEMM
+def gemm_bound(ref, mag, k, dtype, c0=None, c_f32=False):
+  """tg_batched_gemm: C = alpha op(A) op(B) (+ C0).  conv_bound with K = k products accumulated in fp32 (MFMA, or fmaf in
+  the fp32 kernel), + 1 for `g.alpha * acc`, + 1 for the `*c + v` of accumulate; mag = |alpha| |a| |b| (+ |C0|).
+  `ref` includes C0.  A 16-bit C0 is read back exactly; the sum is rounded once to C's type (fp32 when c_f32)."""
+  out = 'f32' if c_f32 else dtype
+  K = k + 1 + (0 if c0 is None else 1)
+  m = np.abs(mag) + (0.0 if c0 is None else np.abs(c0))
+  return conv_bound(ref, m, K, out)
+
+
+# ------------------------------------------------------------------------------------------------ row softmax
+def softmax_kernels_reference(s, p, dp, v, dt):
+  """The three softmax kernels' literal formulas in numpy dtype `dt` (float64: the reference; float32: the restatement for
+  E32), each on the operands the kernel itself READS -- the backward kernels take the STORED p, so p is an operand here,
+  already rounded to the storage type, and nothing a 16-bit store did to it is left for the bound to cover:
+      fwd      softmax(s)                                tg_softmax_rows_fwd
+      bwd      p (dp - t),            t = sum dp p      tg_softmax_rows_bwd
+      bwd_bwd  v (dp - t) - dp u,     u = sum v p       tg_softmax_rows_bwd_bwd
+  -> (fwd, bwd, bwd_bwd)."""
+  s, p, dp, v = (np.asarray(x, dt) for x in (s, p, dp, v))
+  e = np.exp(s - s.max(-1, keepdims=True))
+  fwd = e / e.sum(-1, keepdims=True, dtype=dt)
+  t = (dp * p).sum(-1, keepdims=True, dtype=dt)
+  u = (v * p).sum(-1, keepdims=True, dtype=dt)
+  return fwd, p * (dp - t), v * (dp - t) - dp * u
+
+
+# ------------------------------------------------------------------------------------------------ scalar reductions
+def reduction_chain(numel, dtype, cap, vec=True, block=256, one_block=None):
+  """The longest chain of fp32 additions a term of sum_kernel / sample_sumsq_kernel can pass through, from the launch
+  geometry the entry points define (csrc/reduce.hip): blocks = min(cap, ceil((numel / V + 1) / 256)) workgroups of 256
+  threads (ONE for fp32 and in deterministic mode: the exact-parity path -- one_block; tg_sum_ordered keeps its grid for every
+  type: one_block=False), V = 16 bytes of the type; per thread ceil(nvec / threads) trips of V
+  additions plus ceil(tail / threads) scalar ones (vec False: every element is tail); 6 butterfly levels of the wave sum and
+  the 4 wave partials of block_sum added in order; one atomic (or ordered) addition per workgroup; one multiply by the
+  scale.  -> (L, blocks)."""
+  V = 16 // {'float32': 4}.get(_name(dtype), 2)
+  if one_block is None:
+    one_block = _name(dtype) == 'float32'
+  blocks = 1 if one_block else max(1, min(cap, (numel // V + 1 + block - 1) // block))
+  threads = blocks * block
+  nvec = numel // V if vec else 0
+  trips = -(-nvec // threads)
+  tail = -(-(numel - nvec * V) // threads)
+  return trips * V + tail + 6 + block // 64 + blocks + 1, blocks
+
+
+def reduction_bound(terms_abs_sum, L, scale=1.0, term_ops=0):
+  """|err| <= (L + term_ops) 2^-24 |scale| sum|terms| + 2^-126; term_ops: the fp32 operations that FORM a term (1 for |a - b| and
+  for the fmaf of x^2, 0 for a plain sum)."""
+  return (L + term_ops) * U32 * abs(scale) * float(terms_abs_sum) + TINY
+
+
+def gp_penalty_bounds(ss, L, lam):
+  """tg_sample_sumsq + tg_gp_penalty from the float64 per-sample sums of squares ss[b] (L: reduction_chain of one sample):
+      ss^      (L + 1) 2^-24 ss                      the fmaf chain
+      slope    sqrtf: d ss / (2 slope) + 2 2^-24 slope (one unit in the last place); a zero sample has slope = 0 exactly
+      d        slope - 1: one rounding
+      d^2      2 |d| dd + 2^-24 d^2;  summed over the batch by one workgroup: (ceil(batch / 256) + 12) 2^-24 sum d^2;
+               lambda * tot / batch: two operations
+      coef     lambda 2 d / (slope batch): three multiplies and a division (2): 5 2^-24 |coef| + the errors of d and slope;
+               slope = 0: coef = 0, this project's choice (the literal formula divides 0 by 0)
+  -> (loss, coef) references and (b_loss, b_coef)."""
+  ss = np.asarray(ss, np.float64)
+  b = ss.size
+  slope = np.sqrt(ss)
+  dss = (L + 1) * U32 * ss
+  pos = slope > 0
+  sl = np.where(pos, slope, 1.0)
+  dslope = np.where(pos, dss / (2 * sl) + 2 * U32 * slope, 0.0)
+  d = slope - 1.0
+  dd = dslope + U32 * np.abs(d)
+  loss = lam * (d * d).sum() / b
+  b_loss = lam / b * ((2 * np.abs(d) * dd + U32 * d * d).sum() + (-(-b // 256) + 12) * U32 * (d * d).sum()) + TINY
+  coef = np.where(pos, lam * 2.0 * d / (sl * b), 0.0)
+  b_coef = np.where(pos, lam * 2.0 / b * (dd / sl + np.abs(d) * dslope / sl ** 2) + 5 * U32 * np.abs(coef), 0.0) + TINY
+  return (loss, coef), (b_loss, b_coef)
+
+
+# ------------------------------------------------------------------------------------------------ Adam
+def adam_step_bounds(th, g, m, v, lr_t, b1, b2, eps, gscale):
+  """One step of adam_kernel (csrc/reduce.hip) in float64 from the fp32 state it READS (the previous step's stored theta, m,
+  v: inputs of this launch, not its output), with the fp32 scalars it is given, and the error of every fp32 operation on
+  the way.  Each operation counts 2^-24 of its result (the compiler may contract a multiply into the following add, which
+  only removes a rounding); sqrtf and the division are not required to be correctly rounded: one unit in the last place
+  (2 x 2^-24) each; every operation may also flush a subnormal result: + 2^-126.
+      gi = g gscale                                1 rounding
+      mi = b1 m + (1 - b1) gi                      (1 - b1), two products, the sum, gi's own: 4 u32 (|b1 m| + |(1 - b1) gi|)
+      vi = b2 v + (1 - b2) gi gi                   gi twice, (1 - b2), two products (three multiplies), the sum: 7 u32 vi
+      r  = sqrtf(vi)                               |sqrt(a) - sqrt(b)| <= min(|a - b| / sqrt(b), sqrt|a - b|), + 2 u32 r
+      d  = r + eps                                 1 rounding
+      t  = th - lr_t mi / d                        one multiply, the division (2), the subtraction
+  -> (theta, m, v) references and (b_theta, b_m, b_v) bounds, numpy float64 or torch float64 alike (operator syntax only)."""
+  f32 = np.float32
+  b1, b2, eps, gscale, lr_t = (float(f32(x)) for x in (b1, b2, eps, gscale, lr_t))
+  c1, c2 = float(f32(1.0) - f32(b1)), float(f32(1.0) - f32(b2))
+  sqrt = (lambda a: a.sqrt()) if hasattr(th, 'sqrt') else np.sqrt
+  minimum = (lambda a, b: a.minimum(b)) if hasattr(th, 'minimum') else np.minimum
+  gi = g * gscale
+  mi = b1 * m + c1 * gi
+  vi = b2 * v + c2 * gi * gi
+  bm = 4.0 * U32 * (abs(b1 * m) + abs(c1 * gi)) + 2 * TINY
+  bv = 7.0 * U32 * vi + 3 * TINY
+  r = sqrt(vi)
+  br = minimum(bv / (r + 1e-300), sqrt(bv)) + 2.0 * U32 * r + TINY
+  d = r + eps
+  bd = br + U32 * d + TINY
+  upd = lr_t * mi / d
+  # d is at least eps - bd away from zero; relative error of the quotient to first order, the denominator's taken at d - bd
+  bupd = lr_t * bm / (d - bd) + abs(upd) * (bd / (d - bd) + 3.0 * U32) + 2 * TINY
+  t = th - upd
+  bt = U32 * abs(t) + (1.0 + U32) * bupd + TINY
+  return (t, mi, vi), (bt, bm, bv)
+
+
+# ------------------------------------------------------------------------------------------------ flash attention
+K_STALE = 6.0      # csrc/flash.hip kStaleMax: the running maximum may lag the true one by this much (natural-log units)
+
+
+def attention_terms(q, k, v):
+  """float64 softmax attention of [n, len, d] operands and the magnitudes the bounds need -> dict(s, smax, p, lse, o, mag
+  (= p |v|), A (= max_j |q_i| . |k_j|, per query), vsum (= sum_j |v_j|, per feature))."""
+  s = np.einsum('nid,njd->nij', q, k)
+  smax = s.max(-1)
+  e = np.exp(s - smax[..., None])
+  l = e.sum(-1)
+  p = e / l[..., None]
+  return dict(s=s, smax=smax, p=p, lse=smax + np.log(l), o=np.einsum('nij,njd->nid', p, v),
+              mag=np.einsum('nij,njd->nid', p, np.abs(v)), A=np.einsum('nid,njd->nij', np.abs(q), np.abs(k)).max(-1),
+              vsum=np.abs(v).sum(1))
+
+
+def attention_eps(A, dqk, ln):
+  """The relative error of one unnormalised fp32 probability exp(s_ij - m) of flash_fwd_kernel before it is packed, in units
+  of 2^-24, counted from the kernel's own operations (A = max_j |q_i| . |k_j| bounds |s| and |m|):
+      d_qk A      the score: d_qk exact products accumulated in fp32 by the MFMA (the zero padding to 16 adds nothing)
+      2 A         fma(s, log2e, -m2): one rounding of a value of magnitude |s - m| log2e <= 2 A log2e, times ln 2
+      2 A         log2e as an fp32 constant (relative 2^-24) scales s - m, |s - m| <= 2 A
+      A           m2 = m_new * log2e, rounded once per rescale; it holds for the whole span of blocks that use it
+      2           v_exp_f32: one unit in the last place
+      4 A         the rescales: (m_run - m_new) and its product with log2e are rounded, each relative to |m_run - m_new|;
+                  the increments of one row are all positive and sum to at most the range of its scores, 2 A
+      3 len / 32  per rescale (at most one per 32-key block) one v_exp_f32 (2) and one multiply acc *= corr (1)
+  -> ((d_qk + 9) A + 2 + 3 len / 32) 2^-24."""
+  return ((dqk + 9.0) * A + 2.0 + 3.0 * (ln // 32)) * U32
+
+
+def _attention_rho(eps, ln, dtype):
+  """Relative error of the row sum l: every summand rounded to 16 bit (u) after its exponent error (eps), summed in fp32
+  over len keys (len 2^-24), and -- l >= 1 - eps, the key that set the maximum has p = 1 -- the absolute 2^-25 of an fp16
+  subnormal per key."""
+  u = unit_roundoff(dtype)
+  r = u + eps + ln * U32 + ln * tiny(dtype)
+  assert np.all(r < 0.5), 'the exponent error alone exceeds one half: the bound says nothing at this score scale'
+  return r
+
+
+def attention_fwd_bound(t, dqk, dtype):
+  """O = N / l, N = sum_j p_j v_j, both from the SAME packed probabilities.  |N^ - N| <= (u + eps + len 2^-24) mag l +
+  2^-25 sum_j |v_j| (fp16 subnormal pack; l >= 1), |l^ - l| <= rho l; 1 / l and acc * inv are two fp32 operations; one storage
+  rounding:
+      u |ref| + (1 + u) [((u + eps + len 2^-24) (mag + |ref|) + tiny16 (sum_j |v_j| + len |ref|)) / (1 - rho) + 2 2^-24 |ref|] + tiny
+  t = attention_terms(q, k, v)."""
+  u = unit_roundoff(dtype)
+  ln = t['s'].shape[-1]
+  eps = attention_eps(t['A'], dqk, ln)[..., None]
+  rho = _attention_rho(eps, ln, dtype)
+  ref = np.abs(t['o'])
+  num = (u + eps + ln * U32) * (t['mag'] + ref) + tiny(dtype) * (t['vsum'][:, None, :] + ln * ref)
+  return u * ref + (1.0 + u) * (num / (1.0 - rho) + 2.0 * U32 * ref) + tiny(dtype)
+
+
+def attention_lse_bound(t, dqk, dtype):
+  """lse = m_run + __logf(l): l carries rho (relative), so log l carries -log(1 - rho); __logf is v_log_f32 (one unit in
+  the last place) times ln 2, rounded: 3 2^-24 |log l| with |log l| <= lse - max_j s + kStaleMax + rho (the stale maximum);
+  the final addition is one rounding of |lse|."""
+  ln = t['s'].shape[-1]
+  rho = _attention_rho(attention_eps(t['A'], dqk, ln), ln, dtype)
+  logl = np.abs(t['lse'] - t['smax']) + K_STALE + rho
+  return -np.log1p(-rho) + 3.0 * U32 * logl + U32 * np.abs(t['lse']) + TINY
+
+
+def attention_grads_reference(q, k, v, go, t=None):
+  """dQ, dK, dV of softmax attention in float64 and the magnitude terms of their bounds -> dict."""
+  t = attention_terms(q, k, v) if t is None else t
+  p = t['p']
+  gp = np.einsum('nid,njd->nij', go, v)
+  D = (gp * p).sum(-1, keepdims=True)
+  ds = p * (gp - D)
+  gpa = np.einsum('nid,njd->nij', np.abs(go), np.abs(v))
+  Da = (p * gpa).sum(-1, keepdims=True)
+  dsa = p * (gpa + Da)
+  return dict(dq=np.einsum('nij,njd->nid', ds, k), dk=np.einsum('nij,nid->njd', ds, q), dv=np.einsum('nij,nid->njd', p, go),
+              gpa=gpa, Da=Da, dsa=dsa, mag_dq=np.einsum('nij,njd->nid', dsa, np.abs(k)),
+              mag_dk=np.einsum('nij,nid->njd', dsa, np.abs(q)), mag_dv=np.einsum('nij,nid->njd', p, np.abs(go)))
+
+
+def attention_bwd_bounds(q, k, v, go, t, r, dqk, dtype):
+  """flash_bwd_q_kernel / flash_bwd_kv_kernel, each bound of the form u_out |ref| + R u mag + A 2^-24 mag + T tiny16 S, every
+  term named.  Per query i the recomputed probability p^ = exp2(fma(s, log2e, -lse2)) carries, relative,
+      epb_i = ((d_qk + 2) A_i + 3 |lse_i| + 2) 2^-24 + Blse_i
+  (the score's accumulation d_qk A; the fma's rounding and the fp32 log2e on |s - lse| <= A + |lse|: 2 (A + |lse|); lse2 = lse
+  log2e rounded: |lse|; v_exp_f32: 2) -- and Blse_i, the forward's own lse bound: the lse this kernel READS is the forward
+  kernel's output (R: "lse carrying the forward's error", about one u).
+      dV_j = sum_i pack(p^_ij) dO_i       R u: P packed (1) + Blse;  A = len;  T S = 2^-25 sum_i |dO_i|
+      D_i  = <dO_i, O_i> from the STORED O: |D^ - D| <= sum_d |dO_id| BO_id + d_v 2^-24 sum_d |dO_id| |O_id| =: dD_i with BO the
+             forward's own element bound (R: "O stored in 16 bit")
+      ds^_ij = pack(p^ (dp - D^)): dp = dO V^T over d_v products (d_v 2^-24 gpa), the subtraction and the multiply (2 2^-24
+             of gpa + Da), the pack (u, and 2^-25 absolute in fp16):
+             |ds^ - ds| <= (u + epb_i + (d_v + 3) 2^-24) dsa_ij + p_ij dD_i + tiny16
+      dQ_i = sum_j ds^_ij k_j             A = len;  T S = 2^-25 sum_j |k_j|
+      dK_j = sum_i ds^_ij q_i             A = len;  T S = 2^-25 sum_i |q_i|
+  t = attention_terms, r = attention_grads_reference -> (b_dq, b_dk, b_dv)."""
+  u = unit_roundoff(dtype)
+  t16 = tiny(dtype)
+  n, ln, _ = q.shape
+  dv = v.shape[2]
+  p = t['p']
+  epb = ((dqk + 2.0) * t['A'] + 3.0 * np.abs(t['lse']) + 2.0) * U32 + attention_lse_bound(t, dqk, dtype)      # [n, len]
+  ago, aq, ak = np.abs(go), np.abs(q), np.abs(k)
+  dD = (ago * attention_fwd_bound(t, dqk, dtype)).sum(-1) + dv * U32 * (ago * np.abs(t['o'])).sum(-1)       # [n, len]
+  rel = (u + epb + (dv + 3.0) * U32)[..., None]                                                              # per query
+  eds = rel * r['dsa'] + p * dD[..., None]                                                                   # [n, i, j]
+  b_dq = u * np.abs(r['dq']) + (1 + u) * (np.einsum('nij,njd->nid', eds, ak) + ln * U32 * r['mag_dq']
+                                          + t16 * ak.sum(1)[:, None, :]) + t16
+  b_dk = u * np.abs(r['dk']) + (1 + u) * (np.einsum('nij,nid->njd', eds, aq) + ln * U32 * r['mag_dk']
+                                          + t16 * aq.sum(1)[:, None, :]) + t16
+  epv = (u + epb)[..., None] * p
+  b_dv = u * np.abs(r['dv']) + (1 + u) * (np.einsum('nij,nid->njd', epv, ago) + ln * U32 * r['mag_dv']
+                                          + t16 * ago.sum(1)[:, None, :]) + t16
+  return b_dq, b_dk, b_dv
+
+
+
+def attention_bwd_bwd_bounds(q, k, v, go, aq, ak, av, t, r, dqk, dtype):
+  """flash_bb_stats / flash_bb_q / flash_bb_kv (csrc/flash.hip), the closed form of oracle/np_ops.attention_backward_backward
+  evaluated on the absolute values of its operands with every difference turned into a sum -- the magnitudes -- and the
+  error of every fp32 quantity on the way, to first order, per (query i, key j).  With epb_i and dD_i as in
+  attention_bwd_bounds (the recomputed probability's relative error with the forward's lse bound in it; D from the stored O):
+      gp  = dO V^T      d_v products       |d gp| <= d_v 2^-24 gpa            gpa = |dO| |V|^T
+      w   = aQ K^T + Q aK^T   2 d_qk       |d w|  <= 2 d_qk 2^-24 wa          wa  = |aQ| |K|^T + |Q| |aK|^T
+      y   = dO aV^T     d_v products       |d y|  <= d_v 2^-24 ya             ya  = |dO| |aV|^T
+      E_i = sum_j p w   (fp32 chain)       dE_i = (epb + (2 d_qk + 1 + len) 2^-24) Ea,   Ea = sum_j p wa
+      F_i = J + H - 2 D E,  J = sum p y, H = sum p w gp:
+            dF_i = (epb + (d_v + 1 + len) 2^-24) Ja + (epb + (2 d_qk + d_v + 2 + len) 2^-24) Ha + 2 (dD Ea + Da dE)
+                   + 8 2^-24 Fa,     Ja = sum p ya, Ha = sum p wa gpa, Fa = Ja + Ha + 2 Da Ea
+      the four packed maps (u each, 2^-25 absolute in fp16):
+      pv = p                               (u + epb) p
+      gs = p (gp - D)                      (u + epb + (d_v + 3) 2^-24) dsa + p dD                         dsa = p (gpa + Da)
+      tv = p (w - E)                       (u + epb + (2 d_qk + 3) 2^-24) Ta + p dE                       Ta = p (wa + Ea)
+      uv = p (x - F), x = fma(w, gp - D, y) - E gp:   Xa = ya + wa (gpa + Da) + Ea gpa,
+            dx = (3 d_v + 2 d_qk + 3) 2^-24 Xa + wa dD + gpa dE;   (u + epb + 2 2^-24) Ua + p (dx + dF),   Ua = p (Xa + Fa)
+      adj Q  = gs aK + uv K,  adj dO = pv aV + tv V   (sums over keys),   adj K = gs^T aQ + uv^T Q,  adj V = tv^T dO  (over queries):
+      each the map errors times the other operand's magnitude, + 2 len 2^-24 mag (two MFMA chains of len), + 2^-25 S, + u_out |ref|.
+  The saturated rows (late_spike): D, a fmaf chain over d_v products, and gP, an MFMA sum over the same products, differ by up
+  to d_v 2^-24 gpa each where the exact difference is 0, and the difference meets |k| = 20 in adj Q: the (d_v + 3) 2^-24 dsa |K|
+  term above -- absolute noise of that size next to a true value of 1e-29 is inside the bound, by derivation.
+  -> bounds of (adj q, adj k, adj v, adj dO); `refs` = the float64 adjoints in that order."""
+  u = unit_roundoff(dtype)
+  t16 = tiny(dtype)
+  n, ln, _ = q.shape
+  dv = v.shape[2]
+  p = t['p']
+  A = lambda x: np.abs(x)
+  mm = lambda a, b: np.einsum('nid,njd->nij', a, b)
+  epb = (((dqk + 2.0) * t['A'] + 3.0 * np.abs(t['lse']) + 2.0) * U32 + attention_lse_bound(t, dqk, dtype))[..., None]
+  dD = ((A(go) * attention_fwd_bound(t, dqk, dtype)).sum(-1) + dv * U32 * (A(go) * A(t['o'])).sum(-1))[..., None]
+  gpa, Da, dsa = r['gpa'], r['Da'], r['dsa']
+  wa = mm(A(aq), A(k)) + mm(A(q), A(ak))
+  ya = mm(A(go), A(av))
+  rs = lambda x: x.sum(-1, keepdims=True)
+  Ea, Ja, Ha = rs(p * wa), rs(p * ya), rs(p * wa * gpa)
+  Fa = Ja + Ha + 2 * Da * Ea
+  dE = (epb + (2 * dqk + 1 + ln) * U32) * Ea
+  dF = (epb + (dv + 1 + ln) * U32) * Ja + (epb + (2 * dqk + dv + 2 + ln) * U32) * Ha + 2 * (dD * Ea + Da * dE) + 8 * U32 * Fa
+  Ta = p * (wa + Ea)
+  Xa = ya + wa * (gpa + Da) + Ea * gpa
+  Ua = p * (Xa + Fa)
+  e_pv = (u + epb) * p
+  e_gs = (u + epb + (dv + 3) * U32) * dsa + p * dD
+  e_tv = (u + epb + (2 * dqk + 3) * U32) * Ta + p * dE
+  dx = (3 * dv + 2 * dqk + 3) * U32 * Xa + wa * dD + gpa * dE
+  e_uv = (u + epb + 2 * U32) * Ua + p * (dx + dF)
+  kj = lambda m, x: np.einsum('nij,njd->nid', m, x)      # sum over keys
+  qi = lambda m, x: np.einsum('nij,nid->njd', m, x)      # sum over queries
+  colsum = lambda *xs: sum(A(x).sum(1) for x in xs)[:, None, :]
+
+  def fin(ref, err, mag, S):
+    return u * np.abs(ref) + (1 + u) * (err + 2 * ln * U32 * mag + t16 * S) + t16
+  refs = r['bb']
+  b_q = fin(refs[0], kj(e_gs, A(ak)) + kj(e_uv, A(k)), kj(dsa, A(ak)) + kj(Ua, A(k)), colsum(ak, k))
+  b_k = fin(refs[1], qi(e_gs, A(aq)) + qi(e_uv, A(q)), qi(dsa, A(aq)) + qi(Ua, A(q)), colsum(aq, q))
+  b_v = fin(refs[2], qi(e_tv, A(go)), qi(Ta, A(go)), colsum(go))
+  b_go = fin(refs[3], kj(e_pv, A(av)) + kj(e_tv, A(v)), kj(p, A(av)) + kj(Ta, A(v)), colsum(av, v))
+  return b_q, b_k, b_v, b_go
+
+
+ATTENTION_FAMILIES = ('benign', 'ramp_up', 'ramp_down', 'slow_up', 'mixed', 'late_spike', 'big', 'equal')
+
+
+def attention_family(name, n, ln, dk, rng, rnd):
+  """q, k [n, len, d_qk] of one score family, built in float64 and rounded to the storage type by `rnd`.  benign: q =
+  tanh(randn), k = tanh(2 randn); the others overwrite feature 0 (j = key index / len):
+      ramp_up     q0 = 4, k0 = 16 j          every 32-key block raises the maximum by 2048 / len
+      ramp_down   q0 = 4, k0 = -16 j         the maximum sits in block 0, later probabilities underflow the 16-bit pack
+      slow_up     q0 = 4, k0 = 1.25 (len / 32) j     a rise of 5 per block: stale maximum, p > 1, a rescale every second block
+      mixed       q0 = +4 (odd queries) / -4 (even), k0 = 16 j    the lanes of one wave disagree on `raise`
+      late_spike  q0 = 4, k0 = 0 except k[len - 3][0] = 20        one rescale by e^80 in the last block, saturated rows
+      big         q and k times 6
+      equal       every key the same: uniform rows"""
+  q = np.tanh(rng.randn(n, ln, dk))
+  k = np.tanh(rng.randn(n, ln, dk) * 2)
+  j = np.arange(ln) / float(ln)
+  if name in ('ramp_up', 'ramp_down', 'slow_up', 'late_spike'):
+    q[:, :, 0] = 4.0
+  if name == 'ramp_up' or name == 'mixed':
+    k[:, :, 0] = 16.0 * j
+  elif name == 'ramp_down':
+    k[:, :, 0] = -16.0 * j
+  elif name == 'slow_up':
+    k[:, :, 0] = 1.25 * (ln / 32.0) * j
+  elif name == 'late_spike':
+    k[:, :, 0] = 0.0
+    k[:, ln - 3, 0] = 20.0
+  elif name == 'big':
+    q, k = q * 6.0, k * 6.0
+  elif name == 'equal':
+    k = np.repeat(k[:, :1], ln, axis=1)
+  if name == 'mixed':
+    q[:, :, 0] = np.where(np.arange(ln) % 2 == 1, 4.0, -4.0)
+  assert name in ATTENTION_FAMILIES, name
+  return rnd(q), rnd(k)

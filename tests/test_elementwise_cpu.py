@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import elementwise as E
+from oracle import np_ops as N      # noqa: E402  (checker only)
 
 
 def rel_l2(a, b):
@@ -313,3 +314,405 @@ def test_mbstd_conditioning_term_keeps_the_fp32_check_alive(n, groups, c, coinci
   gg[..., c] *= 1.01
   worst, msg = E.check_elementwise(gg, r64[2], bound[2], 'ggo statistic off by 1 %')
   assert msg is not None and 'c %d..%d' % (c, c) in msg, (worst, msg)
+
+
+# ------------------------------------------------------------------------------------------------ flash attention forward
+def f16(a):
+  return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.float16).float().numpy().astype(np.float64)
+
+
+def _r16(a, dtype):
+  """float64 -> the 16-bit type, round to nearest even, straight from float64."""
+  return torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dtype).double().numpy()
+
+
+def flash_fwd_model(q, k, v, dtype, skip_rescale=None, drop_block=None, v_from_image=None):
+  """csrc/flash.hip's forward in numpy: float64 where the kernel is fp32, its 16-bit pack of P, its stale running maximum
+  (raised only when a 32-key block beats it by more than 6, decided per query, taken per 32-query wave), its row sum of the
+  PACKED probabilities -- the clean output the planted faults are edits of:
+      skip_rescale = (image, query, block)          that query's accumulators are not multiplied by corr at that block
+      drop_block = (image, query, feature block, key block)    32 features of one row leave one 32-key block out
+      v_from_image = (image, source)                image `image` reads the V of image `source`
+  -> (O rounded to dtype, lse)."""
+  n, ln, dv = v.shape
+  out, lse = np.empty((n, ln, dv)), np.empty((n, ln))
+  for im in range(n):
+    s = q[im] @ k[im].T
+    vi = v[v_from_image[1]] if v_from_image is not None and v_from_image[0] == im else v[im]
+    m = np.full(ln, -np.inf)
+    acc, l = np.zeros((ln, dv)), np.zeros(ln)
+    for kb in range(ln // 32):
+      sb = s[:, 32 * kb:32 * kb + 32]
+      mx = sb.max(1)
+      rs = mx > m + E.K_STALE
+      wave = np.repeat(rs.reshape(-1, 32).any(1), 32)
+      m_new = np.where(rs, mx, m)
+      with np.errstate(invalid='ignore'):
+        corr = np.where(np.isinf(m), 0.0, np.exp(m - m_new))
+      corr = np.where(wave, corr, 1.0)
+      if skip_rescale is not None and skip_rescale[0] == im and skip_rescale[2] == kb:
+        corr[skip_rescale[1]] = 1.0
+      acc *= corr[:, None]
+      l *= corr
+      m = np.where(wave, m_new, m)
+      pk = _r16(np.exp(sb - m[:, None]), dtype)
+      l += pk.sum(1)
+      add = pk @ vi[32 * kb:32 * kb + 32]
+      if drop_block is not None and drop_block[0] == im and drop_block[3] == kb:
+        add[drop_block[1], 32 * drop_block[2]:32 * drop_block[2] + 32] = 0.0
+      acc += add
+    out[im] = _r16(acc / l[:, None], dtype)
+    lse[im] = m + np.log(l)
+  return out, lse
+
+
+FLASH_TODAY = {'fwd': [(2, 256, 8, 64), (1, 1024, 16, 128), (3, 128, 8, 256)]}      # tests/test_gpu_ops.py's forward cases
+
+
+def flash_guard_today(o, lse, t, dtype):
+  """test_flash_attention_forward's assertions: rel-L2 of O, max |lse - want|."""
+  bf = dtype == torch.bfloat16
+  return rel_l2(o, t['o']) < (6e-3 if bf else 8e-4), float(np.abs(lse - t['lse']).max()) < (2e-3 if bf else 3e-4)
+
+
+def _flash_case(family, n, ln, dk, dv, dtype, seed=7):
+  rng = np.random.RandomState(seed)
+  rnd = lambda a: _r16(a, dtype)
+  q, k = E.attention_family(family, n, ln, dk, rng, rnd)
+  v = rnd(rng.randn(n, ln, dv))
+  t = E.attention_terms(q, k, v)
+  return q, k, v, t, E.attention_fwd_bound(t, dk, dtype), E.attention_lse_bound(t, dk, dtype)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('family', E.ATTENTION_FAMILIES)
+def test_flash_forward_model_is_inside_the_derived_bound(family, dtype):
+  """The numpy model of the forward kernel (its pack, its stale maximum, its rescales) on every score family: every element of
+  O and lse inside the bound derived in elementwise.attention_fwd_bound / attention_lse_bound, and not by orders of
+  magnitude -- the bound is of the size of the pack's rounding, which the model performs (late_spike: every row attends to
+  one key with p = 1 exactly, O is that key's V, no rounding happens)."""
+  q, k, v, t, bo, bl = _flash_case(family, 2, 256, 8, 64, dtype)
+  o, lse = flash_fwd_model(q, k, v, dtype)
+  wo = E.assert_elementwise(o, t['o'], bo, 'model O %s' % family)
+  wl = E.assert_elementwise(lse, t['lse'], bl, 'model lse %s' % family)
+  print('flash model %-10s %s: worst ratio O %.3f lse %.3f' % (family, dtype, wo, wl))
+  assert wo <= 1.0 and wl <= 1.0 and (wo > 0.05 or family == 'late_spike')
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_planted_flash_fault_one_key_block_missing_from_one_feature_block(dtype):
+  """One (query row, 32-feature block) of O accumulated without one 32-key block (a lost MFMA step), at today's (1, 1024, 16,
+  128): 32 elements of 131072 move by a few per cent of their magnitude -- inside today's rel-L2, outside the element bound,
+  and the message names the row and the feature block."""
+  q, k, v, t, bo, bl = _flash_case('benign', 1, 1024, 16, 128, dtype)
+  # the (row, key block) whose share of the row's probability is nearest 5 % (bf16) / 1 % (fp16): about ten times the pack's
+  # rounding, well under what rel-L2 over the tensor notices
+  mass = t['p'][0].reshape(1024, 32, 32).sum(-1)
+  row, kb = np.unravel_index(int(np.argmin(np.abs(mass - (0.05 if dtype == torch.bfloat16 else 0.01)))), mass.shape)
+  o, lse = flash_fwd_model(q, k, v, dtype, drop_block=(0, int(row), 1, int(kb)))
+  assert flash_guard_today(o, lse, t, dtype) == (True, True)
+  worst, msg = E.check_elementwise(o, t['o'], bo, 'key block dropped')
+  assert msg is not None and worst > 3.0 and 'd0 0..0' in msg and 'd1 %d..%d' % (row, row) in msg, (worst, msg)
+  lo = [int(x) for x in msg.split('d2 ')[1].split(';')[0].split('..')]
+  assert 32 <= lo[0] and lo[1] <= 63, msg
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_planted_flash_fault_one_row_lse_off_by_4u(dtype):
+  """One row's lse off by 4 u.  Today's guard on lse is an absolute 2e-3 (bf16) / 3e-4 (fp16) = u / 2 and u / 1.6: it does
+  catch 4 u on the benign family -- and it rejects the CLEAN model on the families it was never run on (one dominant,
+  rounded probability moves lse by up to u), so it cannot be carried over to them.  The derived bound accepts the clean
+  model everywhere (the test above) and rejects 4 u on every family."""
+  u = E.unit_roundoff(dtype)
+  rejected_clean = 0
+  for family in E.ATTENTION_FAMILIES:
+    q, k, v, t, bo, bl = _flash_case(family, 1, 256, 8, 64, dtype)
+    o, lse = flash_fwd_model(q, k, v, dtype)
+    rejected_clean += not flash_guard_today(o, lse, t, dtype)[1]
+    lse[0, 130] += 4 * u
+    worst, msg = E.check_elementwise(lse, t['lse'], bl, 'lse + 4u')
+    assert msg is not None and worst > 1.5 and 'd1 130..130' in msg, (family, worst, msg)
+  assert rejected_clean >= 1
+
+
+def test_planted_flash_fault_one_rescale_skipped():
+  """One query of a ramp keeps its accumulators unscaled at ONE rescale, the one before the last.  Scores: q0 = 4 against a
+  staircase k0 rising by 6.5 / 4 per 32-key block (every block beats the stale maximum by just over kStaleMax), the other key
+  features zero; V = +1, +1, -1, -1 by block plus noise, so that what the blocks before the skipped rescale hold differs from
+  the row's value.  They then weigh e^6.5 times too much: e^-6.5 = 1.5e-3 of the row -- the largest effect a skipped rescale can
+  have short of the last one (a rescale happens only above kStaleMax = 6, so what it scales is at most e^-6 of the row once
+  another follows).  That is under one bf16 u -- no element check can see it there, nor is it an error worth seeing -- so this
+  fault is planted in fp16: 64 elements of one row, inside today's rel-L2 (8e-4), outside the element bound."""
+  dtype = torch.float16
+  n, ln, dk, dv = 3, 256, 16, 64
+  rng = np.random.RandomState(21)
+  rnd = lambda a: _r16(a, dtype)
+  q, k = E.attention_family('benign', n, ln, dk, rng, rnd)
+  q[:, :, 0] = 4.0
+  k[:] = 0.0
+  k[:, :, 0] = rnd(6.5 / 4.0 * (np.arange(ln) // 32))      # a staircase: one step per block
+  v = rnd(np.where((np.arange(ln) // 32) % 4 < 2, 1.0, -1.0)[None, :, None] + 0.1 * rng.randn(n, ln, dv))
+  t = E.attention_terms(q, k, v)
+  bo, bl = E.attention_fwd_bound(t, dk, dtype), E.attention_lse_bound(t, dk, dtype)
+  o, lse = flash_fwd_model(q, k, v, dtype)
+  assert E.assert_elementwise(o, t['o'], bo, 'clean staircase') <= 1.0
+  of, lf = flash_fwd_model(q, k, v, dtype, skip_rescale=(2, 41, ln // 32 - 2))
+  assert flash_guard_today(of, lf, t, dtype)[0]
+  worst, msg = E.check_elementwise(of, t['o'], bo, 'rescale skipped')
+  assert msg is not None and worst > 1.5 and 'd0 2..2' in msg and 'd1 41..41' in msg, (worst, msg)
+  # lse sees it too: l is too large by the same e^-6.5 of itself
+  worst, msg = E.check_elementwise(lf, t['lse'], bl, 'rescale skipped, lse')
+  assert msg is not None and 'd1 41..41' in msg, (worst, msg)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_planted_flash_fault_image_one_of_three_reads_image_zeros_v(dtype):
+  """Image 1 of 3 computed from image 0's V (the img * d_v * len offset of the packed V workspace), at (3, 256, 16, 64).
+  Today's forward test has no case of this template instance (d_qk 16 with d_v 64) and none with three images of two loop
+  trips: the guard the suite has today is never asked.  Where it IS asked -- the same fault at its own (3, 128, 8, 256) --
+  it fails, as it should: the gap is the shape list, not the measure.  The element check fails on image 1 only, and so does
+  the comparison of image 1 with the same image run alone (bit for bit on the clean model)."""
+  shape = (3, 256, 16, 64)
+  assert shape not in FLASH_TODAY['fwd'] and not any(s[2:] == shape[2:] for s in FLASH_TODAY['fwd'])
+  q, k, v, t, bo, bl = _flash_case('benign', *shape, dtype=dtype)
+  o, lse = flash_fwd_model(q, k, v, dtype, v_from_image=(1, 0))
+  worst, msg = E.check_elementwise(o, t['o'], bo, 'image 1 from V[0]')
+  assert msg is not None and worst > 100.0 and 'd0 1..1' in msg, (worst, msg)
+  clean, _ = flash_fwd_model(q, k, v, dtype)
+  alone, _ = flash_fwd_model(q[1:2], k[1:2], v[1:2], dtype)
+  assert np.array_equal(clean[1], alone[0]) and not np.array_equal(o[1], alone[0])
+  q, k, v, t, bo, bl = _flash_case('benign', 3, 128, 8, 256, dtype=dtype)
+  o, lse = flash_fwd_model(q, k, v, dtype, v_from_image=(1, 0))
+  assert not flash_guard_today(o, lse, t, dtype)[0]
+
+
+# ------------------------------------------------------------------------------------------------ flash attention backwards
+def flash_bwd_maps(q, k, v, go, dtype):
+  """What csrc/flash.hip's two backward passes hold per (query, key) before their second products, in numpy: the probability
+  recomputed from the forward model's lse, D = <dO, O> from the forward model's STORED O, and the 16-bit packs of P and dS --
+  the clean maps the planted faults below are edits of -> dict(p16, ds16, ph, D, gp)."""
+  o16, lse = flash_fwd_model(q, k, v, dtype)
+  ph = np.exp(np.einsum('nid,njd->nij', q, k) - lse[..., None])
+  gp = np.einsum('nid,njd->nij', go, v)
+  D = (go * o16).sum(-1, keepdims=True)
+  return dict(p16=_r16(ph, dtype), ds16=_r16(ph * (gp - D), dtype), ph=ph, D=D, gp=gp)
+
+
+def _dropped_block(m, x, ref, bound, tol=None):
+  """Among every (image, row, block of 32) of the sum over the last index of m against x: the block whose loss moves its row
+  furthest outside `bound` -- with `tol`, among those that keep the whole tensor's rel-L2 under half of it (the loss LEAST
+  visible to rel-L2 for what it does to its row; searched, not tuned) -> (image, row, block, delta [d], ratio)."""
+  n, ln, _ = m.shape
+  delta = np.einsum('nibj,nbjd->nibd', m.reshape(n, ln, ln // 32, 32), x.reshape(n, ln // 32, 32, -1))      # [n, i, block, d]
+  ratio = (np.abs(delta) / bound[:, :, None, :]).max(-1)
+  if tol is not None:
+    ratio = np.where(np.sqrt((delta ** 2).sum(-1)) / np.linalg.norm(ref) < 0.5 * tol, ratio, 0.0)
+  im, row, kb = (int(i) for i in np.unravel_index(int(np.argmax(ratio)), ratio.shape))
+  return im, row, kb, delta[im, row, kb], float(ratio[im, row, kb])
+
+
+def _flash_bwd_case(family, dtype):
+  n, ln, dk, dv = 1, 512, 16, 128      # a case of today's test_flash_attention_backward
+  rng = np.random.RandomState(11)
+  rnd = lambda a: _r16(a, dtype)
+  q, k = E.attention_family(family, n, ln, dk, rng, rnd)
+  v, go = rnd(rng.randn(n, ln, dv)), rnd(rng.randn(n, ln, dv))
+  t = E.attention_terms(q, k, v)
+  r = E.attention_grads_reference(q, k, v, go, t)
+  bounds = E.attention_bwd_bounds(q, k, v, go, t, r, dk, dtype)
+  mp = flash_bwd_maps(q, k, v, go, dtype)
+  raw = (np.einsum('nij,njd->nid', mp['ds16'], k), np.einsum('nij,nid->njd', mp['ds16'], q), np.einsum('nij,nid->njd', mp['p16'], go))
+  return q, k, go, r, bounds, mp, raw, rnd
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_planted_flash_faults_in_the_first_order_backward(dtype):
+  """The numpy model of the packed P and dS at today's (1, 512, 16, 128): dQ, dK and dV inside attention_bwd_bounds.
+  (a) dV: one key's row summed without one block of 32 queries (a lost MFMA step of flash_bwd_kv_kernel) passes today's guard
+      -- rel-L2 of every gradient under 1.2e-2 (bf16) / 2e-3 (fp16) -- and is far outside the element bound, which names the row.
+  (b) dQ: the same fault in flash_bwd_q_kernel.  Here the bound is NOT the sharper measure on benign rows: D = <dO, O> from the
+      16-bit O (d_v worst-case roundings, about 17 u of dS at d_v = 128) and the pack on |dO| |V|^T make it about 50 u of
+      the row, and the worst dropped block that rel-L2 still passes reaches a ratio of 0.36 (bf16) / 0.49 (fp16), printed
+      below.  What the bound adds for dQ and dK is the families rel-L2 cannot be asked on: on ramp_up the CLEAN model has a
+      rel-L2 of 1.8e-2 / 2.4e-3 -- today's guard rejects an honest kernel (cancellation along the ramp) -- while every element
+      is inside the bound, and a row that lost one key block is outside it."""
+  tol = 1.2e-2 if dtype == torch.bfloat16 else 2e-3
+  names = ('dq', 'dk', 'dv')
+  q, k, go, r, bounds, mp, raw, rnd = _flash_bwd_case('benign', dtype)
+  worst = [E.assert_elementwise(rnd(g), r[nm], b, 'model ' + nm) for g, nm, b in zip(raw, names, bounds)]
+  print('flash bwd model %s: worst ratios dq %.3f dk %.3f dv %.3f' % ((dtype,) + tuple(worst)))
+  assert max(worst) <= 1.0
+  im, row, qb, delta, _ = _dropped_block(mp['p16'].transpose(0, 2, 1), go, r['dv'], bounds[2], tol)
+  bad = raw[2].copy()
+  bad[im, row] -= delta
+  assert all(rel_l2(rnd(g), r[nm]) < tol for g, nm in zip(raw[:2] + (bad,), names))      # today's guard
+  w, msg = E.check_elementwise(rnd(bad), r['dv'], bounds[2], 'query block missing from dV')
+  print('flash bwd fault %s: dV key %d query block %d, rel-L2 %.2e, worst ratio %.2f' % (dtype, row, qb, rel_l2(rnd(bad), r['dv']), w))
+  assert msg is not None and w > 5.0 and 'd1 %d..%d' % (row, row) in msg, (w, msg)
+  print('flash bwd %s: the worst key block a row of dQ can lose under today\'s rel-L2: ratio %.2f'
+        % (dtype, _dropped_block(mp['ds16'], k, r['dq'], bounds[0], tol)[4]))
+  q, k, go, r, bounds, mp, raw, rnd = _flash_bwd_case('ramp_up', dtype)
+  assert E.assert_elementwise(rnd(raw[0]), r['dq'], bounds[0], 'model dq, ramp_up') <= 1.0
+  assert rel_l2(rnd(raw[0]), r['dq']) > tol      # today's guard rejects the clean model: it cannot be asked here
+  im, row, kb, delta, _ = _dropped_block(mp['ds16'], k, r['dq'], bounds[0])
+  bad = raw[0].copy()
+  bad[im, row] -= delta
+  w, msg = E.check_elementwise(rnd(bad), r['dq'], bounds[0], 'key block missing from dQ, ramp_up')
+  print('flash bwd fault %s: ramp_up dQ row %d key block %d, worst ratio %.2f' % (dtype, row, kb, w))
+  assert msg is not None and w > 2.0 and 'd1 %d..%d' % (row, row) in msg, (w, msg)
+
+
+def flash_bb_model(q, k, v, go, aq, ak, av, dtype, e_from_image=None):
+  """csrc/flash.hip's second-order pass in numpy: the statistics D (from the stored O), E and F in float64, the four maps P,
+  gS, T, U packed to 16 bit, then the closed form's products (oracle/np_ops.attention_backward_backward).  e_from_image =
+  (image, source): image `image` reads the E statistic of image `source` (a wrong per-image offset of the statistics
+  workspace).  -> the unrounded (adj q, adj k, adj v, adj dO) and the packed maps."""
+  mp = flash_bwd_maps(q, k, v, go, dtype)
+  p, D, gp = mp['ph'], mp['D'], mp['gp']
+  w = np.einsum('nid,njd->nij', aq, k) + np.einsum('nid,njd->nij', q, ak)
+  e = (p * w).sum(-1, keepdims=True)
+  if e_from_image is not None:
+    e = e.copy()
+    e[e_from_image[0]] = e[e_from_image[1]]
+  x = np.einsum('nid,njd->nij', go, av) + w * (gp - D) - e * gp
+  f = (p * x).sum(-1, keepdims=True)
+  m = dict(pv=mp['p16'], gs=mp['ds16'], tv=_r16(p * (w - e), dtype), uv=_r16(p * (x - f), dtype))
+  kj = lambda a, b: np.einsum('nij,njd->nid', a, b)
+  qi = lambda a, b: np.einsum('nij,nid->njd', a, b)
+  return [kj(m['gs'], ak) + kj(m['uv'], k), qi(m['gs'], aq) + qi(m['uv'], q), qi(m['tv'], go), kj(m['pv'], av) + kj(m['tv'], v)], m
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+def test_planted_flash_faults_in_the_second_order_pass(dtype):
+  """Second order at today's (2, 256, 8, 64): the numpy model of the four packed maps gives the four adjoints inside
+  attention_bwd_bwd_bounds.  (a) One query row of adj dO = P aV + T V whose T V sum misses one 32-key block passes today's
+  guard (rel-L2 under 2.5e-2 bf16 / 4e-3 fp16 on all four) and is outside the element bound, which names the row.  (b) Image
+  1 reading image 0's E statistic is outside the bound on image 1 alone, in adj v and adj dO (the maps E enters); rel-L2 sees
+  that one too at this shape -- it is here to show the bound rejects it, and the device test's image-alone comparison is
+  what pins the offsets at every shape."""
+  n, ln, dk, dv = 2, 256, 8, 64
+  rng = np.random.RandomState(13)
+  rnd = lambda a: _r16(a, dtype)
+  q, k = E.attention_family('benign', n, ln, dk, rng, rnd)
+  v, go, av = (rnd(rng.randn(n, ln, dv)) for _ in range(3))
+  aq, ak = rnd(rng.randn(n, ln, dk)), rnd(rng.randn(n, ln, dk))
+  t = E.attention_terms(q, k, v)
+  r = E.attention_grads_reference(q, k, v, go, t)
+  r['bb'] = N.attention_backward_backward(q, k, v, go, aq, ak, av)
+  bounds = E.attention_bwd_bwd_bounds(q, k, v, go, aq, ak, av, t, r, dk, dtype)
+  raw, m = flash_bb_model(q, k, v, go, aq, ak, av, dtype)
+  names = ('adj q', 'adj k', 'adj v', 'adj dO')
+  worst = [E.assert_elementwise(rnd(g), ref, b, 'model ' + nm) for g, ref, b, nm in zip(raw, r['bb'], bounds, names)]
+  print('flash bwd_bwd model %s: worst ratios %s' % (dtype, ' '.join('%s %.3f' % x for x in zip(names, worst))))
+  assert max(worst) <= 1.0
+  tol = 2.5e-2 if dtype == torch.bfloat16 else 4e-3
+  im, row, kb, delta, _ = _dropped_block(m['tv'], v, r['bb'][3], bounds[3], tol)
+  bad = raw[3].copy()
+  bad[im, row] -= delta
+  assert all(rel_l2(rnd(g), ref) < tol for g, ref in zip(raw[:3] + [bad], r['bb']))      # today's guard
+  w, msg = E.check_elementwise(rnd(bad), r['bb'][3], bounds[3], 'key block missing from adj dO')
+  print('flash bwd_bwd fault %s: image %d row %d block %d, rel-L2 %.2e, worst ratio %.2f' % (dtype, im, row, kb, rel_l2(bad, r['bb'][3]), w))
+  assert msg is not None and w > 2.0 and 'd0 %d..%d' % (im, im) in msg and 'd1 %d..%d' % (row, row) in msg, (w, msg)
+  off, _ = flash_bb_model(q, k, v, go, aq, ak, av, dtype, e_from_image=(1, 0))
+  for i in (2, 3):
+    w, msg = E.check_elementwise(rnd(off[i]), r['bb'][i], bounds[i], names[i] + ', E of image 0 in image 1')
+    assert msg is not None and w > 2.0 and 'd0 1..1' in msg, (names[i], w, msg)
+
+
+# ------------------------------------------------------------------------------------------------ batched GEMM
+def test_planted_gemm_fault_one_vector_of_the_last_ragged_tile_keeps_its_old_value():
+  """C (+)= 0.5 A B at (2, 1032, 520, 8) in bf16 onto a non-zero C: the last row tile has 8 of its 128 rows, the last column tile
+  8 of its 64 columns.  One 8-element vector of that corner keeps the value C held before: 8 of a million elements -- rel-L2
+  2.7e-3 < today's 4e-3; outside the element bound."""
+  rng = np.random.RandomState(5)
+  b_, m, n, k = 2, 1032, 520, 8
+  a, b, c0 = bf16(rng.randn(b_, m, k)), bf16(rng.randn(b_, k, n)), bf16(rng.randn(b_, m, n))
+  ref = 0.5 * (a @ b) + c0
+  bound = E.gemm_bound(ref, 0.5 * (np.abs(a) @ np.abs(b)), k, torch.bfloat16, c0=c0)
+  clean = bf16(ref.astype(np.float32))
+  assert 0.5 < E.assert_elementwise(clean, ref, bound, 'clean gemm') <= 1.0
+  got = clean.copy()
+  got[1, 1031, 512:520] = c0[1, 1031, 512:520]
+  assert rel_l2(got, ref) < 4e-3
+  worst, msg = E.check_elementwise(got, ref, bound, 'stale vector')
+  assert msg is not None and worst > 10.0 and 'd0 1..1' in msg and 'd1 1031..1031' in msg and 'd2 512..519' in msg, (worst, msg)
+
+
+# ------------------------------------------------------------------------------------------------ scalar reductions
+def _sum_model(x, V, threads, drop_tail=False):
+  """sum_kernel's order in fp32: per thread its vectors (grid stride), then its tail elements, then the tree."""
+  x = x.astype(np.float32)
+  nvec = x.size // V
+  acc = np.zeros(threads, np.float32)
+  body = x[:nvec * V].reshape(nvec, V)
+  for i0 in range(0, nvec, threads):
+    chunk = body[i0:i0 + threads]
+    for j in range(V):
+      acc[:chunk.shape[0]] += chunk[:, j]
+  if not drop_tail:
+    tail = x[nvec * V:]
+    acc[:tail.size] += tail
+  return float(acc.reshape(-1, 2).sum(1, dtype=np.float32).sum(dtype=np.float32))
+
+
+def test_planted_sum_fault_the_vector_tail_dropped():
+  """tg_sum at the sizes the suite has today (384 and 768 elements, 6 x 64 x 64 x 32 in the ordered test) has no vector tail:
+  a kernel that drops the tail loop returns the same bits there, whatever the guard.  At 4099 = 512 vectors of 8 + 3, with the
+  tail elements (and each workgroup's first and last element) a thousand times the rest, the dropped tail is far outside
+  L 2^-24 sum|x| -- and so would ONE dropped or doubled element of them be."""
+  rng = np.random.RandomState(9)
+  for numel in (384, 768):
+    x = bf16(rng.rand(numel))
+    assert numel % 8 == 0 and _sum_model(x, 8, 256) == _sum_model(x, 8, 256, drop_tail=True)
+  numel = 4099
+  x = bf16(rng.rand(numel))
+  x[4096:] *= 1e3
+  L, blocks = E.reduction_chain(numel, torch.bfloat16, 1024)
+  assert blocks == 3 and L == 1 * 8 + 1 + 6 + 4 + 3 + 1
+  bound = E.reduction_bound(np.abs(x).sum(), L)
+  ref = x.sum()
+  assert abs(_sum_model(x, 8, 256 * blocks) - ref) <= bound
+  assert abs(_sum_model(x, 8, 256 * blocks, drop_tail=True) - ref) > 100 * bound
+  assert np.abs(x[4096:]).min() > 100 * bound      # one spiked element alone is visible
+  # the geometry: a 16 x 256 x 256 x 3 tensor takes more than one grid-stride trip at every workgroup cap the entry points use
+  big = 16 * 256 * 256 * 3
+  for cap in (1024, 512, 64):
+    Lb, nb = E.reduction_chain(big, torch.bfloat16, cap)
+    assert nb == cap and Lb >= 2 * 8 + cap
+  assert E.reduction_chain(75, torch.bfloat16, 64, vec=False) == (1 + 6 + 4 + 1 + 1, 1)
+
+
+# ------------------------------------------------------------------------------------------------ Adam
+def test_adam_bound_accepts_fp32_arithmetic_and_rejects_a_wrong_epsilon_placement():
+  """adam_step_bounds: numpy's float32 evaluation of the kernel's formula (with and without the products contracted into the
+  sums) sits inside the per-element bounds for theta, m and v over ten steps with |g| from 1e-20 to 1e4 and g = 0; epsilon
+  inside the root (the other Adam), a missing grad_scale, and beta2 used for m do not."""
+  rng = np.random.RandomState(3)
+  f = np.float32
+  n = 257
+  th, m, v = f(rng.randn(n)), np.zeros(n, f), np.zeros(n, f)
+  th[::8] = 0.0      # where theta is of the update's own size nothing hides the update behind theta's rounding
+  scale = np.where(np.arange(n) % 4 == 1, 1e4, np.where(np.arange(n) % 4 == 2, 1e-20, 1.0))
+  scale[np.arange(n) % 4 == 3] = 0.0
+  b1, b2, eps, gs = f(0.5), f(0.99), f(1e-8), f(1.0 / 1024)
+  for step in range(1, 11):
+    g = f(rng.randn(n) * scale * 1024)
+    lr_t = f(1e-4 * np.sqrt(1 - 0.99 ** step) / (1 - 0.5 ** step))
+    (rt, rm, rv), (bt, bm, bv) = E.adam_step_bounds(th.astype(np.float64), g.astype(np.float64), m.astype(np.float64),
+                                                    v.astype(np.float64), lr_t, b1, b2, eps, gs)
+    with np.errstate(under='ignore'):
+      gi = g * gs
+      mi = b1 * m + (f(1) - b1) * gi
+      vi = b2 * v + (f(1) - b2) * gi * gi
+      t = th - lr_t * mi / (np.sqrt(vi) + eps)
+      assert E.assert_elementwise(t, rt, bt, 'theta') <= 1.0 and E.assert_elementwise(mi, rm, bm, 'm') <= 1.0
+      assert E.assert_elementwise(vi, rv, bv, 'v') <= 1.0
+      # contracted: products in float64, one rounding at the sum
+      mc = f(np.float64(b1) * m + np.float64(f(1) - b1) * gi)
+      assert E.assert_elementwise(mc, rm, bm, 'm contracted') <= 1.0
+      if step == 3:
+        wrong = th - lr_t * mi / np.sqrt(vi + eps)
+        assert E.check_elementwise(wrong, rt, bt, 'eps inside the root')[1] is not None
+        assert E.check_elementwise(th - lr_t * (b1 * m + (f(1) - b1) * g) / (np.sqrt(vi) + eps), rt, bt, 'no grad_scale')[1] is not None
+        assert E.check_elementwise(b2 * m + (f(1) - b2) * gi, rm, bm, 'beta2 for m')[1] is not None
+    th, m, v = t, mi, vi

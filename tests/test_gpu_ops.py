@@ -15,6 +15,14 @@ the emulated kernels): every element against its own bound, built from the float
   pool, upsample^T u |ref| (16-bit); fp32: + 3 2^-24 sum|x|  a sum of four stored values
   streaming ops    u |ref| + (1 + u) ops 2^-24 mag      the kernel's own 1-4 fp32 operations
   copies           array_equal
+  flash forward    O: u |ref| + (1 + u) [((u + eps + len 2^-24) (mag + |ref|) + tiny16 (sum|v| + len |ref|)) / (1 - rho) + 2 2^-24 |ref|]
+                   lse: -log(1 - rho) + 3 2^-24 (lse - max s + 6 + rho) + 2^-24 |lse|;  eps = ((d_qk + 9) A + 2 + 3 len / 32) 2^-24
+  flash backward   u |ref| + R u mag + A 2^-24 mag + 2^-25 S    P, dS packed; the forward's lse and O bounds carried in
+  flash 2nd order  the same over the packed maps P, gS, T, U and the statistics D, E, F; magnitudes from the closed form
+  batched GEMM     the conv bound with K = k + 1 (alpha) + 1 (accumulate), mag = |alpha| |a| |b| + |C0|
+  softmax kernels  u |ref| + 16 E32, each kernel on the operands it reads
+  scalar sums      L 2^-24 |scale| sum|terms|            L: the longest chain of additions the launch geometry allows
+  Adam             one step in float64 from the fp32 state it reads, each fp32 operation counted; the bf16 shadow bit-exact
 with u = 2^-8 (bf16), 2^-11 (fp16), 2^-24 (fp32), `+ tiny` everywhere (2^-25 for fp16: half its subnormal spacing), and
 every further storage rounding the product path defines named where it is added.  Each check prints
 `[elementwise] <family> <dtype> worst ratio <r>` (run with -s).
@@ -64,6 +72,7 @@ def tol_for(dtype, grad=False):
 
 
 # ---------------------------------------------------------------------------------------------- element-wise bookkeeping
+import functools            # noqa: E402
 import zlib                  # noqa: E402
 import elementwise as E      # noqa: E402
 
@@ -3620,3 +3629,451 @@ def test_norm_act_fed_by_conv_statistics_elementwise(ops, producer, n, hw, cin, 
     zmag = np.abs(ref).reshape(n, hw // 2, 2, hw // 2, 2, cout).mean(axis=(2, 4))
     bound = E.e32_bound(refp, E.e32(r32['zp'].numpy(), refp), dtype) + (1 + u_st) * u_st * zmag
     _ew_note('norm_act conv_stats zp', dname, E.assert_elementwise(host(zp), refp, bound, what + ' zp'))
+
+
+# ===================================================================== attention, softmax, GEMM, losses, Adam: element-wise
+# The derivations are in tests/elementwise.py (each count names the kernel operation it stands for); one line each:
+#   flash forward    u |ref| + (1 + u) [((u + eps + len 2^-24) (mag + |ref|) + tiny16 (sum|v| + len |ref|)) / (1 - rho) + 2 2^-24 |ref|]
+#                    eps = ((d_qk + 9) A + 2 + 3 len / 32) 2^-24, A = max_j |q_i| . |k_j|, mag = softmax(s) |v|
+#   flash lse        -log(1 - rho) + 3 2^-24 (lse - max s + 6 + rho) + 2^-24 |lse|,   rho = u + eps + len 2^-24 + len tiny16
+#   flash dQ dK dV   u |ref| + R u mag + A 2^-24 mag + 2^-25 S: P / dS packed, the forward's lse and O bounds carried in, A = len + d_v + 3
+#   flash 2nd order  the same form over the four packed maps (P, gS, T, U); magnitudes: the closed form on |operands|, differences as sums
+#   batched GEMM     conv_bound with K = k + 1 (alpha) + 1 (accumulate), mag = |alpha| |a| |b| + |C0|
+#   softmax kernels  u |ref| + 16 E32, each kernel on the operands it reads
+#   scalar sums      L 2^-24 |scale| sum|terms|, L from the launch geometry (trips, tail, tree, one add per workgroup)
+#   Adam             one step in float64 from the fp32 state it reads, every fp32 operation counted once
+FLASH_DTYPES = {'bf16': torch.bfloat16, 'f16': torch.float16}
+FLASH_FWD_SHAPES = [(1, 128, 8, 64), (3, 256, 16, 64), (2, 384, 8, 128), (1, 256, 16, 128), (2, 128, 16, 256), (1, 384, 8, 256)]
+FLASH_BWD_SHAPES = [(1, 128, 8, 64), (3, 256, 16, 64), (2, 384, 8, 128), (1, 256, 16, 128)]
+FLASH_BB_SHAPES = [(1, 128, 8, 64), (2, 256, 16, 64), (1, 256, 8, 128), (2, 128, 16, 128)]
+FLASH_FWD_CASES = [(f,) + s for s in FLASH_FWD_SHAPES for f in E.ATTENTION_FAMILIES] + \
+    [(f, 1, 1024, 16, 128) for f in ('benign', 'ramp_up')]
+FLASH_BWD_CASES = [(f,) + s for s in FLASH_BWD_SHAPES for f in E.ATTENTION_FAMILIES]
+FLASH_BB_CASES = [(f,) + s for s in FLASH_BB_SHAPES for f in E.ATTENTION_FAMILIES]
+
+
+def _r16(a, dtype):
+  return bf16_round(a) if dtype == torch.bfloat16 else f16_round(a)
+
+
+@functools.lru_cache(maxsize=None)
+def _flash_inputs(family, n, ln, dk, dv, dname):
+  """Operands of one case (float64 values of the storage type) and their float64 attention, computed once and shared by the
+  forward, first-order and second-order tests; nobody writes to them."""
+  dtype = FLASH_DTYPES[dname]
+  rng = np.random.RandomState(zlib.crc32(('%s%d%d%d%d' % (family, n, ln, dk, dv)).encode()) % (2 ** 31))
+  rnd = lambda a: _r16(a, dtype)
+  q, k = E.attention_family(family, n, ln, dk, rng, rnd)
+  v, go = rnd(rng.randn(n, ln, dv)), rnd(rng.randn(n, ln, dv))
+  adj = tuple(rnd(rng.randn(n, ln, d)) for d in (dk, dk, dv))
+  t = E.attention_terms(q, k, v)
+  for a in (q, k, v, go) + adj + tuple(x for x in t.values()):
+    a.setflags(write=False)
+  return dict(q=q, k=k, v=v, go=go, adj=adj, t=t)
+
+
+@pytest.mark.parametrize('dname', sorted(FLASH_DTYPES))
+@pytest.mark.parametrize('family,n,ln,dk,dv', FLASH_FWD_CASES)
+def test_flash_attention_forward_elementwise(ops, family, n, ln, dk, dv, dname):
+  """tg_flash_attention_fwd on the eight score families (elementwise.attention_family: real rescales every block, a stale
+  maximum with p > 1, lanes of one wave that disagree on `raise`, probabilities under the 16-bit pack's range, one rescale by
+  e^80, saturated and uniform rows), every template instance, one / several loop trips and an odd number of 128-query
+  workgroups: EVERY element of O and of lse inside its derived bound against float64 on the rounded operands; and each image
+  of a batch bit-identical to the same image run alone (the img * d_v * len offsets of the packed V workspace)."""
+  dtype = FLASH_DTYPES[dname]
+  c = _flash_inputs(family, n, ln, dk, dv, dname)
+  qd, kd, vd = (to_dev(c[x], dtype) for x in 'qkv')
+  assert ops.flash_attention_supported(qd, vd)
+  o, lse = ops.flash_attention_fwd_raw(qd, kd, vd)
+  t = c['t']
+  wo = E.assert_elementwise(host(o), t['o'], E.attention_fwd_bound(t, dk, dtype), 'flash O %s' % family)
+  wl = E.assert_elementwise(host(lse), t['lse'], E.attention_lse_bound(t, dk, dtype), 'flash lse %s' % family)
+  _ew_note('flash fwd O %s' % family, dname, wo)
+  _ew_note('flash fwd lse %s' % family, dname, wl)
+  for i in range(n if n > 1 else 0):
+    o1, l1 = ops.flash_attention_fwd_raw(qd[i:i + 1].contiguous(), kd[i:i + 1].contiguous(), vd[i:i + 1].contiguous())
+    assert torch.equal(o1[0], o[i]) and torch.equal(l1[0], lse[i]), 'image %d of %d differs from the same image alone' % (i, n)
+
+
+@pytest.mark.parametrize('dname', sorted(FLASH_DTYPES))
+@pytest.mark.parametrize('family,n,ln,dk,dv', FLASH_BWD_CASES)
+def test_flash_attention_backward_elementwise(ops, family, n, ln, dk, dv, dname):
+  """tg_flash_attention_bwd fed by the forward kernel's own O and lse (as in the product): every element of dQ, dK, dV inside
+  elementwise.attention_bwd_bounds -- u_out |ref| + R u mag + A 2^-24 mag + 2^-25 S, the forward's lse and O bounds carried in
+  as this kernel's input errors; rel-L2 says nothing here (a saturated row's gradient is 1e-29, an ill-conditioned row's
+  cancels).  Batch independence as in the forward."""
+  dtype = FLASH_DTYPES[dname]
+  c = _flash_inputs(family, n, ln, dk, dv, dname)
+  qd, kd, vd, gd = (to_dev(c[x], dtype) for x in ('q', 'k', 'v', 'go'))
+  assert ops.flash_attention_trainable(qd, vd)
+  o, lse = ops.flash_attention_fwd_raw(qd, kd, vd)
+  got = ops._flash_bwd_raw(qd, kd, vd, o, lse, gd)
+  r = E.attention_grads_reference(c['q'], c['k'], c['v'], c['go'], c['t'])
+  bounds = E.attention_bwd_bounds(c['q'], c['k'], c['v'], c['go'], c['t'], r, dk, dtype)
+  for g, nm, b in zip(got, ('dq', 'dk', 'dv'), bounds):
+    _ew_note('flash bwd %s %s' % (nm, family), dname, E.assert_elementwise(host(g), r[nm], b, 'flash %s %s' % (nm, family)))
+  for i in range(n if n > 1 else 0):
+    sl = lambda x: x[i:i + 1].contiguous()
+    o1, l1 = ops.flash_attention_fwd_raw(sl(qd), sl(kd), sl(vd))
+    for g, g1 in zip(got, ops._flash_bwd_raw(sl(qd), sl(kd), sl(vd), o1, l1, sl(gd))):
+      assert torch.equal(g1[0], g[i]), 'image %d of %d differs from the same image alone' % (i, n)
+
+
+def _flash_second_order(ops, calls, dtype, q, k, v, go, aq, ak, av):
+  """The four adjoints through the product's autograd path; the second-order pass must be the flash kernel's launch, not the
+  batched-GEMM / softmax composition a cleared USE_FLASH_BWD_BWD would select."""
+  qd, kd, vd, gd = (to_dev(x, dtype).requires_grad_(True) for x in (q, k, v, go))
+  assert ops.USE_FLASH_BWD_BWD is True
+  with ops.second_order():
+    assert ops.flash_attention_trainable(qd, vd)
+  o = ops.flash_attention(qd, kd, vd)
+  gq, gk, gv = torch.autograd.grad(o, (qd, kd, vd), gd, create_graph=True)
+  calls.clear()
+  out = torch.autograd.grad((gq, gk, gv), (qd, kd, vd, gd), tuple(to_dev(x, dtype) for x in (aq, ak, av)))
+  names = [c[0] for c in calls]
+  assert names.count('tg_flash_attention_bwd_bwd') == 1, names
+  assert not [x for x in names if x.startswith(('tg_batched_gemm', 'tg_softmax_rows'))], names
+  return out
+
+
+@pytest.mark.parametrize('dname', sorted(FLASH_DTYPES))
+@pytest.mark.parametrize('family,n,ln,dk,dv', FLASH_BB_CASES)
+def test_flash_attention_second_order_elementwise(ops, record_calls, family, n, ln, dk, dv, dname):
+  """tg_flash_attention_bwd_bwd through the product's autograd path (create_graph backward, then its backward): every element of
+  the four adjoints inside elementwise.attention_bwd_bwd_bounds against float64 autograd on the rounded operands, on every
+  score family -- the saturated rows included, where the truth is 1e-29 and the kernel returns the fp32 noise of D against
+  gP times |k| (the bound's (d_v + 3) 2^-24 dsa |K| term, derived there).  And each image of a batch bit-identical to the same
+  image run alone (the per-image offsets of the packed workspaces and of the E / F statistics)."""
+  dtype = FLASH_DTYPES[dname]
+  c = _flash_inputs(family, n, ln, dk, dv, dname)
+  ops_ = (c['q'], c['k'], c['v'], c['go']) + c['adj']
+  got = _flash_second_order(ops, record_calls, dtype, *ops_)
+  r = E.attention_grads_reference(c['q'], c['k'], c['v'], c['go'], c['t'])
+  r['bb'] = _attention_second_order_ref(*ops_)
+  bounds = E.attention_bwd_bwd_bounds(*ops_, c['t'], r, dk, dtype)
+  for g, ref, b, nm in zip(got, r['bb'], bounds, ('adj q', 'adj k', 'adj v', 'adj dO')):
+    _ew_note('flash bwd_bwd %s %s' % (nm, family), dname, E.assert_elementwise(host(g), ref, b, 'flash %s %s' % (nm, family)))
+  for i in range(n if n > 1 else 0):
+    alone = _flash_second_order(ops, record_calls, dtype, *(x[i:i + 1] for x in ops_))
+    for g, g1, nm in zip(got, alone, ('adj q', 'adj k', 'adj v', 'adj dO')):
+      assert torch.equal(g1[0], g[i]), '%s: image %d of %d differs from the same image alone' % (nm, i, n)
+
+
+# ------------------------------------------------------------------------------------------------ batched GEMM
+BGEMM_EW_CASES = BGEMM_CASES + [(2, 136, 72, 40), (2, 264, 200, 72), (1, 8, 8, 8)]      # 16-byte staging with ragged m, n, k tiles
+
+
+def _round_dt(a, dtype):
+  return a.astype(np.float32).astype(np.float64) if dtype == torch.float32 else _r16(a, dtype)
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('batch,m,n,k', BGEMM_EW_CASES)
+def test_batched_gemm_elementwise(ops, batch, m, n, k, dname):
+  """tg_batched_gemm, all four layouts: every element inside conv_bound with K = k + 1 (the alpha multiply).  The last three
+  cases are eligible for the 16-byte vector staging (every extent a multiple of 8) AND ragged in m, n and k."""
+  dtype = EW_DTYPES[dname]
+  rng = np.random.RandomState(zlib.crc32(('bg%d%d%d%d' % (batch, m, n, k)).encode()) % (2 ** 31))
+  for ta in (False, True):
+    for tb in (False, True):
+      a = _round_dt(rng.randn(batch, k, m) if ta else rng.randn(batch, m, k), dtype)
+      b = _round_dt(rng.randn(batch, n, k) if tb else rng.randn(batch, k, n), dtype)
+      oa, ob = (a.transpose(0, 2, 1) if ta else a), (b.transpose(0, 2, 1) if tb else b)
+      ref, mag = 0.5 * np.matmul(oa, ob), 0.5 * np.matmul(np.abs(oa), np.abs(ob))
+      c = ops.bgemm(to_dev(a, dtype), to_dev(b, dtype), ta, tb, 0.5)
+      w = E.assert_elementwise(host(c), ref, E.gemm_bound(ref, mag, k, dtype), 'bgemm ta=%d tb=%d' % (ta, tb))
+      _ew_note('batched gemm', dname, w)
+
+
+@pytest.mark.parametrize('dname,c_f32', [('f32', 0), ('bf16', 0), ('bf16', 1), ('f16', 0), ('f16', 1)])
+@pytest.mark.parametrize('pad', [8, 3])
+@pytest.mark.parametrize('batch,m,n,k', [(2, 136, 72, 40), (1, 8, 8, 8)])
+def test_batched_gemm_c_abi_strides_accumulate_and_f32_output(ops, batch, m, n, k, pad, dname, c_f32):
+  """What include/twingan_hip.h declares and ops.bgemm never passes: accumulate = 1 onto a non-zero C, c_is_f32 = 1 from 16-bit
+  operands, lda / ldb / ldc and batch strides larger than dense (pad 8 keeps the 16-byte staging, pad 3 forces the scalar one).
+  The padding of A and B holds NaN (a kernel that reads it shows), the padding columns, rows and the spare batch slot of C a
+  sentinel that must come back bit-identical."""
+  import twingan_amd.ops as O
+  dtype = EW_DTYPES[dname]
+  cdt = torch.float32 if c_f32 else dtype
+  rng = np.random.RandomState(zlib.crc32(('abi%d%d%d%d%d' % (batch, m, n, k, pad)).encode()) % (2 ** 31))
+  st = torch.cuda.current_stream().cuda_stream
+  for ta in (0, 1):
+    for tb in (0, 1):
+      (ra, ca), (rb, cb) = ((k, m) if ta else (m, k)), ((n, k) if tb else (k, n))
+      a, b = _round_dt(rng.randn(batch, ra, ca), dtype), _round_dt(rng.randn(batch, rb, cb), dtype)
+      c0 = _round_dt(rng.randn(batch, m, n), cdt)
+      A = torch.full((batch, ra + 2, ca + pad), float('nan'), dtype=dtype, device=dev())
+      B = torch.full((batch, rb + 2, cb + pad), float('nan'), dtype=dtype, device=dev())
+      C = torch.full((batch + 1, m + 1, n + pad), -7.25, dtype=cdt, device=dev())
+      A[:, :ra, :ca], B[:, :rb, :cb], C[:batch, :m, :n] = to_dev(a, dtype), to_dev(b, dtype), to_dev(c0, cdt)
+      before = C.clone()
+      O.call('tg_batched_gemm', A.data_ptr(), B.data_ptr(), C.data_ptr(), batch, m, n, k, ta, tb, ca + pad, cb + pad, n + pad,
+             (ra + 2) * (ca + pad), (rb + 2) * (cb + pad), (m + 1) * (n + pad), -0.75, 1, O._dt(A), c_f32, st)
+      oa, ob = (a.transpose(0, 2, 1) if ta else a), (b.transpose(0, 2, 1) if tb else b)
+      ref = -0.75 * np.matmul(oa, ob) + c0
+      bound = E.gemm_bound(ref, 0.75 * np.matmul(np.abs(oa), np.abs(ob)), k, dtype, c0=c0, c_f32=bool(c_f32))
+      w = E.assert_elementwise(host(C[:batch, :m, :n]), ref, bound, 'bgemm C ABI ta=%d tb=%d pad=%d' % (ta, tb, pad))
+      _ew_note('batched gemm C ABI', dname + ('>f32' if c_f32 else ''), w)
+      keep = torch.ones_like(C, dtype=torch.bool)
+      keep[:batch, :m, :n] = False
+      bits = torch.int32 if cdt == torch.float32 else torch.int16
+      assert torch.equal(C.view(bits)[keep], before.view(bits)[keep]), 'the padding of C changed (ta=%d tb=%d)' % (ta, tb)
+
+
+# ------------------------------------------------------------------------------------------------ row softmax
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('cols', [1, 63, 64, 100, 255, 256, 257, 4096, 4100])
+def test_softmax_kernels_elementwise(ops, cols, dname):
+  """tg_softmax_rows_fwd / _bwd / _bwd_bwd, five rows: scores scaled to a row range of about 4, 40 and 160 (the last under both
+  16-bit types' range), one all-equal row, one row of values about -1e4 (fp32; a plain row in 16 bit) -- one thread's worth of
+  columns, a partial wave, exactly / one more than a block, many trips with a tail.  Each kernel on the operands it reads
+  (the backwards take the stored p), every element inside u |ref| + 16 E32, E32 taken PER ROW: the absolute term of a row is
+  set by that row's own largest element, not by the largest of the five, so the small probabilities of the range-40 and
+  range-160 rows are not judged against the uniform row's scale."""
+  import twingan_amd.ops as O
+  dtype = EW_DTYPES[dname]
+  rng = np.random.RandomState(500 + cols)
+  s = rng.randn(5, cols)
+  for r, rg in enumerate((4.0, 40.0, 160.0)):
+    s[r] *= rg / max(np.ptp(s[r]), 1e-30) if cols > 1 else 1.0
+  s[3] = s[3, 0]
+  if dtype == torch.float32:
+    s[4] = -1e4 + s[4]
+  s = _round_dt(s, dtype)
+  dp, v = _round_dt(rng.randn(5, cols), dtype), _round_dt(rng.randn(5, cols), dtype)
+  p_in = _round_dt(E.softmax_kernels_reference(s, s, dp, v, np.float64)[0], dtype)      # the stored p the backwards read
+  r64 = E.softmax_kernels_reference(s, p_in, dp, v, np.float64)
+  r32 = E.softmax_kernels_reference(s, p_in, dp, v, np.float32)
+  sd, pd, dpd, vd = (to_dev(x, dtype) for x in (s, p_in, dp, v))
+  out = [torch.empty_like(sd) for _ in range(3)]
+  st, dt = torch.cuda.current_stream().cuda_stream, O._dt(sd)
+  O.call('tg_softmax_rows_fwd', sd.data_ptr(), out[0].data_ptr(), 5, cols, dt, st)
+  O.call('tg_softmax_rows_bwd', pd.data_ptr(), dpd.data_ptr(), out[1].data_ptr(), 5, cols, dt, st)
+  O.call('tg_softmax_rows_bwd_bwd', pd.data_ptr(), dpd.data_ptr(), vd.data_ptr(), out[2].data_ptr(), 5, cols, dt, st)
+  for got, a64, a32, nm in zip(out, r64, r32, ('fwd', 'bwd', 'bwd_bwd')):
+    e32_row = np.abs(a32.astype(np.float64) - a64).max(-1, keepdims=True)
+    w = E.assert_elementwise(host(got), a64, E.e32_bound(a64, e32_row, dtype), 'softmax %s cols %d' % (nm, cols))
+    _ew_note('softmax ' + nm, dname, w)
+
+
+# ------------------------------------------------------------------------------------------------ losses
+LOSS_SHAPES = [(1, 1, 1, 1), (2, 5, 5, 3), (3, 5, 5, 3), (1, 4099, 1, 1), (16, 256, 256, 3)]
+LOSS_BIG = 16 * 256 * 256 * 3
+
+
+def _spike_positions(numel, dtype):
+  """The elements a broken index would drop or double: the first and last element, the vector tail, and the first and last
+  element of every workgroup's 256 vectors in every grid-stride trip (a trip is a whole number of workgroups, so these are the
+  same positions at every workgroup cap) -- of its 256 ELEMENTS where the length is no multiple of the vector width, the case
+  in which a per-sample sum takes the scalar loop."""
+  V = 4 if dtype == torch.float32 else 8
+  nvec = numel // V
+  first, efirst = np.arange(0, nvec, 256), np.arange(0, numel if numel % V else 0, 256)
+  idx = np.unique(np.concatenate([np.array([0, numel - 1]), np.arange(nvec * V, numel), first * V,
+                                  np.minimum(first + 255, max(nvec - 1, 0)) * V + V - 1, efirst, efirst + 255]))
+  return idx[(idx >= 0) & (idx < numel)]
+
+
+def _spiked(rng, shape, dtype, per_sample=False, scale=1.0):
+  """Values in +-[0.5, 1) * scale with the elements of _spike_positions 1e3 times that (per sample for the per-sample sums)."""
+  x = (0.5 + 0.5 * rng.rand(*shape)) * np.where(rng.rand(*shape) < 0.5, -1.0, 1.0) * scale
+  flat = x.reshape(shape[0], -1) if per_sample else x.reshape(1, -1)
+  flat[:, _spike_positions(flat.shape[1], dtype)] *= 1e3
+  return _round_dt(x, dtype)
+
+
+@pytest.mark.parametrize('ordered', [False, True], ids=['plain', 'ordered'])
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('shape', LOSS_SHAPES, ids=['x'.join(map(str, s)) for s in LOSS_SHAPES])
+def test_loss_reductions_elementwise(ops, shape, dname, ordered):
+  """abs_diff_mean, mean and gradient_penalty at 1, 150, 225 (per = 75 with batch 3: samples that do not start on a 16-byte
+  boundary), 4099 (a vector tail) and 16 x 256 x 256 x 3 elements (more than one grid-stride trip at every workgroup cap: 1024
+  plain, 512 ordered, 64 per sample), in the plain route and the deterministic() ordered one.  The data is spiked where an
+  index fault would bite (_spike_positions).  Forward: |got - ref| <= L 2^-24 |scale| sum|terms| with L from the launch geometry;
+  gradients element by element; the ordered route twice, bit-identical."""
+  from twingan_amd import _lib
+  lib = _lib.load()
+  dtype = EW_DTYPES[dname]
+  numel = int(np.prod(shape))
+  rng = np.random.RandomState(numel % 9973 + 17 * ordered)
+  u = E.unit_roundoff(dtype)
+  # the geometry each route launches (csrc/reduce.hip, ops._scalar_sum_into): tg_sum / tg_abs_diff_sum cap 1024 and ONE workgroup
+  # for fp32; tg_sum_ordered cap 512 for every type; tg_sample_sumsq cap 64, one workgroup for fp32 and in deterministic mode
+  geo = (512, False) if ordered else (1024, None)
+  a = _spiked(rng, shape, dtype)
+  b = _round_dt(0.5 + 0.5 * rng.rand(*shape), dtype)
+  per = numel // shape[0]
+  g = _spiked(rng, shape, dtype, per_sample=True, scale=1.0 / np.sqrt(per))
+  was = lib.tg_set_deterministic(1 if ordered else 0)
+  try:
+    assert ops.deterministic() == ordered
+    runs = []
+    for _ in range(2 if ordered else 1):
+      ad, bd, gd = (to_dev(x, dtype).requires_grad_(True) for x in (a, b, g))
+      l1, l2, l3 = ops.abs_diff_mean(ad, bd, 0.1), ops.mean(ad, -1.0), ops.gradient_penalty(gd, 10.0)
+      (l1 * 3.0 + l2 * 0.5 + l3 * 2.0).backward()
+      runs.append((l1.clone(), l2.clone(), l3.clone(), ad.grad.clone(), bd.grad.clone(), gd.grad.clone()))
+    if ordered:
+      for x, y in zip(*runs):
+        assert torch.equal(x, y), 'the ordered route differs between two runs'
+  finally:
+    lib.tg_set_deterministic(was)
+  l1, l2, l3, ga, gb, gg = runs[0]
+  L, _ = E.reduction_chain(numel, dtype, geo[0], one_block=geo[1])
+  # abs_diff_mean: terms |a - b| (one fp32 subtraction each)
+  terms = np.abs(a - b)
+  bnd = E.reduction_bound(terms.sum(), L, 0.1 / numel, term_ops=1)
+  r1 = abs(l1.item() - 0.1 * terms.sum() / numel) / bnd
+  bnd2 = E.reduction_bound(np.abs(a).sum(), L, 1.0 / numel)
+  r2 = abs(l2.item() + a.sum() / numel) / bnd2
+  print('[loss sums] %s %s numel %d: L %d, ratios abs_diff %.3f mean %.3f' % (dname, 'ordered' if ordered else 'plain', numel, L, r1, r2))
+  assert r1 <= 1.0 and r2 <= 1.0, (r1, r2)
+  _ew_note('loss sums ' + ('ordered' if ordered else 'plain'), dname, max(r1, r2))
+  if numel > 1:
+    # the test's own power: ONE spiked element dropped or doubled moves either sum by more than its bound (the exception: the
+    # fp32 plain route sums 3 M elements in ONE workgroup, a chain of 12 K additions whose worst case exceeds one spike)
+    # -- there a single-element index fault of the fp32 plain route is NOT detectable by the sum; the 16-bit types and the ordered
+    # route, which run the same sum_kernel template over the same indices, are what pins its indexing at that size).  The
+    # same for |a - b|, whose spiked terms are at least |a| - 1
+    spike = np.abs(a).max() / 2.0 / numel
+    spike1 = 0.1 * (np.abs(a).max() - 1.0) / 2.0 / numel
+    assert (spike > bnd2 and spike1 > bnd) or (dname == 'f32' and not ordered and numel == LOSS_BIG), (spike, bnd2, spike1, bnd)
+  # gradients: 3 k sign(a - b) and 0.5 k': the weight as a C float, its product with the incoming gradient, then the store
+  # (3 2^-24 + u of each term); a's gradient is the stored sum of its two stored terms (u of the sum)
+  sgn, t1, t2 = np.sign(a - b), 0.3 / numel, 0.5 / numel
+  one = lambda m: (u + 3 * E.U32) * m + E.tiny(dtype)
+  ra = t1 * sgn - t2
+  _ew_note('loss gradients', dname, E.assert_elementwise(host(ga).reshape(shape), ra, one(t1) + one(t2) + u * np.abs(ra) + E.tiny(dtype),
+                                                         'abs_diff_mean + mean, d a'))
+  _ew_note('loss gradients', dname, E.assert_elementwise(host(gb).reshape(shape), -t1 * sgn, one(t1), 'abs_diff_mean, d b'))
+  # gradient penalty: per-sample sums of squares (an fmaf per term), the scalar tail, coef[b] x g
+  Ls, _ = E.reduction_chain(per, dtype, 64, vec=(shape[0] == 1 or per % (4 if dtype == torch.float32 else 8) == 0),
+                            one_block=True if ordered else None)
+  ss = (g.reshape(shape[0], -1) ** 2).sum(1)
+  (loss, coef), (b_loss, b_coef) = E.gp_penalty_bounds(ss, Ls, 10.0)
+  r3 = abs(l3.item() - loss) / b_loss
+  print('[loss sums] gradient penalty: L %d ratio %.3f' % (Ls, r3))
+  assert r3 <= 1.0, (l3.item(), loss, b_loss)
+  _ew_note('gradient penalty', dname, r3)
+  cb = (1,) * (len(shape) - 1)
+  ref = 2.0 * coef.reshape((-1,) + cb) * g
+  bound = 2.0 * b_coef.reshape((-1,) + cb) * np.abs(g) + (u + 3 * E.U32) * np.abs(ref) + E.tiny(dtype)
+  _ew_note('gradient penalty grad', dname, E.assert_elementwise(host(gg).reshape(shape), ref, bound, 'gradient penalty d g'))
+
+
+@pytest.mark.parametrize('ordered', [False, True], ids=['plain', 'ordered'])
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('numel', [1, 4099, 300001])
+def test_loss_sums_of_a_view_off_the_16_byte_boundary(ops, numel, dname, ordered):
+  """mean and abs_diff_mean of contiguous views that start ONE element into their buffers (_chk asks for contiguity only): the
+  base pointers of tg_sum, tg_abs_diff_sum and tg_sum_ordered are then 2 or 4 bytes off a 16-byte boundary, and the entry
+  points must send every element through the scalar loop (sum_kernel's vec = 0) -- reduction_chain(vec=False) is the chain
+  that launch has.  One element, several workgroups, and 300001 elements (several grid-stride trips of the scalar loop).
+  Also a alone off the boundary with b on it: the condition is on BOTH operands.  abs_diff_mean's gradients element-wise."""
+  from twingan_amd import _lib
+  lib = _lib.load()
+  dtype = EW_DTYPES[dname]
+  rng = np.random.RandomState(numel % 9973 + 31 * ordered)
+  u = E.unit_roundoff(dtype)
+  a = _spiked(rng, (numel,), dtype)
+  b = _round_dt(0.5 + 0.5 * rng.rand(numel), dtype)
+  abuf, bbuf = (torch.full((numel + 1,), float('nan'), dtype=dtype, device=dev()) for _ in range(2))
+  abuf[1:], bbuf[1:] = to_dev(a, dtype), to_dev(b, dtype)
+  av, bv, b0 = abuf[1:].requires_grad_(True), bbuf[1:].requires_grad_(True), to_dev(b, dtype)
+  assert av.is_contiguous() and av.data_ptr() % 16 != 0 and bv.data_ptr() % 16 != 0 and b0.data_ptr() % 16 == 0
+  was = lib.tg_set_deterministic(1 if ordered else 0)
+  try:
+    runs = []
+    for _ in range(2 if ordered else 1):
+      l1, l2, l4 = ops.abs_diff_mean(av, bv, 0.1), ops.mean(av, -1.0), ops.abs_diff_mean(av, b0, 0.1)
+      ga, gb = torch.autograd.grad(l1 * 3.0, (av, bv))
+      runs.append((l1.clone(), l2.clone(), l4.clone(), ga, gb))
+    if ordered:
+      for x, y in zip(*runs):
+        assert torch.equal(x, y), 'the ordered route differs between two runs'
+  finally:
+    lib.tg_set_deterministic(was)
+  l1, l2, l4, ga, gb = runs[0]
+  L, _ = E.reduction_chain(numel, dtype, 512 if ordered else 1024, vec=False, one_block=False if ordered else None)
+  terms = np.abs(a - b)
+  bnd1 = E.reduction_bound(terms.sum(), L, 0.1 / numel, term_ops=1)
+  bnd2 = E.reduction_bound(np.abs(a).sum(), L, 1.0 / numel)
+  r1 = abs(l1.item() - 0.1 * terms.sum() / numel) / bnd1
+  r4 = abs(l4.item() - 0.1 * terms.sum() / numel) / bnd1
+  r2 = abs(l2.item() + a.sum() / numel) / bnd2
+  print('[loss sums] unaligned %s %s numel %d: L %d, ratios abs_diff %.3f (a alone off: %.3f) mean %.3f'
+        % (dname, 'ordered' if ordered else 'plain', numel, L, r1, r4, r2))
+  assert r1 <= 1.0 and r2 <= 1.0 and r4 <= 1.0, (r1, r2, r4)
+  _ew_note('loss sums unaligned ' + ('ordered' if ordered else 'plain'), dname, max(r1, r2, r4))
+  if numel > 1:      # one spiked element dropped or doubled moves either sum by more than its bound
+    spike = np.abs(a).max() / 2.0
+    assert spike / numel > bnd2 and 0.1 * spike / numel > bnd1, (spike, bnd1, bnd2)
+  sgn, t1 = np.sign(a - b), 0.3 / numel
+  one = (u + 3 * E.U32) * t1 + E.tiny(dtype)
+  E.assert_elementwise(host(ga), t1 * sgn, one, 'abs_diff_mean of views, d a')
+  E.assert_elementwise(host(gb), -t1 * sgn, one, 'abs_diff_mean of views, d b')
+  assert bool(torch.isnan(abuf[0])) and bool(torch.isnan(bbuf[0]))
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+def test_gradient_penalty_of_an_all_zero_sample(ops, dname):
+  """One all-zero sample in the batch: slope = 0, where the literal formula's gradient 2 lambda (slope - 1) g / (slope batch)
+  is 0 / 0.  The kernel's `slope > 0` guard makes that sample's coefficient -- and gradient -- 0: loss
+  and gradient finite, the loss counts (0 - 1)^2 for the sample, its gradient is exactly 0, the others' are right."""
+  dtype = EW_DTYPES[dname]
+  rng = np.random.RandomState(77)
+  g = _round_dt(rng.randn(3, 5, 5, 3) * 0.1, dtype)
+  g[1] = 0.0
+  gd = to_dev(g, dtype).requires_grad_(True)
+  l = ops.gradient_penalty(gd, 10.0)
+  l.backward()
+  gr = host(gd.grad)
+  assert np.isfinite(l.item()) and np.all(np.isfinite(gr)) and np.all(gr[1] == 0.0)
+  L, _ = E.reduction_chain(75, dtype, 64, vec=False)
+  (loss, coef), (b_loss, b_coef) = E.gp_penalty_bounds((g.reshape(3, -1) ** 2).sum(1), L, 10.0)
+  assert coef[1] == 0.0 and abs(l.item() - loss) <= b_loss
+  ref = coef.reshape(3, 1, 1, 1) * g
+  bound = b_coef.reshape(3, 1, 1, 1) * np.abs(g) + (E.unit_roundoff(dtype) + 3 * E.U32) * np.abs(ref) + E.tiny(dtype)
+  E.assert_elementwise(gr, ref, bound, 'gradient penalty with a zero sample')
+
+
+# ------------------------------------------------------------------------------------------------ Adam
+@pytest.mark.parametrize('numel', [1, 255, 257, 5000000])
+def test_adam_step_elementwise(numel):
+  """tg_adam_tick + tg_adam_step, ten steps: grad_scale = 1 / 1024 on gradients multiplied by 1024, the rate read from the device
+  pointer, a shadow buffer; elements with g = 0 throughout, |g| = 1e4, |g| = 1e-20 (v is subnormal in fp32), theta = 0 (where
+  nothing hides the update behind theta's own rounding).  After EVERY step theta, m and v are inside the bounds of
+  elementwise.adam_step_bounds -- one step in float64 from the fp32 state the launch read -- and the shadow equals the
+  round-to-nearest-even bfloat16 of the theta the kernel stored, bit for bit.  One element, a partial / just over one
+  workgroup, and 5 M elements (more than the 4096-workgroup cap: the grid-stride loop)."""
+  from twingan_amd._lib import call
+  gen = torch.Generator().manual_seed(numel % 1000)
+  ar = torch.arange(numel)
+  kind = ar % 4
+  scale = torch.where(kind == 1, 1e4, torch.where(kind == 2, 1e-20, torch.where(kind == 3, 0.0, 1.0))).double()
+  th0 = torch.randn(numel, generator=gen)
+  th0[ar % 8 == 0] = 0.0
+  thd, md, vd = th0.to(dev()), torch.zeros(numel, device=dev()), torch.zeros(numel, device=dev())
+  shadow = torch.full((numel,), 7.0, dtype=torch.bfloat16, device=dev())
+  step = torch.zeros(1, dtype=torch.int64, device=dev())
+  lr_t = torch.zeros(1, dtype=torch.float32, device=dev())
+  st = torch.cuda.current_stream().cuda_stream
+  worst = [0.0, 0.0, 0.0]
+  for t in range(1, 11):
+    gdev = (torch.randn(numel, generator=gen).double() * scale * 1024.0).float().to(dev())
+    prev = [x.double().cpu().numpy() for x in (thd, gdev, md, vd)]
+    call('tg_adam_tick', step.data_ptr(), lr_t.data_ptr(), 1e-4, 0.5, 0.99, st)
+    call('tg_adam_step', thd.data_ptr(), gdev.data_ptr(), md.data_ptr(), vd.data_ptr(), shadow.data_ptr(), numel, 0.0,
+         lr_t.data_ptr(), 0.5, 0.99, 1e-8, 1.0 / 1024.0, st)
+    assert int(step.item()) == t
+    want_lr = 1e-4 * np.sqrt(1 - float(np.float32(0.99)) ** t) / (1 - 0.5 ** t)
+    assert abs(lr_t.item() - want_lr) <= 2 * E.U32 * want_lr
+    refs, bounds = E.adam_step_bounds(*prev, lr_t.item(), 0.5, 0.99, 1e-8, 1.0 / 1024.0)
+    for i, (got, nm) in enumerate(((thd, 'theta'), (md, 'm'), (vd, 'v'))):
+      worst[i] = max(worst[i], E.assert_elementwise(got.double().cpu().numpy(), refs[i], bounds[i], 'adam %s step %d' % (nm, t)))
+    assert torch.equal(shadow.view(torch.int16), thd.to(torch.bfloat16).view(torch.int16)), 'shadow != bf16(theta) at step %d' % t
+  if numel >= 255:
+    assert bool((md[kind.to(dev()) == 3] == 0).all()) and bool((thd[kind.to(dev()) == 3] == th0.to(dev())[kind.to(dev()) == 3]).all())
+  for w, nm in zip(worst, ('theta', 'm', 'v')):
+    _ew_note('adam ' + nm, 'f32', w)

@@ -422,13 +422,14 @@ __global__ __launch_bounds__(NTHR) void mbstd_bwd_bwd_kernel(const T* __restrict
 // reductions
 // ------------------------------------------------------------------------------------------------
 // MODE 0: sum(x)  1: sum|x-y|;  PART: out[blockIdx.x] = this workgroup's sum;  direct (a ONE-workgroup launch that does not
-// accumulate): out[0] is written, not added to -- the launch needs no zero fill before it
+// accumulate): out[0] is written, not added to -- the launch needs no zero fill before it;  vec = 0: an operand does not
+// start on a 16-byte boundary (a view into a larger buffer), every element takes the scalar loop
 template <typename T, int MODE, bool PART = false>
 __global__ void sum_kernel(const T* __restrict__ x, const T* __restrict__ y, float* __restrict__ out, int64_t numel,
-                           float scale, int direct = 0) {
+                           float scale, int direct = 0, int vec = 1) {
   __shared__ float red[8];
   constexpr int V = Vec16<T>::N;
-  const int64_t nvec = numel / V, stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nvec = vec ? numel / V : 0, stride = (int64_t)gridDim.x * blockDim.x;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
     Vec16<T> a = ldv(x + i * V);
@@ -472,13 +473,14 @@ __global__ void abs_diff_bwd_kernel(const T* __restrict__ a, const T* __restrict
   }
 }
 
-// out[b] = sum over sample b of x^2;  grid = (chunks, batch), out pre-zeroed
+// out[b] = sum over sample b of x^2;  grid = (chunks, batch), out pre-zeroed;  vec = 0: x + b * per is not 16-byte aligned
+// for every sample (per no multiple of the vector width, or x itself unaligned), every element takes the scalar loop
 template <typename T>
-__global__ void sample_sumsq_kernel(const T* __restrict__ x, float* __restrict__ out, int64_t per) {
+__global__ void sample_sumsq_kernel(const T* __restrict__ x, float* __restrict__ out, int64_t per, int vec) {
   __shared__ float red[8];
   constexpr int V = Vec16<T>::N;
   const T* base = x + (int64_t)blockIdx.y * per;
-  const int64_t nvec = per / V, stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nvec = vec ? per / V : 0, stride = (int64_t)gridDim.x * blockDim.x;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
     Vec16<T> a = ldv(base + i * V);
@@ -825,7 +827,8 @@ int tg_sum(const void* x, float* out, int64_t numel, float scale, int accumulate
       int rc = zero_unless(out, sizeof(float), accumulate, s, "tg_sum");
       if (rc) return rc;
     }
-    hipLaunchKernelGGL((sum_kernel<T, 0>), dim3(blocks), dim3(256), 0, s, (const T*)x, (const T*)nullptr, out, numel, scale, direct);
+    hipLaunchKernelGGL((sum_kernel<T, 0>), dim3(blocks), dim3(256), 0, s, (const T*)x, (const T*)nullptr, out, numel, scale, direct,
+                       tg_aligned16(x));
   });
   TG_LAUNCH_CHECK("tg_sum");
   return TG_OK;
@@ -842,7 +845,8 @@ int tg_abs_diff_sum(const void* a, const void* b, float* out, int64_t numel, flo
       int rc = zero_unless(out, sizeof(float), accumulate, s, "tg_abs_diff_sum");
       if (rc) return rc;
     }
-    hipLaunchKernelGGL((sum_kernel<T, 1>), dim3(blocks), dim3(256), 0, s, (const T*)a, (const T*)b, out, numel, scale, direct);
+    hipLaunchKernelGGL((sum_kernel<T, 1>), dim3(blocks), dim3(256), 0, s, (const T*)a, (const T*)b, out, numel, scale, direct,
+                       tg_aligned16(a) && tg_aligned16(b));
   });
   TG_LAUNCH_CHECK("tg_abs_diff_sum");
   return TG_OK;
@@ -859,9 +863,11 @@ int tg_sum_ordered(const void* x, const void* y_or_null, float* out, int64_t num
     blocks = tg_grid_for(numel / Vec16<T>::N + 1, 256, 512);
     if ((size_t)blocks > ws_floats) blocks = (int)ws_floats;
     if (y_or_null)
-      hipLaunchKernelGGL((sum_kernel<T, 1, true>), dim3(blocks), dim3(256), 0, s, (const T*)x, (const T*)y_or_null, ws, numel, 1.f);
+      hipLaunchKernelGGL((sum_kernel<T, 1, true>), dim3(blocks), dim3(256), 0, s, (const T*)x, (const T*)y_or_null, ws, numel, 1.f, 0,
+                         tg_aligned16(x) && tg_aligned16(y_or_null));
     else
-      hipLaunchKernelGGL((sum_kernel<T, 0, true>), dim3(blocks), dim3(256), 0, s, (const T*)x, (const T*)nullptr, ws, numel, 1.f);
+      hipLaunchKernelGGL((sum_kernel<T, 0, true>), dim3(blocks), dim3(256), 0, s, (const T*)x, (const T*)nullptr, ws, numel, 1.f, 0,
+                         tg_aligned16(x));
   });
   hipLaunchKernelGGL(ordered_scalar_sum_kernel, dim3(1), dim3(64), 0, s, ws, blocks, out, scale, accumulate);
   TG_LAUNCH_CHECK("tg_sum_ordered");
@@ -886,7 +892,9 @@ int tg_sample_sumsq(const void* x, float* out, int batch, int64_t per, int dtype
   if (rc) return rc;
   TG_DISPATCH_DTYPE(dtype, "tg_sample_sumsq", {
     const int chunks = exact_grid<T>() ? 1 : tg_grid_for(per / Vec16<T>::N + 1, 256, 64);
-    hipLaunchKernelGGL(sample_sumsq_kernel<T>, dim3(chunks, batch), dim3(256), 0, s, (const T*)x, out, per);
+    // sample b starts at x + b * per: on a 16-byte boundary for every b only when per is a multiple of the vector width
+    const int vec = tg_aligned16(x) && (batch == 1 || per % Vec16<T>::N == 0);
+    hipLaunchKernelGGL(sample_sumsq_kernel<T>, dim3(chunks, batch), dim3(256), 0, s, (const T*)x, out, per, vec);
   });
   TG_LAUNCH_CHECK("tg_sample_sumsq");
   return TG_OK;
