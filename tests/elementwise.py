@@ -650,3 +650,172 @@ def attention_family(name, n, ln, dk, rng, rnd):
     q[:, :, 0] = np.where(np.arange(ln) % 2 == 1, 4.0, -4.0)
   assert name in ATTENTION_FAMILIES, name
   return rnd(q), rnd(k)
+
+
+# ------------------------------------------------------------------------------------------------ spectral norm
+def sn_formulas(w2, u, G, dt):
+  """libs/sn.py:38-101 for one power iteration, literally, in torch dtype `dt` on the CPU (float64: the reference; float32:
+  its restatement for E32), the gradient by autograd with nothing stopped:
+      v_raw = u W^T,  v = l2n(v_raw),  u_raw = v W,  u' = l2n(u_raw),  sigma = v W u'^T,  W_bar = W / sigma,
+      l2n(x) = x / sqrt(max(sum x^2, 1e-12))                              (tf.nn.l2_normalize)
+  w2 [K, cout], u [1, cout], G = d L / d W_bar [K, cout] -> dict of numpy float64 arrays: w_bar, u_new, v, stats = {sigma,
+  sqrt(max(|v_raw|^2, 1e-12))} (what the kernel saves for its backward), gw, and the float64 pieces of the gradient's
+  magnitude (sigma, s = sum G o W, b = (a - v (v . a)) / |v_raw| with a = W u'^T)."""
+  import torch
+  w = w2.detach().to(dt).clone().requires_grad_(True)
+  ut, g = u.detach().to(dt).reshape(1, -1), G.detach().to(dt)
+  l2n = lambda x: x / x.pow(2).sum().clamp_min(1e-12).sqrt()
+  v_raw = ut @ w.t()
+  v = l2n(v_raw)
+  u1 = l2n(v @ w)
+  sigma = (v @ w @ u1.t()).reshape(())
+  w_bar = w / sigma
+  gw, = torch.autograd.grad((w_bar * g).sum(), w)
+  nv = v_raw.pow(2).sum().clamp_min(1e-12).sqrt()
+  a = w.detach() @ u1.detach().t()                                   # [K, 1]
+  vd = v.detach().t()                                                # [K, 1]
+  b = (a - vd * (vd * a).sum()) / nv.detach()
+  f = lambda t: t.detach().double().numpy()
+  return dict(w_bar=f(w_bar), u_new=f(u1).reshape(-1), v=f(v).reshape(-1), stats=np.array([float(sigma.detach()), float(nv.detach())]), gw=f(gw),
+              sigma=float(sigma.detach()), s=float((g * w.detach()).sum()), b=f(b).reshape(-1))
+
+
+def sn_bounds(w2, u, G):
+  """tg_spectral_norm_fwd / _bwd (csrc/sn.hip): every output ends in a division by a norm and has no product structure, so
+  the normaliser convention: e32_bound(ref, E, 'f32') = 2^-24 |ref| + 16 E + 2^-126 with, per output,
+      E = max(max |float32 restatement - float64|, 2^-24 max(mag))
+  of the literal formulas (sn_formulas) by torch on the CPU.  The floor: the float32 restatement can be EXACT where the
+  kernel is not -- for cout = 1, u' = x / sqrt(x^2) is +-1 in any precision while the kernel's rsqrtf is one unit off; for a
+  1 x 1 matrix the gradient cancels to exactly 0 in both -- and one fp32 rounding of the largest intermediate is the least
+  any fp32 evaluation owes.  mag:
+      w_bar, u', v, stats    |ref|
+      gw                     the sum of the absolute summands of  G / sigma - (s / sigma^2) (v (x) u' + b (x) u):
+                             |G| / sigma + |s| / sigma^2 (|v (x) u'| + |b (x) u|),   s = sum G o W, b = (a - v (v . a)) / |v_raw|
+  m = 16 as for the normalisers: torch's float32 sums are pairwise, the kernels' are lane-strided fmaf chains of up to
+  cout / 64 (rows) and K / 64 (columns) terms that meet in a butterfly and a two-stage sum in a fixed order.
+  The saved v and stats = {sigma, |v_raw|} are checked too: a wrong stats[1] shows only in the b term of the gradient, which
+  vanishes at a converged u.
+  -> (ref, bound): dicts over w_bar, u_new, v, stats, gw (numpy float64)."""
+  import torch
+  r64, r32 = sn_formulas(w2, u, G, torch.float64), sn_formulas(w2, u, G, torch.float32)
+  sig, s = r64['sigma'], r64['s']
+  ud = u.detach().double().numpy().reshape(-1)
+  mag = {k: np.abs(r64[k]) for k in ('w_bar', 'u_new', 'v', 'stats')}
+  mag['gw'] = np.abs(G.detach().double().numpy()) / abs(sig) + abs(s) / sig ** 2 * (
+      np.abs(np.outer(r64['v'], r64['u_new'])) + np.abs(np.outer(r64['b'], ud)))
+  bound = {}
+  for k in mag:
+    E = max(e32(r32[k], r64[k]), U32 * float(mag[k].max()))
+    bound[k] = e32_bound(r64[k], E, 'f32')
+  return {k: r64[k] for k in mag}, bound
+
+
+def sn_bwd_closed_form(G, W, u, u_new, v, stats, dt=np.float64):
+  """The backward kernel's own closed form from the operands it READS (sn.hip's header comment), numpy dtype `dt`:
+      gw = G / sigma - (s / sigma^2) (v (x) u' + b (x) u),  s = sum G o W,  a = W u'^T,  b = (a - v (v . a)) / stats[1]."""
+  G, W, u, u_new, v, stats = (np.asarray(x, dt) for x in (G, W, u, u_new, v, stats))
+  sigma, nv = stats[0], stats[1]
+  a = W @ u_new
+  b = (a - v * (v * a).sum(dtype=dt)) / nv
+  s = (G * W).sum(dtype=dt)
+  return G / sigma - (s / (sigma * sigma)) * (np.outer(v, u_new) + np.outer(b, u))
+
+
+# ------------------------------------------------------------------------------------------------ the loss tail
+def cosine_formulas(e, p, weight, gin, dt):
+  """tf.losses.cosine_distance(l2n(expected), l2n(embedding), axis=-1, weights=w) as csrc/reduce.hip documents it, in torch dtype
+  `dt` on the CPU: out = (w / B) sum_b (1 - e_b . p_b rsqrt(max(|e_b|^2, 1e-12)) rsqrt(max(|p_b|^2, 1e-12))); the gradient towards
+  p by autograd times the incoming gradient `gin` -- the clamp's own derivative is 0, so below it phat = p 1e6 is linear in p.
+  -> dict(out, gp [B, D], rows [B] = 1 - cos_b, cos [B]) as numpy float64."""
+  import torch
+  et, pt = e.detach().to(dt), p.detach().to(dt).clone().requires_grad_(True)
+  ie = torch.rsqrt((et * et).sum(1).clamp_min(1e-12))
+  ip = torch.rsqrt((pt * pt).sum(1).clamp_min(1e-12))
+  cos = (et * pt).sum(1) * ie * ip
+  rows = 1.0 - cos
+  out = rows.sum() * (weight / e.shape[0])
+  gp, = torch.autograd.grad(out * gin, pt)
+  f = lambda t: t.detach().double().numpy()
+  return dict(out=float(out.detach()), gp=f(gp), rows=f(rows), cos=f(cos))
+
+
+def cosine_bounds(e, p, weight, gin):
+  """cosine_distance_fwd_kernel / _bwd_kernel.  Forward: the b row terms 1 - cos_b, each an operation without product
+  structure (three fmaf chains, two rsqrtf) -> e32_bound of a row with E = max(max_b |float32 - float64|, 2^-24 max_b (1 +
+  |cos_b|)) (the floor: where p = 3 e the float32 restatement can return exactly 0), summed in row order by one thread (b
+  additions) and scaled once: reduction_bound(sum |rows|, L = b + 1, w / B).  Backward, per element: e32_bound with E per row,
+  floored at 2^-24 |k| / max(|p_b|, 1e-6), k = w gin / B: the two summands ehat / |p| and phat cos / |p| are each of that
+  size and cancel where p is parallel to e.  -> (ref, b_out, b_gp)."""
+  import torch
+  r64, r32 = cosine_formulas(e, p, weight, gin, torch.float64), cosine_formulas(e, p, weight, gin, torch.float32)
+  b = e.shape[0]
+  scale = weight / b
+  E_row = max(e32(r32['rows'], r64['rows']), U32 * float((1.0 + np.abs(r64['cos'])).max()))
+  b_out = abs(scale) * float(e32_bound(r64['rows'], E_row, 'f32').sum()) + reduction_bound(np.abs(r64['rows']).sum(), b + 1, scale)
+  pn = np.maximum(np.sqrt((p.detach().double().numpy() ** 2).sum(1)), 1e-6)
+  E_g = np.maximum(np.abs(r32['gp'] - r64['gp']).max(1), U32 * abs(scale * gin) / pn)[:, None]
+  return r64, b_out, e32_bound(r64['gp'], E_g, 'f32')
+
+
+def pred_loss_reference(x, mode, a, b):
+  """pred_loss_f / pred_loss_df (csrc/reduce.hip) in float64 -> (f, df, |parts| of f summed, term_ops, sigmoid or None):
+      mode 1  relu(a + b x)         term_ops 2: the product, the addition (fmaxf is exact); derivative b where a + b x > 0, else
+                                    0 -- at a + b x = 0 exactly it is 0, as tf.nn.relu's
+      mode 2  max(x, 0) - x a + log1p(exp(-|x|))   term_ops 11: x a (1), the subtraction (1), expf one unit in the last place (2)
+                                    carried through log1p (d log1p(t) = dt / (1 + t) <= 2 (2^-24) t <= 4 (2^-24) log1p(t)), log1pf
+                                    itself (2), the addition (1)
+      mode 3  x^2                   term_ops 1"""
+  x = np.asarray(x, np.float64)
+  if mode == 1:
+    z = a + b * x
+    return np.maximum(z, 0.0), np.where(z > 0, b, 0.0), np.maximum(z, 0.0), 2, None
+  if mode == 2:
+    sp = np.log1p(np.exp(-np.abs(x)))
+    sig = np.where(x >= 0, 1.0 / (1.0 + np.exp(-np.abs(x))), np.exp(-np.abs(x)) / (1.0 + np.exp(-np.abs(x))))
+    return np.maximum(x, 0.0) - x * a + sp, sig - a, np.maximum(x, 0.0) + np.abs(x * a) + sp, 11, sig
+  if mode == 3:
+    return x * x, 2.0 * x, x * x, 1, None
+  return x, np.ones_like(x), np.abs(x), 0, None
+
+
+def pred_loss_fwd_bound(parts_sum, n, scale, term_ops, extra_ops=0):
+  """One 256-thread workgroup: ceil(n / 256) additions per thread, 6 butterfly levels, the 4 wave partials, the scale
+  multiply (+ extra_ops: what a caller's epilogue adds)."""
+  return reduction_bound(parts_sum, -(-n // 256) + 6 + 4 + 1 + extra_ops, scale, term_ops)
+
+
+def pred_loss_bwd_bound(ref, g_abs, sig, ops=4):
+  """gx = (gscale scale) df: per element ops 2^-24 |ref| + 2^-126 with the four fp32 operations g = gscale scale (1), df (2 x,
+  or b: at most 1), g df (1), and one for the scale's own conversion to float.  Mode 2 needs one more term, by derivation: df =
+  sigmoid(x) - label CANCELS where the sigmoid saturates (x = 20, label 1: the float64 difference is 2e-9, the fp32 one 0),
+  and the error of the sigmoid itself -- expf (2), 1 + e (1), the division (2), relative to sigmoid(x) -- does not shrink with
+  the difference: + 5 2^-24 |g| sigmoid(x)."""
+  bnd = ops * U32 * np.abs(ref) + TINY
+  return bnd if sig is None else bnd + 5.0 * U32 * g_abs * sig
+
+
+def dot_chain(numel):
+  """tg_dot (csrc/attention.hip): nparts = min(1024, ceil(numel / 16384)) workgroups of per = ceil(numel / nparts) elements:
+  ceil(per / 256) fmaf per thread (64 at 16384), 6 + 4 levels of the block sum; dot_final: ceil(nparts / 256) additions per
+  thread, 6 + 4 again.  -> (L, nparts, per)."""
+  nparts = min(1024, -(-numel // 16384))
+  per = -(-numel // nparts)
+  return -(-per // 256) + 10 + -(-nparts // 256) + 10, nparts, per
+
+
+def variance_bound(x, dtype, batch):
+  """ops.batch_variance = tg_sum, tg_sample_sumsq, tg_var_from_sums: E[x^2] - E[x]^2, clamped at 0.  The kernel FORMS that
+  difference, so no bound relative to the variance can hold (0.9 + 0.01 U: the variance is 1e-5 of E[x^2]); the bound is
+  relative to E[x^2]:  (L + 3) 2^-24 E[x^2] + 2^-126,
+      L = L_ss + 1 + L_b + 2 L_s:   L_ss the chain of one sample's sum of squares (cap 64; + 1: the fmaf that forms a term), L_b =
+      ceil(batch / 256) + 10 the sum over the samples in var_from_sums, L_s the chain of tg_sum (cap 1024) -- twice, for m^2 =
+      (sum / n)^2, with mean|x|^2 <= E[x^2];  3: the two multiplies by 1 / numel and the subtraction.
+  x: the STORED values (float64 numpy).  -> (var, bound, L)."""
+  numel = x.size
+  per = numel // batch
+  V = 4 if _name(dtype) in ('float32', 'f32') else 8
+  L_ss, _ = reduction_chain(per, dtype, 64, vec=(batch == 1 or per % V == 0))
+  L_s, _ = reduction_chain(numel, dtype, 1024)
+  L = L_ss + 1 + (-(-batch // 256) + 10) + 2 * L_s
+  ex2 = float((x * x).mean())
+  return max(ex2 - float(x.mean()) ** 2, 0.0), (L + 3) * U32 * ex2 + TINY, L

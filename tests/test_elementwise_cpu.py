@@ -716,3 +716,279 @@ def test_adam_bound_accepts_fp32_arithmetic_and_rejects_a_wrong_epsilon_placemen
         assert E.check_elementwise(th - lr_t * (b1 * m + (f(1) - b1) * g) / (np.sqrt(vi) + eps), rt, bt, 'no grad_scale')[1] is not None
         assert E.check_elementwise(b2 * m + (f(1) - b2) * gi, rm, bm, 'beta2 for m')[1] is not None
     th, m, v = t, mi, vi
+
+
+# ------------------------------------------------------------------------------------------------ spectral norm
+F32 = np.float32
+
+
+def sn_model(w, u, G, drop_cols_from=None, drop_last_split_row=False, drop_b=False, unclamped_nv=False):
+  """csrc/sn.hip in numpy float32 (sums by numpy: the order is not what the faults are about) with a planted fault:
+      drop_cols_from        sn_finish's ur[j] loop stops after j = 0: columns >= 256 of u_raw read 0
+      drop_last_split_row   sn_coldot's last K split (ks = 15) leaves its last row out
+      drop_b                the b (x) u term missing from the gradient
+      unclamped_nv          stats[1] = |v_raw| instead of sqrt(max(|v_raw|^2, 1e-12))
+  -> dict(w_bar, u_new, v, stats, gw)."""
+  w, u, G = F32(w), F32(u).reshape(-1), F32(G)
+  K, cout = w.shape
+  v_raw = w @ u
+  ss = F32((v_raw * v_raw).sum())
+  inv_v = F32(1.0) / np.sqrt(np.maximum(ss, F32(1e-12)))
+  rows = np.ones(K, bool)
+  per = -(-K // 16)
+  if drop_last_split_row and 15 * per < K:
+    rows[K - 1] = False
+  u_raw = (v_raw[rows] @ w[rows]) * inv_v
+  if drop_cols_from is not None:
+    u_raw[drop_cols_from:] = 0
+  ssu = F32((u_raw * u_raw).sum())
+  inv_u = F32(1.0) / np.sqrt(np.maximum(ssu, F32(1e-12)))
+  sigma = ssu * inv_u
+  u_new, v = u_raw * inv_u, v_raw * inv_v
+  nv = np.sqrt(ss) if unclamped_nv else F32(1.0) / inv_v
+  a = w @ u_new
+  b = np.zeros_like(a) if drop_b else (a - v * F32((v * a).sum())) / nv
+  s = F32((G * w).sum())
+  gw = G / sigma - (s / (sigma * sigma)) * (np.outer(v, u_new) + np.outer(b, u))
+  return dict(w_bar=w / sigma, u_new=u_new, v=v, stats=np.array([sigma, nv]), gw=gw)
+
+
+def _sn_case(K, cout, scale=0.1, converged=False, seed=5):
+  g = torch.Generator().manual_seed(seed)
+  w = (scale * torch.randn(K, cout, generator=g, dtype=torch.float64)).float()
+  u = torch.randn(1, cout, generator=g, dtype=torch.float64)
+  if converged == 'svd':
+    u = torch.linalg.svd(w.double())[2][:1]
+  elif converged:
+    l2n = lambda x: x / x.norm()
+    for _ in range(30):
+      u = l2n(l2n(u @ w.double().t()) @ w.double())
+  return w, u.float(), torch.randn(K, cout, generator=g)
+
+
+def sn_guard_today(got, ref):
+  """test_spectral_norm_matches_oracle as it stands: rel-L2 < 2e-5 on w_bar and u', < 1e-4 on the gradient."""
+  return rel_l2(got['w_bar'], ref['w_bar']) < 2e-5 and rel_l2(got['u_new'], ref['u_new']) < 2e-5 and rel_l2(got['gw'], ref['gw']) < 1e-4
+
+
+def _sn_rejects(got, ref, bound, keys=('w_bar', 'u_new', 'v', 'stats', 'gw')):
+  return [k for k in keys if E.check_elementwise(got[k], ref[k], bound[k], k)[1] is not None]
+
+
+SN_OLD = [(144, 32), (3, 16), (1024, 64), (2376, 256), (45, 7)]      # test_spectral_norm_matches_oracle's five, as [K, cout]
+
+
+def test_planted_spectral_norm_faults():
+  """The clean numpy model is inside sn_bounds at every shape used here.  Then, per fault, what the new check and the old
+  guard (rel-L2 at the old five shapes, w ~ 0.1 N(0, 1), a random u) make of it:
+    columns >= 256 of u_raw dropped     old shapes have cout <= 256: the faulty model returns the SAME BITS there -- no guard can see
+                                        it; at cout = 257 u'[256] = 0 is outside its bound (rel-L2 would see it at that shape too: the
+                                        gain is the shape)
+    last row of the last K split        rejected by both wherever split 15 is not empty (K = 144, 1024, 2376 of the old five):
+                                        the old guard was as sharp
+    b (x) u missing, random u           rejected by both
+    b (x) u missing, u after 30 iterations   a random 144 x 32 matrix has a small spectral gap: b is not yet 0, the gradient is
+                                        off by 7.7e-5 in rel-L2 -- UNDER the old 1e-4 -- and by 136 bounds element-wise: the one
+                                        arithmetic fault here that the old guard passes
+    b (x) u missing, u the singular vector   b = 0 up to rounding: NEITHER sees it -- which is why the random state stays in the test
+    stats[1] unclamped                  the same bits wherever |v_raw| >= 1e-6; below the clamp the saved stats (checked directly now,
+                                        never before) are outside their bound
+  For fp32 spectral norm the rel-L2 guard at 2e-5 is about as sharp as the bound (16 E32 is of the same order): what is new is
+  the shapes, the states and the entry points, not the arithmetic of the bound."""
+  for K, cout in SN_OLD + [(72, 257), (16, 129), (1, 1), (5, 1)]:
+    w, u, G = _sn_case(K, cout)
+    ref, bound = E.sn_bounds(w, u, G)
+    assert _sn_rejects(sn_model(w, u, G), ref, bound) == [], (K, cout)
+  # columns >= 256
+  for K, cout in SN_OLD:
+    w, u, G = _sn_case(K, cout)
+    a, b = sn_model(w, u, G), sn_model(w, u, G, drop_cols_from=256)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+  w, u, G = _sn_case(72, 257)
+  ref, bound = E.sn_bounds(w, u, G)
+  bad = sn_model(w, u, G, drop_cols_from=256)
+  assert 'u_new' in _sn_rejects(bad, ref, bound) and not sn_guard_today(bad, ref)
+  # last row of the last K split
+  seen_old = []
+  for K, cout in SN_OLD + [(16, 129)]:
+    w, u, G = _sn_case(K, cout)
+    ref, bound = E.sn_bounds(w, u, G)
+    bad = sn_model(w, u, G, drop_last_split_row=True)
+    hit = 15 * -(-K // 16) < K
+    assert bool(_sn_rejects(bad, ref, bound)) == hit and (not sn_guard_today(bad, ref)) == hit, (K, cout)
+    seen_old.append(hit)
+  assert seen_old == [True, False, True, True, False, True]
+  # b (x) u
+  w, u, G = _sn_case(144, 32)
+  ref, bound = E.sn_bounds(w, u, G)
+  bad = sn_model(w, u, G, drop_b=True)
+  assert _sn_rejects(bad, ref, bound) == ['gw'] and not sn_guard_today(bad, ref)
+  w, u, G = _sn_case(144, 32, converged=True)
+  ref, bound = E.sn_bounds(w, u, G)
+  bad = sn_model(w, u, G, drop_b=True)
+  assert _sn_rejects(bad, ref, bound) == ['gw'] and sn_guard_today(bad, ref) and 5e-5 < rel_l2(bad['gw'], ref['gw']) < 1e-4
+  w, u, G = _sn_case(144, 32, converged='svd')
+  ref, bound = E.sn_bounds(w, u, G)
+  bad = sn_model(w, u, G, drop_b=True)
+  assert _sn_rejects(bad, ref, bound) == [] and sn_guard_today(bad, ref)
+  # stats[1]
+  w, u, G = _sn_case(144, 32)
+  a, b = sn_model(w, u, G), sn_model(w, u, G, unclamped_nv=True)
+  assert all(np.array_equal(a[k], b[k]) for k in a)
+  w, u, G = _sn_case(144, 32, scale=1e-8 / (144 * 32) ** 0.5)
+  ref, bound = E.sn_bounds(w, u, G)
+  fwd = ('w_bar', 'u_new', 'v', 'stats')
+  assert ref['stats'][1] == 1e-6 and _sn_rejects(sn_model(w, u, G), ref, bound, fwd) == []
+  assert _sn_rejects(sn_model(w, u, G, unclamped_nv=True), ref, bound, fwd) == ['stats']
+
+
+def test_planted_spectral_norm_sink_and_job_table_faults():
+  """accumulate overwriting the sink: the sink holds gw (the last call's) and not sink0 + 2 gw -- outside the two-call bound at
+  every element where sink0 + gw is not ~ 0; no test asked before.  Job 17's blocks of the finish pass taking job 16's fin0: its
+  local block index is off by job 16's block count, so its first blocks of w_bar and (local block 0 never runs) u', v and stats
+  keep what the buffers held -- the bit-for-bit comparison with the one-kernel path fails; the old table had 6 jobs: no test."""
+  w, u, G = _sn_case(63, 17)
+  ref, bound = E.sn_bounds(w, u, G)
+  gw = sn_model(w, u, G)['gw']
+  sink0 = np.random.RandomState(1).randn(63, 17).astype(np.float32)
+  want = sink0.astype(np.float64) + 2.0 * ref['gw']
+  b2 = 2.0 * bound['gw'] + 2.0 * E.U32 * np.abs(want)
+  assert E.check_elementwise((sink0 + gw) + gw, want, b2, 'sink')[1] is None
+  worst, msg = E.check_elementwise(gw, want, b2, 'sink overwritten')
+  assert msg is not None and worst > 1e3
+  # the job table: fin0 = running total of ceil(K cout / 1024) blocks
+  sizes = [63 * 129, 1 * 1, 33 * 1024, 5 * 1] * 5
+  fin0 = np.concatenate([[0], np.cumsum([-(-s // 1024) for s in sizes])])
+  j = 17
+  w17 = np.random.RandomState(2).randn(sizes[j]).astype(np.float32)
+  out = np.full(sizes[j], -7.25, np.float32)      # what the buffer held
+  shift = int(fin0[j] - fin0[j - 1])                  # blockIdx - fin0[16] = local + shift
+  for blk in range(-(-sizes[j] // 1024)):
+    lo = (blk + shift) * 1024
+    out[lo:min(sizes[j], lo + 1024)] = w17[lo:min(sizes[j], lo + 1024)] * F32(0.5)
+  assert shift >= 1 and not np.array_equal(out, w17 * F32(0.5))
+
+
+# ------------------------------------------------------------------------------------------------ the loss tail
+def test_planted_loss_tail_faults():
+  """None of these entry points had an operator test ("no test" is the old guard throughout):
+    cosine backward without the clamped branch    (ehat - phat cos) / |p| below the clamp: outside the bound on the clamped family
+    pred_losses dividing by 256, not group_size   the same bits at group_size = 256, outside at 255 and 257
+    a hinge derivative taken with >=              differs only where a + b x = 0 exactly: the planted +-1
+    the wave GEMM kernel at k = 31                lanes 31..63 add terms from past the row: garbage of the operands' size
+    FC gb missing columns >= 64                   the same bits for n <= 64 (every listed shape); outside at n = 70
+    the dot product's last partial dropped        the same bits at one partial (the 132 elements of the old test); outside at 16385"""
+  rng = np.random.RandomState(8)
+  # cosine
+  e, p = torch.from_numpy(F32(rng.randn(3, 5))), torch.from_numpy(F32(rng.randn(3, 5) * 1e-8))
+  ref, _, b_gp = E.cosine_bounds(e, p, 0.7, 2.5)
+  en, pn = e.double().numpy(), p.double().numpy()
+  ie, ip = 1 / np.sqrt((en * en).sum(1, keepdims=True)), 1e6
+  k = -0.7 * 2.5 / 3
+  clean = k * (en * ie) * ip
+  assert E.check_elementwise(F32(clean), ref['gp'], b_gp, 'clamped branch')[1] is None
+  cos = (en * pn).sum(1, keepdims=True) * ie * ip
+  assert E.check_elementwise(F32(k * (en * ie - pn * ip * cos) * ip), ref['gp'], b_gp, 'no clamped branch')[1] is not None
+  # pred_losses / 256
+  for gs, same in ((255, False), (256, True), (257, False)):
+    x = F32(rng.randn(gs) * 4).astype(np.float64)
+    f, df, parts, term_ops, _ = E.pred_loss_reference(x, 1, 1.0, -1.0)
+    bound = E.pred_loss_fwd_bound(parts.sum(), gs, 0.5 / gs, term_ops, extra_ops=3)
+    assert abs(F32(0.5 * f.sum() / gs) - 0.5 * f.sum() / gs) <= bound
+    assert (abs(F32(0.5 * f.sum() / 256) - 0.5 * f.sum() / gs) <= bound) == same
+  # hinge >=
+  x = np.array([0.5, 1.0, 3.0, -1.0])
+  f, df, _, _, _ = E.pred_loss_reference(x, 1, 1.0, -1.0)
+  g = 0.25
+  wrong = g * np.where(1.0 - x >= 0, -1.0, 0.0)
+  assert E.check_elementwise(g * df, g * df, E.pred_loss_bwd_bound(g * df, g, None), 'hinge')[1] is None
+  w, msg = E.check_elementwise(wrong, g * df, E.pred_loss_bwd_bound(g * df, g, None), 'hinge >=')
+  assert msg is not None and 'd0 1..1' in msg
+  # wave kernel at k = 31
+  a, b = F32(rng.randn(3, 31)).astype(np.float64), F32(rng.randn(31, 5)).astype(np.float64)
+  ref_c = a @ b
+  bound = E.conv_bound(ref_c, np.abs(a) @ np.abs(b), 31, 'f32')
+  assert E.check_elementwise(F32(ref_c), ref_c, bound, 'gemm')[1] is None
+  garbage = (rng.randn(3, 33) @ rng.randn(33, 5))
+  assert E.check_elementwise(F32(ref_c + garbage), ref_c, bound, 'gemm lanes >= k')[1] is not None
+  # FC gb
+  for n, same in ((16, True), (64, True), (70, False)):
+    gq = F32(rng.randn(3, n)).astype(np.float64)
+    rgb = gq.sum(0)
+    got = F32(rgb).copy()
+    got[64:] = 0
+    assert (E.check_elementwise(got, rgb, E.wgrad_bound(rgb, np.abs(gq).sum(0), 3), 'fc gb')[1] is None) == same
+  # dot
+  for numel, same in ((132, True), (16385, False)):
+    x, y = F32(rng.randn(numel)).astype(np.float64), F32(rng.randn(numel)).astype(np.float64)
+    x[-1], y[-1] = 3.0, 3.0
+    L, nparts, per = E.dot_chain(numel)
+    bound = E.reduction_bound(np.abs(x * y).sum(), L, term_ops=1)
+    kept = (x * y)[:(nparts - 1) * per].sum() if nparts > 1 else (x * y).sum()
+    assert abs(F32((x * y).sum()) - (x * y).sum()) <= bound and (abs(kept - (x * y).sum()) <= bound) == same
+
+
+# ------------------------------------------------------------------------------------------------ preprocessing
+def test_planted_preprocessing_faults(monkeypatch):
+  """The oracle with a fault planted, against the clean oracle under the new test's bound (3e-6 in fp32), and what the old checks
+  (tests/test_gpu_data.py: max-abs < 2e-6 / 3e-6, sources at least as large as the target, hw = 32 / 256, random pixels) make of it:
+    bot / right not clamped       a tap past the rectangle reads the zero padding.  Down-sampling (scale >= 1) never reaches it:
+                                  the same values at the old sizes.  A 1 x 1 source up-sampled to 5 x 5 goes dark: rejected
+    the flip applied to the source, not to the resized image
+                                  bilinear without half-pixel centres is not mirror-symmetric: rejected, and by the old check too
+                                  (its fixture has flips); with a crop rectangle, which the old batch tests did not flip, as well
+    saturate dividing by s = 0    NaN on grey, black and white pixels; random pixels are never exactly grey: the old inputs do not
+                                  reach it, the grey / black / white sources do
+    a ragged last workgroup not written
+                                  hw = 32 and 256 are multiples of 256 pixels: nothing ragged; at hw = 33 the last 65 pixels keep the
+                                  buffer's fill"""
+  rng = np.random.RandomState(4)
+  real = N.resize_bilinear_tf1
+
+  def unclamped(x, out_h, out_w):
+    h, w = x.shape[:2]
+    pad = np.zeros((h + 1, w + 1, x.shape[2]))
+    pad[:h, :w] = x
+    fy = np.arange(out_h, dtype=np.float32) * (np.float32(h) / np.float32(out_h))
+    fx = np.arange(out_w, dtype=np.float32) * (np.float32(w) / np.float32(out_w))
+    top, left = np.floor(fy).astype(int), np.floor(fx).astype(int)
+    ly = (fy - top.astype(np.float32)).astype(np.float64)[:, None, None]
+    lx = (fx - left.astype(np.float32)).astype(np.float64)[None, :, None]
+    t = pad[top][:, left] + (pad[top][:, left + 1] - pad[top][:, left]) * lx
+    b = pad[top + 1][:, left] + (pad[top + 1][:, left + 1] - pad[top + 1][:, left]) * lx
+    return t + (b - t) * ly
+
+  big, dot = rng.randint(0, 256, (48, 70, 3), dtype=np.uint8), rng.randint(1, 256, (1, 1, 3), dtype=np.uint8)
+  want_big, want_dot = N.preprocess_image(big, 32, 'RESHAPE', False), N.preprocess_image(dot, 5, 'RESHAPE', False)
+  monkeypatch.setattr(N, 'resize_bilinear_tf1', unclamped)
+  assert np.abs(N.preprocess_image(big, 32, 'RESHAPE', False) - want_big).max() < 2e-6      # the old check passes
+  got = N.preprocess_image(dot, 5, 'RESHAPE', False)
+  monkeypatch.setattr(N, 'resize_bilinear_tf1', real)
+  assert E.check_elementwise(got, want_dot, 3e-6, 'unclamped taps')[1] is not None
+  # the flip
+  for crop in (None, (0, 5, 6, 1)):
+    kw = dict(saturation_first=False, delta=0.0, factor=1.0, crop=crop)
+    want = N.preprocess_image(big, 5, 'RESHAPE', True, flip=True, **kw)
+    got = N.preprocess_image(big[:, ::-1], 5, 'RESHAPE', True, flip=False, **kw)
+    assert E.check_elementwise(got, want, 3e-6, 'flip of the source')[1] is not None
+  want = N.preprocess_image(big, 32, 'RESHAPE', True, flip=True)
+  assert np.abs(N.preprocess_image(big[:, ::-1], 32, 'RESHAPE', True, flip=False) - want).max() > 3e-6      # the old check fails too
+  # saturate on s = 0
+  def saturate_no_guard(c, factor):
+    v = c.max(-1, keepdims=True)
+    with np.errstate(invalid='ignore', divide='ignore'):
+      s = (v - c.min(-1, keepdims=True)) / v
+      return v - (v - c) * (np.minimum(s * factor, 1.0) / s)
+  grey = np.repeat(rng.randint(0, 256, (4, 4, 1), dtype=np.uint8), 3, axis=2)
+  for im, hit in ((big[:8, :8], False), (grey, True), (np.zeros((2, 2, 3), np.uint8), True), (np.full((2, 3, 3), 255, np.uint8), True)):
+    x = N.preprocess_image(im, 4, 'RESHAPE', False)
+    want = N.preprocess_image(im, 4, 'RESHAPE', True, factor=1.4)
+    got = np.clip(saturate_no_guard(x, 1.4), 0.0, 1.0)
+    assert (E.check_elementwise(got, want, 3e-6, 'saturate')[1] is not None) == hit
+  # the ragged last workgroup
+  for hw, hit in ((32, False), (33, True)):
+    want = N.preprocess_image(big, hw, 'RESHAPE', False)
+    got = np.full(hw * hw * 3, np.nan)
+    full = (hw * hw // 256) * 256 * 3
+    got[:full] = want.reshape(-1)[:full]
+    assert (E.check_elementwise(got.reshape(want.shape), want, 3e-6, 'ragged workgroup')[1] is not None) == hit

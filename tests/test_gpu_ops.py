@@ -23,6 +23,11 @@ the emulated kernels): every element against its own bound, built from the float
   softmax kernels  u |ref| + 16 E32, each kernel on the operands it reads
   scalar sums      L 2^-24 |scale| sum|terms|            L: the longest chain of additions the launch geometry allows
   Adam             one step in float64 from the fp32 state it reads, each fp32 operation counted; the bf16 shadow bit-exact
+  spectral norm    2^-24 |ref| + 16 E, E = max(E32, 2^-24 max(mag)); the multi-kernel launch bit-equal to the one-kernel path
+  loss tail        reduction_bound over one workgroup's chain; gradients 4 2^-24 |ref| (+ 5 2^-24 |g| sigmoid for the cross entropy)
+  small GEMM, FC   the conv bound with K = k (+ 1 per bias / accumulate); parameter gradients as fp32 gradients with P = m
+  tanh, dot        u |ref| + 16 E32; ops 2^-24 mag for the pointwise pieces; tg_dot by its two-stage chain
+  preprocessing    u |want| + 3e-6 against oracle.np_ops.preprocess_image, through the C ABI
 with u = 2^-8 (bf16), 2^-11 (fp16), 2^-24 (fp32), `+ tiny` everywhere (2^-25 for fp16: half its subnormal spacing), and
 every further storage rounding the product path defines named where it is added.  Each check prints
 `[elementwise] <family> <dtype> worst ratio <r>` (run with -s).
@@ -4077,3 +4082,800 @@ def test_adam_step_elementwise(numel):
     assert bool((md[kind.to(dev()) == 3] == 0).all()) and bool((thd[kind.to(dev()) == 3] == th0.to(dev())[kind.to(dev()) == 3]).all())
   for w, nm in zip(worst, ('theta', 'm', 'v')):
     _ew_note('adam ' + nm, 'f32', w)
+
+
+# ------------------------------------------------------------------------------------------------ spectral norm
+SN_OLD_SHAPES = [(3, 3, 16, 32), (1, 1, 3, 16), (4, 4, 64, 64), (3, 3, 264, 256), (3, 3, 5, 7)]
+SN_SHAPES = [(1, 1, 1, 1), (1, 1, 1, 5), (1, 1, 5, 1), (1, 1, 2, 64), (1, 1, 15, 65), (1, 1, 17, 63), (4, 4, 16, 1), (1, 1, 4096, 1),
+             (3, 3, 7, 129), (3, 3, 8, 257), (1, 1, 64, 300), (3, 3, 16, 512), (1, 1, 16, 1023), (1, 1, 33, 1024), (1, 1, 1025, 3)] + SN_OLD_SHAPES
+SN_STATES = [(1e-4, 'random'), (0.1, 'random'), (30.0, 'random'), (1e-4, 'converged'), (0.1, 'converged'), (30.0, 'converged'),
+             (0.1, 'rank1')]
+_SN_ID = lambda sh: 'x'.join(map(str, sh))
+
+
+def _sn_power(w2, u, iters):
+  l2n = lambda x: x / x.pow(2).sum().clamp_min(1e-12).sqrt()
+  for _ in range(iters):
+    u = l2n(l2n(u @ w2.t()) @ w2)
+  return u
+
+
+def _sn_inputs(shape, scale, kind, salt=0):
+  """-> (w [kh, kw, cin, cout], u [1, cout], G like w) as float32 CPU tensors.  random: w ~ scale N(0, 1) (1e-4, 0.1, and 30 --
+  the equalised-learning-rate kernels are N(0, 1)), u ~ N(0, 1); converged: u after 30 float64 power iterations (b ~ 0: the
+  v (x) u' term carries the gradient); rank1: w = scale (p (x) q + 1e-3 N(0, 1)), nearly degenerate.  The seed of a case is the
+  first for which the float64 norms |u W^T| and |v W| are at least 1e-5, ten times l2_normalize's clamp: the clamped branch is
+  not what the backward's closed form differentiates (from the inputs alone, as _seeded does for the normalisers)."""
+  cout = shape[3]
+  k_rows = shape[0] * shape[1] * shape[2]
+  base = zlib.crc32(('sn%s%g%s%d' % (shape, scale, kind, salt)).encode()) % (2 ** 31 - 64)
+  for seed in range(base, base + 64):
+    g = torch.Generator().manual_seed(seed)
+    if kind == 'rank1':
+      w2 = scale * (torch.randn(k_rows, 1, generator=g, dtype=torch.float64) * torch.randn(1, cout, generator=g, dtype=torch.float64)
+                    + 1e-3 * torch.randn(k_rows, cout, generator=g, dtype=torch.float64))
+    else:
+      w2 = scale * torch.randn(k_rows, cout, generator=g, dtype=torch.float64)
+    w2 = w2.float()
+    u = torch.randn(1, cout, generator=g, dtype=torch.float64)
+    if kind == 'converged':
+      u = _sn_power(w2.double(), u, 30)
+    u = u.float()
+    G = torch.randn(k_rows, cout, generator=g, dtype=torch.float64).float()
+    v_raw = u.double() @ w2.double().t()
+    u_raw = (v_raw / v_raw.norm()) @ w2.double()
+    if float(v_raw.norm()) >= 1e-5 and float(u_raw.norm()) >= 1e-5:
+      return w2.reshape(shape), u, G.reshape(shape)
+  raise AssertionError('no seed keeps %s %g %s off the clamp' % (shape, scale, kind))
+
+
+def _sn_run(ops, w, u, G):
+  """ops.spectral_norm forward + backward on the device -> dict(w_bar, u_new, v, stats, gw) as float64 numpy, plus u_new on the device."""
+  wd = w.clone().to(dev()).requires_grad_(True)
+  w_bar, u_new = ops.spectral_norm(wd, u.clone().to(dev()))
+  _, _, _, v, stats = w_bar.grad_fn.saved_tensors
+  (w_bar * G.to(dev())).sum().backward()
+  k_rows = w.numel() // w.shape[-1]
+  return dict(w_bar=host(w_bar).reshape(k_rows, -1), u_new=host(u_new).reshape(-1), v=host(v), stats=host(stats),
+              gw=host(wd.grad).reshape(k_rows, -1)), u_new.detach()
+
+
+def _sn_check(what, got, ref, bound):
+  for key in ('w_bar', 'u_new', 'v', 'stats', 'gw'):
+    if key in got:
+      _ew_note('spectral norm ' + key, 'f32', E.assert_elementwise(got[key], ref[key], bound[key], '%s %s' % (what, key)))
+
+
+@pytest.mark.parametrize('shape', SN_SHAPES, ids=_SN_ID)
+def test_spectral_norm_elementwise(ops, shape):
+  """tg_spectral_norm_fwd / _bwd, every element of w_bar, u', the saved v and stats = {sigma, |v_raw|}, and d L / d w inside
+  elementwise.sn_bounds, against float64 autograd of the literal formulas.  Shapes: a 1 x 1 matrix, one row, one column
+  (cout = 1: a prediction layer), k_rows on both sides of ROWS = KS = 16, K = 4096 and 1025 rows on a thin matrix, cout across
+  64, 128, 256 (where sn_finish's ur[4] loop takes its second, third and fourth trip), 512 and the documented limit of 1024;
+  the five shapes test_spectral_norm_matches_oracle has.  States: weight scales 1e-4 / 0.1 / 30, u random and converged
+  (b ~ 0), one nearly rank-1 matrix."""
+  k_rows, cout = shape[0] * shape[1] * shape[2], shape[3]
+  for scale, kind in SN_STATES:
+    w, u, G = _sn_inputs(shape, scale, kind)
+    got, _ = _sn_run(ops, w, u, G)
+    ref, bound = E.sn_bounds(w.reshape(k_rows, cout), u, G.reshape(k_rows, cout))
+    _sn_check('sn %s %g %s' % (_SN_ID(shape), scale, kind), got, ref, bound)
+  # one more state: w ~ 1e-8 N(0, 1) / sqrt(K cout) (|u W^T| ~ 1e-8), where BOTH l2_normalize clamps are active (|u W^T|^2 and |v W|^2 < 1e-12; v =
+  # v_raw 1e6, stats[1] = 1e-6).  Forward outputs and the saved v / stats only: a stats[1] left unclamped shows nowhere else, and
+  # the backward's closed form differentiates the unclamped normalisation, so its gradient is not asked here
+  g = torch.Generator().manual_seed(k_rows * 7 + cout)
+  w = (1e-8 / (k_rows * cout) ** 0.5 * torch.randn(shape, generator=g, dtype=torch.float64)).float()
+  u, G = torch.randn(1, cout, generator=g), torch.randn(shape, generator=g)
+  assert float((u.double() @ w.double().reshape(k_rows, cout).t()).norm()) < 1e-7
+  got, _ = _sn_run(ops, w, u, G)
+  ref, bound = E.sn_bounds(w.reshape(k_rows, cout), u, G.reshape(k_rows, cout))
+  assert ref['stats'][1] == 1e-6
+  del got['gw']
+  _sn_check('sn %s clamped' % _SN_ID(shape), got, ref, bound)
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 1, 1), (1, 1, 17, 63), (3, 3, 8, 257), (1, 1, 33, 1024), (3, 3, 16, 32)], ids=_SN_ID)
+def test_spectral_norm_gradient_into_a_sink_that_holds_values(ops, shape):
+  """tg_spectral_norm_bwd with accumulate = 1 (ops.GradSink.register(w, sink): the trainer's route): forward + backward twice
+  onto a sink pre-filled with seeded values -> sink0 + 2 gw, every element inside the sum of the two single-call bounds plus
+  the two fp32 additions (2 2^-24 |ref|); w.grad stays None."""
+  k_rows, cout = shape[0] * shape[1] * shape[2], shape[3]
+  for scale, kind in ((0.1, 'random'), (30.0, 'converged')):
+    w, u, G = _sn_inputs(shape, scale, kind, salt=1)
+    gen = torch.Generator().manual_seed(k_rows * 1031 + cout)
+    sink0 = torch.randn(shape, generator=gen) * float(G.abs().mean()) / scale      # of the gradient's own size: gw ~ G / sigma
+    wd, sink = w.clone().to(dev()).requires_grad_(True), sink0.clone().to(dev())
+    ops.GradSink.clear()
+    ops.GradSink.register(wd, sink)
+    try:
+      for _ in range(2):
+        w_bar, _ = ops.spectral_norm(wd, u.to(dev()))
+        (w_bar * G.to(dev())).sum().backward()
+    finally:
+      ops.GradSink.clear()
+    assert wd.grad is None
+    ref, bound = E.sn_bounds(w.reshape(k_rows, cout), u, G.reshape(k_rows, cout))
+    want = sink0.double().numpy().reshape(k_rows, cout) + 2.0 * ref['gw']
+    _ew_note('spectral norm gw into sink', 'f32', E.assert_elementwise(host(sink).reshape(k_rows, cout), want,
+                                                                      2.0 * bound['gw'] + 2.0 * E.U32 * np.abs(want),
+                                                                      'sn sink %s %g %s' % (_SN_ID(shape), scale, kind)))
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 5, 1), (3, 3, 7, 129), (1, 1, 16, 1023), (3, 3, 16, 32)], ids=_SN_ID)
+def test_spectral_norm_ten_chained_power_iterations(ops, shape):
+  """Ten runs, each from the previous run's u' (what a training run does): every step's sigma, u', v and w_bar element-wise
+  against the float64 step taken from the DEVICE's own u (as the Adam test hands the reference the state the launch read)."""
+  k_rows, cout = shape[0] * shape[1] * shape[2], shape[3]
+  w, u, G = _sn_inputs(shape, 0.1, 'random', salt=2)
+  for step in range(10):
+    got, u_dev = _sn_run(ops, w, u, G)
+    ref, bound = E.sn_bounds(w.reshape(k_rows, cout), u, G.reshape(k_rows, cout))
+    _sn_check('sn chained %s step %d' % (_SN_ID(shape), step), got, ref, bound)
+    u = u_dev.cpu().reshape(1, cout)
+
+
+SN_MULTI_SHAPES = [SN_SHAPES[i] for i in (11, 0, 13, 2, 19, 7, 12, 1, 9, 16, 3, 14, 8, 17, 4, 10, 5, 15, 6, 18,
+                                           0, 12, 2, 13, 1, 11, 7, 9, 3, 14, 16, 4, 19)]      # 33 jobs: 1-block and many-block jobs adjacent
+
+
+def test_spectral_norm_multi_of_33_jobs_and_assign_u(ops):
+  """tg_spectral_norm_fwd_multi over a table of 33 jobs (config 4 lays 60 end to end; sn_job_of finds each block's job at every
+  boundary: jobs of 1 and of hundreds of blocks next to each other, cout = 1, 1023 and 1024 among them) and over a table of ONE
+  job: w_bar, u' and the gradients equal the one-kernel entry point's bit for bit.  SnTable.assign_u (tg_sn_assign_u): u
+  equals u' for every job afterwards, bit for bit, and a second run from the assigned u again equals the single-kernel path."""
+  assert len(SN_MULTI_SHAPES) == 33
+  g = torch.Generator().manual_seed(41)
+  ws = [(torch.randn(*sh, generator=g) * 0.1).to(dev()) for sh in SN_MULTI_SHAPES]
+  us = [torch.randn(1, sh[3], generator=g).to(dev()) for sh in SN_MULTI_SHAPES]
+  gq = [torch.randn(*sh, generator=g).to(dev()) for sh in SN_MULTI_SHAPES]
+  outs = [torch.empty(w.numel(), dtype=torch.float32, device=w.device) for w in ws]
+  wds = [w.clone().requires_grad_(True) for w in ws]
+
+  def single(j):
+    wd = ws[j].clone().requires_grad_(True)
+    wb, un = ops.spectral_norm(wd, us[j].clone())
+    (wb * gq[j]).sum().backward()
+    return wb.detach().clone(), un.detach().clone(), wd.grad.clone()
+
+  table = None
+  for run in range(2):
+    ones = [single(j) for j in range(33)]
+    for wd in wds:
+      wd.grad = None
+    res, table2 = ops.spectral_norm_multi(list(zip(wds, us, outs)), table)
+    assert run == 0 or table2 is table
+    table = table2
+    sum((wb * q).sum() for (wb, _), q in zip(res, gq)).backward()
+    for j, ((wb, un), wd, (wb1, un1, g1)) in enumerate(zip(res, wds, ones)):
+      assert torch.equal(wb.detach(), wb1) and torch.equal(un.detach().reshape(-1), un1.reshape(-1)), (run, j, SN_MULTI_SHAPES[j])
+      assert torch.equal(wd.grad, g1), (run, j, SN_MULTI_SHAPES[j])
+    before = [u.clone() for u in us]
+    table.assign_u()
+    for j, (u, (u_new, _, _, _)) in enumerate(zip(us, table.bufs)):
+      assert torch.equal(u.reshape(-1), u_new), (run, j, SN_MULTI_SHAPES[j])
+      assert u.numel() == 1 or not torch.equal(u, before[j]), j
+  # a table of a single job (njobs = 1: sn_job_of's loop body never runs)
+  j = SN_MULTI_SHAPES.index((1, 1, 16, 1023))
+  wd1, out1 = ws[j].clone().requires_grad_(True), torch.empty(ws[j].numel(), dtype=torch.float32, device=dev())
+  want = single(j)
+  res1, t1 = ops.spectral_norm_multi([(wd1, us[j], out1)], None)
+  assert t1.n == 1
+  (res1[0][0] * gq[j]).sum().backward()
+  assert torch.equal(res1[0][0].detach(), want[0]) and torch.equal(res1[0][1].detach().reshape(-1), want[1].reshape(-1))
+  assert torch.equal(wd1.grad, want[2])
+  t1.assign_u()
+  assert torch.equal(us[j].reshape(-1), t1.bufs[0][0])
+
+
+def test_spectral_norm_refuses_what_it_cannot_run(ops):
+  """cout = 1025 (sn_finish holds u_raw in four registers per thread: 1024 columns) is refused with TG_EINVAL by
+  tg_spectral_norm_fwd and by tg_sn_table_fill, a workspace one byte short by the forward and the backward; nothing is launched
+  (every output keeps its sentinel, the host table and the running totals keep theirs).  tg_spectral_norm_bwd has no such
+  limit -- sn_rowdot strides over the columns and sn_bwd_apply is element-wise -- and computes cout = 1025 from hand-made
+  u' / v / stats: checked against the closed form in float64 on the operands it reads."""
+  import ctypes
+  from twingan_amd import _lib
+  lib = _lib.load()
+  st = torch.cuda.current_stream().cuda_stream
+  rng = np.random.RandomState(1025)
+
+  def run(k_rows, cout, short=0, which='fwd'):
+    w, u, G = (to_dev(rng.randn(*s)) for s in ((k_rows, cout), (cout,), (k_rows, cout)))
+    outs = [torch.full((n,), -7.25, device=dev()) for n in (k_rows * cout, cout, k_rows, 2)]
+    nbytes = lib.tg_spectral_norm_workspace(k_rows, cout)
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev())
+    if which == 'fwd':
+      rc = lib.tg_spectral_norm_fwd(w.data_ptr(), u.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+                                    outs[3].data_ptr(), k_rows, cout, ws.data_ptr(), nbytes - short, st)
+    else:
+      rc = lib.tg_spectral_norm_bwd(G.data_ptr(), w.data_ptr(), u.data_ptr(), u.data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
+                                    outs[0].data_ptr(), 0, k_rows, cout, ws.data_ptr(), nbytes - short, st)
+    torch.cuda.synchronize()
+    return rc, all(bool((o == -7.25).all()) for o in outs) and bool((ws == 0).all())
+
+  TG_EINVAL = -1      # include/twingan_hip.h
+  assert run(3, 1025) == (TG_EINVAL, True)
+  assert run(5, 70, short=1) == (TG_EINVAL, True)
+  assert run(5, 70, short=1, which='bwd') == (TG_EINVAL, True)
+  assert run(5, 70)[0] == 0
+  # tg_sn_table_fill
+  host_table = ctypes.create_string_buffer(b'\x5a' * lib.tg_sn_table_bytes(2), lib.tg_sn_table_bytes(2))
+  totals = (ctypes.c_int32 * 3)(11, 12, 13)
+  buf = torch.zeros(1025 * 3 + 4096, device=dev())
+  nbytes = lib.tg_spectral_norm_workspace(3, 1025)
+  wsb = torch.zeros(nbytes, dtype=torch.uint8, device=dev())
+  p = buf.data_ptr()
+  rc = lib.tg_sn_table_fill(1, p, p, p, p, p, p, wsb.data_ptr(), nbytes, 3, 1025, ctypes.addressof(host_table), totals)
+  assert rc == TG_EINVAL and tuple(totals) == (11, 12, 13) and host_table.raw == b'\x5a' * lib.tg_sn_table_bytes(2)
+  rc = lib.tg_sn_table_fill(1, p, p, p, p, p, p, wsb.data_ptr(), lib.tg_spectral_norm_workspace(3, 1024) - 1, 3, 1024,
+                            ctypes.addressof(host_table), totals)
+  assert rc == TG_EINVAL and tuple(totals) == (11, 12, 13)
+  # the backward at cout = 1025, from hand-made operands
+  k_rows, cout = 3, 1025
+  w, u, G = (torch.randn(*s, generator=torch.Generator().manual_seed(7 + i)) * sc
+             for i, (s, sc) in enumerate((((k_rows, cout), 0.1), ((1, cout), 1.0), ((k_rows, cout), 1.0))))
+  r = E.sn_formulas(w, u, G, torch.float64)
+  f32 = lambda a: np.asarray(a, np.float32)
+  u_new, v, stats = f32(r['u_new']), f32(r['v']), f32(r['stats'])
+  ops_in = (G.numpy(), w.numpy(), u.numpy().reshape(-1), u_new, v, stats)
+  ref = E.sn_bwd_closed_form(*ops_in)
+  r32 = E.sn_bwd_closed_form(*ops_in, dt=np.float32)
+  sig, s = float(stats[0]), float((G.double() * w.double()).sum())
+  a = w.double().numpy() @ u_new.astype(np.float64)
+  b = (a - v * (v.astype(np.float64) * a).sum()) / float(stats[1])
+  mag = np.abs(G.numpy()) / sig + abs(s) / sig ** 2 * (np.abs(np.outer(v, u_new)) + np.abs(np.outer(b, u.numpy().reshape(-1))))
+  bound = E.e32_bound(ref, max(E.e32(r32, ref), E.U32 * float(mag.max())), 'f32')
+  gw = torch.full((k_rows, cout), float('nan'), device=dev())
+  nbytes = lib.tg_spectral_norm_workspace(k_rows, cout)
+  wsb = torch.empty(nbytes, dtype=torch.uint8, device=dev())
+  dv = [to_dev(x) for x in ops_in]
+  import twingan_amd.ops as O
+  O.call('tg_spectral_norm_bwd', dv[0].data_ptr(), dv[1].data_ptr(), dv[2].data_ptr(), dv[3].data_ptr(), dv[4].data_ptr(),
+         dv[5].data_ptr(), gw.data_ptr(), 0, k_rows, cout, wsb.data_ptr(), nbytes, st)
+  _ew_note('spectral norm bwd cout 1025', 'f32', E.assert_elementwise(host(gw), ref, bound, 'sn bwd at cout 1025'))
+
+
+# ------------------------------------------------------------------------------------------------ the loss tail
+def _t32(a):
+  return torch.from_numpy(np.ascontiguousarray(a, np.float32))
+
+
+@pytest.mark.parametrize('family', ['random', 'parallel', 'opposite', 'clamped'])
+@pytest.mark.parametrize('b,d', [(1, 1), (3, 5), (4, 256), (5, 257), (16, 600), (2, 1024)])
+def test_cosine_distance_elementwise(ops, b, d, family):
+  """tg_cosine_distance_fwd / _bwd (the encoder-distillation loss), weight 0.7, incoming gradient 2.5: one element, a partial
+  workgroup, exactly one / one more than one trip of 256, several trips.  random; p = 3 e (distance 0, gradient ~ 0: the two
+  summands cancel); p = -e / 2 (distance 2); p 1e-8 with one all-zero row (|p|^2 < 1e-12: the clamped branch of the backward,
+  phat = p 1e6).  Against float64 autograd of the formula with the clamp written as the kernel documents it."""
+  rng = np.random.RandomState(zlib.crc32(('cos%d%d%s' % (b, d, family)).encode()) % (2 ** 31))
+  e = rng.randn(b, d)
+  p = {'random': rng.randn(b, d), 'parallel': 3.0 * e, 'opposite': -0.5 * e, 'clamped': rng.randn(b, d) * 1e-8}[family]
+  if family == 'clamped':
+    p[b // 2] = 0.0
+  e, p = _t32(e), _t32(p)
+  assert family != 'clamped' or float((p.double() ** 2).sum(1).max()) < 0.5e-12
+  ref, b_out, b_gp = E.cosine_bounds(e, p, 0.7, 2.5)
+  pd = p.clone().to(dev()).requires_grad_(True)
+  out = ops.cosine_distance(e.clone().to(dev()), pd, 0.7)
+  (out * 2.5).backward()
+  r = abs(out.item() - ref['out']) / b_out
+  print('[cosine] %s (%d, %d): out %.9g ref %.9g ratio %.3f' % (family, b, d, out.item(), ref['out'], r))
+  assert r <= 1.0, (out.item(), ref['out'], b_out)
+  _ew_note('cosine distance', 'f32', r)
+  _ew_note('cosine distance grad', 'f32', E.assert_elementwise(host(pd.grad), ref['gp'], b_gp, 'cosine %s d p' % family))
+
+
+PRED_MODES = [('hinge_fake', 1, 1.0, 1.0), ('hinge_real', 1, 1.0, -1.0), ('xent_1', 2, 1.0, 0.0), ('xent_0', 2, 0.0, 0.0),
+              ('square', 3, 0.0, 0.0)]
+
+
+def _pred_values(n, seed):
+  """4 N(0, 1) with +-88 planted (expf(-|x|) underflows, the sigmoid saturates), +-20 (sigmoid - 1 cancels in fp32) and +-1
+  (a + b x = 0 exactly for the hinge with a = 1, b = -+1), as far as n has room."""
+  x = np.random.RandomState(seed).randn(n) * 4.0
+  for i, v in enumerate((88.0, -88.0, 1.0, -1.0, 20.0, -20.0)):
+    if 1 + 41 * i < n or (n == 7 and i < 6):
+      x[(1 + 41 * i) if n > 7 else i + 1] = v
+  return x.astype(np.float32).astype(np.float64)
+
+
+@pytest.mark.parametrize('name,mode,a,b', PRED_MODES, ids=[m[0] for m in PRED_MODES])
+@pytest.mark.parametrize('n', [1, 7, 256, 257, 5000])
+def test_pred_loss_elementwise(ops, n, name, mode, a, b):
+  """hinge_mean / sigmoid_xent_mean / square_mean (tg_pred_loss_fwd / _bwd, modes 1-3) at 1, 7, 256, 257 and 5000 predictions,
+  weight 0.3, incoming gradient 2.5.  Forward: reduction_bound with the chain of one 256-thread workgroup; backward: per
+  element (elementwise.pred_loss_bwd_bound)."""
+  x = _pred_values(n, 100 + n)
+  if n == 1 and mode == 1:
+    x[0] = -b      # a + b x = 0
+  f, df, parts, term_ops, sig = E.pred_loss_reference(x, mode, a, b)
+  xd = to_dev(x).requires_grad_(True)
+  fn = {1: lambda t: ops.hinge_mean(t, a, b, 0.3), 2: lambda t: ops.sigmoid_xent_mean(t, a, 0.3), 3: lambda t: ops.square_mean(t, 0.3)}[mode]
+  out = fn(xd)
+  (out * 2.5).backward()
+  want = 0.3 * f.sum() / n
+  bound = E.pred_loss_fwd_bound(parts.sum(), n, 0.3 / n, term_ops)
+  r = abs(out.item() - want) / bound
+  print('[pred loss] %s n %d: got %.9g ref %.9g ratio %.3f' % (name, n, out.item(), want, r))
+  assert r <= 1.0, (out.item(), want, bound)
+  _ew_note('pred loss ' + name.split('_')[0], 'f32', r)
+  g = 2.5 * 0.3 / n
+  _ew_note('pred loss grad ' + name.split('_')[0], 'f32',
+           E.assert_elementwise(host(xd.grad), g * df, E.pred_loss_bwd_bound(g * df, abs(g), sig), 'pred loss %s d x' % name))
+  if mode == 1:
+    assert np.all(host(xd.grad)[a + b * x == 0.0] == 0.0) and (a + b * x == 0.0).any()
+
+
+PRED_JOBS = [      # (group, term, mode, a, b, coef): two jobs into term 0 from different groups, two jobs on group 1 into
+    (0, 0, 1, 1.0, -1.0, 0.5), (2, 0, 1, 1.0, 1.0, 0.5),      # different terms, every mode, term 3 fed by nobody, term 4 fed but
+    (1, 1, 2, 1.0, 0.0, 0.7), (1, 2, 2, 0.0, 0.0, 0.3),        # without a gradient
+    (0, 2, 3, 0.0, 0.0, 1e-3), (2, 1, 0, 0.0, 0.0, -1.0),
+    (1, 4, 1, 1.0, 1.0, 2.0), (0, 4, 0, 0.0, 0.0, 1.0)]
+
+
+def _pred_losses_reference(x, gs, jobs, nterms, gterms):
+  """-> (terms, their bounds, d pred, its bound) in float64: per job coef mean f over its group; acc_t += coef * tot / gs is a
+  multiply, a division (2) and an addition per job: extra_ops 4; the backward adds, per job, g_t (coef / gs) df: the division
+  (2), two multiplies, the addition: 6 2^-24 |summand| each (+ the sigmoid term of mode 2)."""
+  terms, tb = np.zeros(nterms), np.zeros(nterms)
+  gx, gb = np.zeros_like(x), np.full_like(x, E.TINY)
+  for grp, t, mode, a, b, coef in jobs:
+    xs = x[grp * gs:(grp + 1) * gs]
+    f, df, parts, term_ops, sig = E.pred_loss_reference(xs, mode, a, b)
+    terms[t] += coef * f.sum() / gs
+    tb[t] += E.pred_loss_fwd_bound(parts.sum(), gs, coef / gs, term_ops, extra_ops=3)
+    if gterms[t] is not None:
+      k = gterms[t] * coef / gs
+      gx[grp * gs:(grp + 1) * gs] += k * df
+      gb[grp * gs:(grp + 1) * gs] += E.pred_loss_bwd_bound(k * df, abs(k), sig, ops=6)
+  return terms, tb, gx, gb
+
+
+@pytest.mark.parametrize('gs', [1, 3, 64, 255, 256, 257, 1000])
+def test_pred_losses_elementwise(ops, gs):
+  """tg_pred_losses_fwd / _bwd: three groups of gs predictions, eight jobs over four of five terms (PRED_JOBS), gradients for
+  three terms only (term 4 is fed and gets None; term 3 is fed by no job and must read 0).  Against float64, and against the
+  sum of single PredLossFn calls (each inside its own bound)."""
+  x = _pred_values(3 * gs, 200 + gs)
+  gts = [1.5, -0.5, 2.0, None, None]
+  terms, tb, gx, gb = _pred_losses_reference(x, gs, PRED_JOBS, 5, gts)
+  xd = to_dev(x).reshape(3 * gs, 1).requires_grad_(True)
+  out = ops.pred_losses(xd, gs, PRED_JOBS, 5)
+  torch.autograd.backward([out[t] for t in (0, 1, 2)], [torch.full((1,), gts[t], device=dev()) for t in (0, 1, 2)])
+  got = np.array([o.item() for o in out])
+  assert got[3] == 0.0
+  ratios = np.abs(got - terms) / np.maximum(tb, E.TINY)
+  print('[pred losses] gs %d: terms %s ratios %s' % (gs, got, np.round(ratios, 3)))
+  assert np.all(ratios <= 1.0), (got, terms, tb)
+  _ew_note('pred losses', 'f32', ratios.max())
+  _ew_note('pred losses grad', 'f32', E.assert_elementwise(host(xd.grad).reshape(-1), gx, gb, 'pred_losses d pred'))
+  # the sum of single calls
+  one_t, one_tb = np.zeros(5), np.zeros(5)
+  xs = to_dev(x).requires_grad_(True)
+  loss = None
+  for grp, t, mode, a, b, coef in PRED_JOBS:
+    seg = xs[grp * gs:(grp + 1) * gs]
+    o = ops.PredLossFn.apply(seg.contiguous(), mode, a, b, coef)
+    f, df, parts, term_ops, sig = E.pred_loss_reference(x[grp * gs:(grp + 1) * gs], mode, a, b)
+    one_t[t] += o.item()
+    one_tb[t] += E.pred_loss_fwd_bound(parts.sum(), gs, coef / gs, term_ops)
+    if gts[t] is not None:
+      loss = o * gts[t] if loss is None else loss + o * gts[t]
+  loss.backward()
+  assert np.all(np.abs(got - one_t) <= tb + one_tb + 8 * E.U32 * np.abs(terms)), (got, one_t)
+  E.assert_elementwise(host(xd.grad).reshape(-1), host(xs.grad), 2.0 * gb + 8 * E.U32 * np.abs(gx), 'pred_losses vs single calls')
+
+
+def test_pred_losses_limits(ops):
+  """12 jobs and 8 terms are taken (and right); 13 jobs, 9 terms, a group or a term index out of range are refused."""
+  from twingan_amd._lib import TgError
+  gs = 5
+  x = _pred_values(3 * gs, 77)
+  jobs = [(j % 3, j % 8, 1 + j % 3, 1.0 if j % 3 != 2 else 0.0, -1.0, 0.25 + j) for j in range(12)]
+  gts = [0.5 + t for t in range(8)]
+  terms, tb, gx, gb = _pred_losses_reference(x, gs, jobs, 8, gts)
+  xd = to_dev(x).reshape(-1, 1).requires_grad_(True)
+  out = ops.pred_losses(xd, gs, jobs, 8)
+  torch.autograd.backward(list(out), [torch.full((1,), g, device=dev()) for g in gts])
+  got = np.array([o.item() for o in out])
+  assert np.all(np.abs(got - terms) <= tb), (got, terms, tb)
+  E.assert_elementwise(host(xd.grad).reshape(-1), gx, gb, 'pred_losses at 12 jobs / 8 terms')
+  for bad_jobs, nterms in ((jobs + [jobs[0]], 8), (jobs, 9), ([(3, 0, 1, 1.0, 1.0, 1.0)], 2), ([(0, 2, 1, 1.0, 1.0, 1.0)], 2),
+                           ([(-1, 0, 1, 1.0, 1.0, 1.0)], 2), ([(0, -1, 1, 1.0, 1.0, 1.0)], 2)):
+    with pytest.raises(TgError):
+      ops.pred_losses(to_dev(x).reshape(-1, 1), gs, bad_jobs, nterms)
+
+
+@pytest.mark.parametrize('n', [2, 5, 24])
+def test_sum_scalars_elementwise(ops, n):
+  """tg_sum_scalars (tf.add_n over the loss collection): magnitudes over six decades, both signs, summed in argument order:
+  |got - ref| <= n 2^-24 sum|x|; every term's gradient IS the incoming one, bit for bit.  25 terms are refused."""
+  import ctypes
+  from twingan_amd import _lib
+  rng = np.random.RandomState(300 + n)
+  vals = (rng.randn(n) * 10.0 ** rng.uniform(-3, 3, n)).astype(np.float32)
+  ts = [to_dev(vals[i:i + 1]).requires_grad_(True) for i in range(n)]
+  out = ops.sum_scalars(ts)
+  gin = torch.full((1,), 1.7, device=dev())
+  out.backward(gin)
+  ref, bound = vals.astype(np.float64).sum(), n * E.U32 * np.abs(vals.astype(np.float64)).sum() + E.TINY
+  assert abs(out.item() - ref) <= bound, (out.item(), ref, bound)
+  _ew_note('sum_scalars', 'f32', abs(out.item() - ref) / bound)
+  for t in ts:
+    assert torch.equal(t.grad, gin)
+  if n == 24:
+    keep = ts + [to_dev(vals[:1])]
+    ptrs = (ctypes.c_void_p * 25)(*[t.data_ptr() for t in keep])
+    res = torch.full((1,), -7.25, device=dev())
+    rc = _lib.load().tg_sum_scalars(ctypes.addressof(ptrs), 25, res.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == -1 and res.item() == -7.25
+
+
+VAR_SHAPES = [(1, 1, 1, 3), (2, 8, 8, 3), (3, 17, 19, 3), (4, 64, 64, 3), (16, 32, 32, 3)]
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('shape', VAR_SHAPES, ids=['x'.join(map(str, s)) for s in VAR_SHAPES])
+def test_batch_variance_and_dragan_interpolates_elementwise(ops, shape, dname):
+  """ops.batch_variance (tg_sum, tg_sample_sumsq, tg_var_from_sums) and ops.dragan_interpolates on U[-1, 1], on 0.9 + 0.01 U (the
+  cancellation case: the variance is 1e-5 of E[x^2]) and on the constant 0.7 (the result must be >= 0).  The reference is taken
+  on the stored values; the variance's bound is relative to E[x^2] (elementwise.variance_bound), the interpolates' per element:
+  u |ref| + the stored delta's own rounding u |delta| + 5 fp32 operations (noise coef var: 2; axpby: 3) + the variance's bound
+  carried through 0.5 |alpha noise|."""
+  dtype = EW_DTYPES[dname]
+  u = E.unit_roundoff(dtype)
+  rng = np.random.RandomState(zlib.crc32(('var%s' % (shape,)).encode()) % (2 ** 31))
+  for fam in ('uniform', 'offset', 'constant'):
+    base = rng.uniform(-1, 1, shape)
+    x = _round_dt({'uniform': base, 'offset': 0.9 + 0.01 * base, 'constant': np.full(shape, 0.7)}[fam], dtype)
+    noise, alpha = _round_dt(rng.randn(*shape), dtype), rng.rand(shape[0]).astype(np.float32).astype(np.float64)
+    var, bvar, L = E.variance_bound(x, dtype, shape[0])
+    xd = to_dev(x, dtype)
+    got = ops.batch_variance(xd).item()
+    r = abs(got - var) / bvar
+    print('[variance] %s %s %s: got %.9g ref %.9g L %d ratio %.3f' % (dname, shape, fam, got, var, L, r))
+    assert got >= 0.0 and r <= 1.0, (got, var, bvar)
+    _ew_note('batch_variance', dname, r)
+    out = ops.dragan_interpolates(xd, to_dev(noise, dtype), to_dev(alpha))
+    an = 0.5 * np.abs(alpha.reshape(-1, 1, 1, 1) * noise)
+    delta = 0.5 * alpha.reshape(-1, 1, 1, 1) * noise * var
+    ref = x + delta
+    bound = u * np.abs(ref) + (1 + u) * (u * np.abs(delta) + 5 * E.U32 * (np.abs(x) + np.abs(delta)) + bvar * an) + E.tiny(dtype)
+    _ew_note('dragan_interpolates', dname, E.assert_elementwise(host(out), ref, bound, 'dragan_interpolates %s' % fam))
+
+
+# ------------------------------------------------------------------------------------------------ small dense kernels
+SMALL_GEMM_CASES = [(1, 1, 1), (3, 5, 31), (3, 5, 32), (3, 5, 33), (64, 64, 40), (64, 65, 40), (7, 1, 256), (2, 4096, 300),
+                    (65, 63, 100), (4, 16, 512)]
+
+
+def _small_gemm_wave(m, n, k):
+  """tg_small_gemm's choice (csrc/reduce.hip): one wave per output element when k >= 32 and m n <= 4096, else one thread."""
+  return k >= 32 and m * n <= 4096
+
+
+@pytest.mark.parametrize('m,n,k', SMALL_GEMM_CASES)
+def test_small_gemm_elementwise(ops, m, n, k):
+  """GemmFn (tg_small_gemm), all four transposes, forward and both gradients (themselves GEMMs: K = n for d a, K = m for d b):
+  every element inside conv_bound with K summands in fp32.  The shapes sit on both sides of both conditions of the kernel
+  choice (k = 31 / 32 / 33 -- at 33 lanes 33..63 of the wave kernel have no term; m n = 4096 / 4160), and the gradients of one
+  shape take the other kernel (k = 300, m n = 8192: the thread kernel forward; d b is [300, 4096] from K = 2: thread; d a is
+  [2, 300] from K = 4096: wave).  Through the C ABI once each with a bias and with accumulate = 1 onto a non-zero C: K + 1.
+  tg_last_kernel reports the conv kernels only, so the choice is pinned by its restatement here, not by a report."""
+  import twingan_amd.ops as O
+  assert [_small_gemm_wave(*c) for c in SMALL_GEMM_CASES] == [False, False, True, True, True, False, True, False, True, True]
+  rng = np.random.RandomState(zlib.crc32(('sg%d%d%d' % (m, n, k)).encode()) % (2 ** 31))
+  f32 = lambda a: a.astype(np.float32).astype(np.float64)
+  for ta in (False, True):
+    for tb in (False, True):
+      a, b, g = f32(rng.randn(k, m) if ta else rng.randn(m, k)), f32(rng.randn(n, k) if tb else rng.randn(k, n)), f32(rng.randn(m, n))
+      oa, ob = (a.T if ta else a), (b.T if tb else b)
+      ad, bd = to_dev(a).requires_grad_(True), to_dev(b).requires_grad_(True)
+      c = ops.GemmFn.apply(ad, bd, ta, tb)
+      c.backward(to_dev(g))
+      what = 'small gemm (%d, %d, %d) ta=%d tb=%d' % (m, n, k, ta, tb)
+      w = E.assert_elementwise(host(c), oa @ ob, E.conv_bound(oa @ ob, np.abs(oa) @ np.abs(ob), k, 'f32'), what)
+      ga, ma = g @ ob.T, np.abs(g) @ np.abs(ob).T
+      gb, mb = oa.T @ g, np.abs(oa).T @ np.abs(g)
+      w = max(w, E.assert_elementwise(host(ad.grad), ga.T if ta else ga, E.conv_bound(ga.T if ta else ga, ma.T if ta else ma, n, 'f32'),
+                                      what + ' d a'))
+      w = max(w, E.assert_elementwise(host(bd.grad), gb.T if tb else gb, E.conv_bound(gb.T if tb else gb, mb.T if tb else mb, m, 'f32'),
+                                      what + ' d b'))
+      _ew_note('small gemm', 'f32', w)
+      # the C ABI: bias, and accumulate onto a non-zero C
+      bias, c0 = f32(rng.randn(n)), f32(rng.randn(m, n))
+      st = torch.cuda.current_stream().cuda_stream
+      cb, cacc, biasd = torch.empty(m, n, device=dev()), to_dev(c0), to_dev(bias)
+      O.call('tg_small_gemm', ad.data_ptr(), bd.data_ptr(), biasd.data_ptr(), cb.data_ptr(), m, n, k, int(ta), int(tb), 0, st)
+      O.call('tg_small_gemm', ad.data_ptr(), bd.data_ptr(), None, cacc.data_ptr(), m, n, k, int(ta), int(tb), 1, st)
+      mag = np.abs(oa) @ np.abs(ob)
+      w = E.assert_elementwise(host(cb), oa @ ob + bias, E.conv_bound(oa @ ob + bias, mag + np.abs(bias), k + 1, 'f32'), what + ' bias')
+      w = max(w, E.assert_elementwise(host(cacc), oa @ ob + c0, E.conv_bound(oa @ ob + c0, mag + np.abs(c0), k + 1, 'f32'), what + ' acc'))
+      _ew_note('small gemm C ABI', 'f32', w)
+
+
+FC_CASES = [(1, 1, 1), (6, 3, 40), (5, 7, 7), (33, 2, 65), (64, 1, 256), (64, 16, 256), (16, 1, 512), (2, 16, 1000), (4, 9, 5), (3, 70, 80)]
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('m,n,k', FC_CASES)
+def test_fully_connected_elementwise(ops, m, n, k, dname):
+  """ops.fully_connected in first-order passes (FcFn: tg_fc_fwd / tg_fc_bwd, one launch each way; x in the activations' type):
+      y   conv_bound(K = k + 1, 'f32')     k products and the bias       gx   conv_bound(K = n, dtype)
+      gw, gb   wgrad_bound(P = m); through a gradient sink that holds values one more summand (P = m + 1, mag + |sink|)
+  and gx alone in a no_param_grads pass (gw / gb not written).  n = k (5, 7, 7) is the last shape FcFn takes; (4, 9, 5) has
+  n > k, which tg_fc_bwd's one-thread-per-k layout cannot serve: fully_connected must take the composition (asserted by the
+  grad_fn's name) -- the same bounds hold (the cast is exact, the GEMM has the same k products).  (3, 70, 80) is the
+  only shape with n > 64, where gb's columns pass the first 64-thread workgroup of tg_fc_bwd."""
+  dtype = EW_DTYPES[dname]
+  rng = np.random.RandomState(zlib.crc32(('fc%d%d%d' % (m, n, k)).encode()) % (2 ** 31))
+  f32 = lambda a: a.astype(np.float32).astype(np.float64)
+  x, w, b, g = _round_dt(rng.randn(m, k), dtype), f32(rng.randn(k, n)), f32(rng.randn(n)), f32(rng.randn(m, n))
+  xd = to_dev(x, dtype).requires_grad_(True)
+  wd, bd = to_dev(w).requires_grad_(True), to_dev(b).requires_grad_(True)
+  y = ops.fully_connected(xd, wd, bd)
+  assert type(y.grad_fn).__name__ == ('FcFnBackward' if n <= k else 'AddRowBiasFnBackward') and y.dtype == torch.float32
+  y.backward(to_dev(g))
+  what = 'fc (%d, %d, %d)' % (m, n, k)
+  ry, rgx, rgw, rgb = x @ w + b, g @ w.T, x.T @ g, g.sum(0)
+  mgw, mgb = np.abs(x).T @ np.abs(g), np.abs(g).sum(0)
+  _ew_note('fc y', dname, E.assert_elementwise(host(y), ry, E.conv_bound(ry, np.abs(x) @ np.abs(w) + np.abs(b), k + 1, 'f32'), what + ' y'))
+  _ew_note('fc gx', dname, E.assert_elementwise(host(xd.grad), rgx, E.conv_bound(rgx, np.abs(g) @ np.abs(w).T, n, dtype), what + ' gx'))
+  _ew_note('fc gw', dname, E.assert_elementwise(host(wd.grad), rgw, E.wgrad_bound(rgw, mgw, m), what + ' gw'))
+  _ew_note('fc gb', dname, E.assert_elementwise(host(bd.grad), rgb, E.wgrad_bound(rgb, mgb, m), what + ' gb'))
+  # gradient sinks that hold seeded values (FcFn adds into them; the composition's GemmFn hands its gradients to autograd)
+  sw0, sb0 = f32(rng.randn(k, n)), f32(rng.randn(n))
+  sw, sb = to_dev(sw0), to_dev(sb0)
+  ops.GradSink.clear()
+  ops.GradSink.register(wd, sw)
+  ops.GradSink.register(bd, sb)
+  wd.grad = bd.grad = xd.grad = None
+  try:
+    ops.fully_connected(xd, wd, bd).backward(to_dev(g))
+    if n <= k:
+      assert wd.grad is None and bd.grad is None
+      _ew_note('fc gw sink', dname, E.assert_elementwise(host(sw), sw0 + rgw, E.wgrad_bound(sw0 + rgw, mgw + np.abs(sw0), m + 1), what + ' gw sink'))
+      _ew_note('fc gb sink', dname, E.assert_elementwise(host(sb), sb0 + rgb, E.wgrad_bound(sb0 + rgb, mgb + np.abs(sb0), m + 1), what + ' gb sink'))
+    # gx alone: a no_param_grads pass (the gradient penalty's inner gradient) leaves the registered parameters' gradients alone
+    keep = [t.clone() for t in (sw, sb)]
+    wd.grad = bd.grad = xd.grad = None
+    with ops.no_param_grads():
+      ops.fully_connected(xd, wd, bd).backward(to_dev(g))
+    assert wd.grad is None and bd.grad is None and torch.equal(sw, keep[0]) and torch.equal(sb, keep[1])
+    E.assert_elementwise(host(xd.grad), rgx, E.conv_bound(rgx, np.abs(g) @ np.abs(w).T, n, dtype), what + ' gx alone')
+  finally:
+    ops.GradSink.clear()
+
+
+POINT_SIZES = [1, 255, 257, 16384, 16385, 3 * 16384 + 5, 4 * 32 * 32 * 64]
+
+
+@pytest.mark.parametrize('dname', sorted(EW_DTYPES))
+@pytest.mark.parametrize('numel', POINT_SIZES)
+def test_tanh_mul3_scale_dev_and_dot_elementwise(ops, numel, dname):
+  """tg_tanh_fwd / _bwd, tg_mul3 (TanhBwdFn's backward), tg_scale_dev and tg_dot, each on the operands it reads, from one
+  element to 4 x 32 x 32 x 64 (what the attention layer's gamma sees), across tg_dot's 16384 elements per partial.  tanh inputs
+  include +-20, +-1e-4 and 0.  Pointwise: u |ref| + (1 + u) ops 2^-24 mag -- tanh_bwd g (1 - y^2): 3 operations on |g| (1 + y^2);
+  mul3: 3; scale_dev: 1 -- tanh's own error is E of the float32 restatement (torch on the CPU) at m = 16.  tg_dot:
+  reduction_bound with the chain of its two stages (elementwise.dot_chain)."""
+  import twingan_amd.ops as O
+  dtype = EW_DTYPES[dname]
+  u = E.unit_roundoff(dtype)
+  rng = np.random.RandomState(numel % 9973)
+  x = rng.randn(numel) * 2.0
+  for i, v in enumerate((20.0, -20.0, 1e-4, -1e-4, 0.0)):
+    if i * 50 < numel:
+      x[(i * 50) % numel] = v
+  x, g, v = _round_dt(x, dtype), _round_dt(rng.randn(numel), dtype), _round_dt(rng.randn(numel), dtype)
+  xt = torch.from_numpy(x)
+  y64 = torch.tanh(xt).numpy()
+  y32 = torch.tanh(xt.float()).double().numpy()
+  yd = ops.tanh(to_dev(x, dtype))
+  _ew_note('tanh fwd', dname, E.assert_elementwise(host(yd), y64, E.e32_bound(y64, E.e32(y32, y64), dtype), 'tanh %d' % numel))
+  pw = lambda ref, mag, n_ops: u * np.abs(ref) + (1 + u) * n_ops * E.U32 * np.abs(mag) + E.tiny(dtype)
+  y = _round_dt(y64, dtype)      # the stored y the backward reads
+  gd, vd, ysd = to_dev(g, dtype), to_dev(v, dtype), to_dev(y, dtype)
+  st, dt = torch.cuda.current_stream().cuda_stream, O._dt(gd)
+  out = torch.empty_like(gd)
+  O.call('tg_tanh_bwd', gd.data_ptr(), ysd.data_ptr(), out.data_ptr(), numel, dt, st)
+  _ew_note('tanh bwd', dname, E.assert_elementwise(host(out), g * (1 - y * y), pw(g * (1 - y * y), np.abs(g) * (1 + y * y), 3), 'tanh_bwd'))
+  O.call('tg_mul3', ysd.data_ptr(), gd.data_ptr(), vd.data_ptr(), out.data_ptr(), -2.0, numel, dt, st)
+  _ew_note('mul3', dname, E.assert_elementwise(host(out), -2.0 * y * g * v, pw(-2.0 * y * g * v, y * g * v, 3), 'mul3'))
+  gam = np.float32(0.7)
+  sc = ops.scale_dev(gd, to_dev(np.array([gam])))
+  _ew_note('scale_dev', dname, E.assert_elementwise(host(sc), g * float(gam), pw(g * float(gam), g * float(gam), 1), 'scale_dev'))
+  d = ops.DotFn.apply(gd, vd)
+  L, nparts, per = E.dot_chain(numel)
+  bound = E.reduction_bound(np.abs(g * v).sum(), L, term_ops=1)
+  r = abs(d.item() - (g * v).sum()) / bound
+  print('[dot] %s numel %d: %d partials of %d, L %d, ratio %.3f' % (dname, numel, nparts, per, L, r))
+  assert r <= 1.0, (d.item(), (g * v).sum(), bound)
+  _ew_note('dot', dname, r)
+  if nparts > 1:      # the test's own power: the last partial left out moves the sum by more than the bound
+    assert abs((g * v)[(nparts - 1) * per:].sum()) > bound, (nparts, per, bound)
+
+
+def test_tanh_and_scale_second_order_at_the_attention_shape_bf16(ops):
+  """The pattern of test_tanh_and_scale_second_order -- y = gamma tanh(x), gx = d <y, w1> / d x with create_graph, then the
+  gradients of <gx, w2> towards x and gamma -- at 4 x 32 x 32 x 64 in bf16, element-wise.  With t = tanh(x), Et = u |t| + 16 E32
+  the error of the STORED tanh, and every stored intermediate one more u of its magnitude:
+      y      = gamma t                          stored once:       u |y| + |gamma| Et + 1 op
+      gx     = g1 (1 - t^2),  g1 = rnd(w1 gamma)   two stores:        2 u mag + 2 |t g1| Et + 4 ops,  mag = |g1| (1 + t^2)
+      d x    = rnd(rnd(-2 t g1 w2) (1 - t^2))      three stores:      3 u mag + 2 |g1 w2| (1 + 3 t^2) Et + 7 ops,  mag = 2 |t g1 w2| (1 + t^2)
+      d gamma = sum w1 rnd(w2 (1 - t^2))           fp32, tg_dot:      sum [u + 3 ops] |w1 w2| (1 + t^2) + 2 |t w1 w2| Et, + the dot's chain"""
+  dtype, dname, numel = torch.bfloat16, 'bf16', 4 * 32 * 32 * 64
+  u = E.unit_roundoff(dtype)
+  rng = np.random.RandomState(131)
+  x, w1, w2 = (_round_dt(rng.randn(4, 32 * 32, 64), dtype) for _ in range(3))
+  gam = float(np.float32(0.7))
+  xd, gd = to_dev(x, dtype).requires_grad_(True), to_dev(np.array([gam])).requires_grad_(True)
+  y = ops.scale_dev(ops.tanh(xd), gd)
+  gx, = torch.autograd.grad(y, xd, grad_outputs=to_dev(w1, dtype), create_graph=True)
+  torch.autograd.backward(gx, to_dev(w2, dtype))
+  t = np.tanh(x)
+  Et = u * np.abs(t) + 16 * E.e32(torch.tanh(torch.from_numpy(x).float()).double().numpy(), t)
+  ops32 = lambda n_ops, mag: n_ops * E.U32 * mag
+  g1 = w1 * gam
+  r_y = gam * t
+  b_y = u * np.abs(r_y) + (1 + u) * (abs(gam) * Et + ops32(1, np.abs(r_y))) + E.tiny(dtype)
+  r_gx, m_gx = g1 * (1 - t * t), np.abs(g1) * (1 + t * t)
+  b_gx = (1 + u) ** 2 * (2 * u * m_gx + 2 * np.abs(t * g1) * Et + ops32(4, m_gx)) + E.tiny(dtype)
+  r_dx, m_dx = -2 * t * g1 * w2 * (1 - t * t), 2 * np.abs(t * g1 * w2) * (1 + t * t)
+  b_dx = (1 + u) ** 3 * (3 * u * m_dx + 2 * np.abs(g1 * w2) * (1 + 3 * t * t) * Et + ops32(7, m_dx)) + 3 * E.tiny(dtype)
+  _ew_note('tanh scale 2nd order y', dname, E.assert_elementwise(host(y), r_y, b_y, 'y'))
+  _ew_note('tanh scale 2nd order gx', dname, E.assert_elementwise(host(gx), r_gx, b_gx, 'gx'))
+  _ew_note('tanh scale 2nd order d x', dname, E.assert_elementwise(host(xd.grad), r_dx, b_dx, 'd x'))
+  m_dg = np.abs(w1 * w2) * (1 + t * t)
+  L, _, _ = E.dot_chain(numel)
+  r_dg = (w1 * w2 * (1 - t * t)).sum()
+  b_dg = ((u + 3 * E.U32) * m_dg + 2 * np.abs(t * w1 * w2) * Et).sum() * (1 + u) + E.reduction_bound(m_dg.sum(), L, term_ops=1)
+  r = abs(gd.grad.item() - r_dg) / b_dg
+  print('[tanh scale 2nd order] d gamma got %.9g ref %.9g ratio %.3f' % (gd.grad.item(), r_dg, r))
+  assert r <= 1.0
+  _ew_note('tanh scale 2nd order d gamma', dname, r)
+
+
+# ------------------------------------------------------------------------------------------------ preprocessing, through the C ABI
+PRE_U = {'f32': 0.0, 'f16': 2.0 ** -11, 'bf16': 2.0 ** -8}
+PRE_PRECISION = {'f32': 'fp32', 'f16': 'fp16', 'bf16': 'bf16'}
+
+
+@functools.lru_cache(maxsize=None)
+def _pre_sources():
+  """Nine decoded images: 1 x 1, one row, one column (sources SMALLER than every target but hw = 1: up-sampling, where an
+  unclamped bottom / right tap reads past the image), 2 x 3 all white, 5 x 5 all black, 31 x 33 grey (three equal channels:
+  saturate's s = 0), 40 x 13, 64 x 64 and 3 x 200 (down-sampling in one axis, up-sampling in the other)."""
+  rng = np.random.RandomState(90)
+  out = []
+  for h, w in ((1, 1), (1, 7), (7, 1), (2, 3), (5, 5), (31, 33), (40, 13), (64, 64), (3, 200)):
+    im = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
+    if (h, w) == (2, 3):
+      im[:] = 255
+    elif (h, w) == (5, 5):
+      im[:] = 0
+    elif (h, w) == (31, 33):
+      im[:] = im[:, :, :1]
+    out.append(im)
+  return out
+
+
+def _pre_aug(n):
+  """Flips alternate over the batch (so a flip meets every planted crop rectangle); brightness delta at +-32/255 and the
+  saturation factor at 1.4999 and 0.5 (the ends of their ranges) in both orderings, the remaining images random draws."""
+  rng = np.random.RandomState(91)
+  aug = np.zeros((n, 4), np.float32)
+  aug[:, 0] = np.arange(n) % 2
+  aug[:, 1] = (np.arange(n) // 2) % 2
+  aug[:, 2] = rng.uniform(-32.0 / 255.0, 32.0 / 255.0, n)
+  aug[:, 3] = rng.uniform(0.5, 1.5, n)
+  aug[:4, 2] = np.float32([32.0 / 255.0, -32.0 / 255.0, -32.0 / 255.0, 32.0 / 255.0])
+  aug[:4, 3] = np.float32([1.4999, 0.5, 1.4999, 0.5])
+  return aug
+
+
+def _pre_crops(n, mid, hw):
+  """(cy, cx, ch, cw): the whole mid x mid image, its last pixel alone, its last column -- twice over, so each meets both
+  flips -- then draws of the host helper.  hw = 1 has mid = 1: only the whole-image rectangle exists."""
+  from twingan_amd import data as D
+  crop = D.draw_crops(n, mid, 0.8, np.random.default_rng(92))
+  if mid == 1:
+    crop[:] = (0, 0, 1, 1)
+    return crop
+  planted = [(0, 0, mid, mid), (mid - 1, mid - 1, 1, 1), (0, mid - 1, mid, 1)]
+  for i in range(min(6, n)):
+    crop[i] = planted[i % 3]
+  return crop
+
+
+def _pre_launch(pre, tables, color_space=None, mid=None):
+  """tg_preprocess_images_crop through ops.call, as data.Preprocessor.run does it, from tables packed on the host."""
+  import twingan_amd.ops as O
+  from twingan_amd import data as D
+  d = [t.clone().to(dev()) for t in tables]
+  n = tables[1].numel()
+  out = torch.full((n, pre.hw, pre.hw, 3), float('nan'), dtype=pre.dtype, device=dev())
+  O.call('tg_preprocess_images_crop', d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[4].data_ptr() if len(d) > 4 else 0,
+         d[3].data_ptr(), out.data_ptr(), n, pre.hw, pre.mid if mid is None else mid,
+         D.COLOR_SPACES[pre.color_space] if color_space is None else color_space, O._dt(out), torch.cuda.current_stream().cuda_stream)
+  return out
+
+
+def _pre_check(what, dname, pre, images, want, aug=None, crop=None, mode_offsets=None):
+  """The batch against the oracle, element-wise: u |want| + 3e-6 (the project's own fp32 figure for the two-stage path); then
+  every image of the batch bit-identical to the same image preprocessed alone."""
+  out = _pre_launch(pre, pre.pack(images, aug, crop, mode_offsets=mode_offsets))
+  want = np.stack(want)
+  _ew_note('preprocess', dname, E.assert_elementwise(host(out), want, PRE_U[dname] * np.abs(want) + 3e-6, what))
+  bits = torch.int32 if pre.dtype == torch.float32 else torch.int16
+  for i, im in enumerate(images):
+    one = _pre_launch(pre, pre.pack([im], None if aug is None else aug[i:i + 1], None if crop is None else crop[i:i + 1],
+                                    mode_offsets=None if mode_offsets is None else mode_offsets[i:i + 1]))
+    assert torch.equal(one.view(bits)[0], out.view(bits)[i]), '%s: image %d of the batch differs from the same image alone' % (what, i)
+
+
+@pytest.mark.parametrize('cropping', [False, True], ids=['plain', 'cropping'])
+@pytest.mark.parametrize('hw', [1, 2, 5, 16, 33])
+def test_preprocess_kernel_elementwise(hw, cropping):
+  """tg_preprocess_images_crop (csrc/preprocess.hip) against oracle.np_ops.preprocess_image, here and not in test_gpu_data.py so
+  that it also runs over the emulated kernels: nine sources (_pre_sources) in one batch, targets of 1, 2, 5, 16 and 33 pixels
+  (a ragged last workgroup at every one: hw^2 is no multiple of 256; 33^2 = 1089 takes five), PAD / CROP / RESHAPE, rgb / yiq /
+  bgr / gray, fp32 / fp16 / bf16, without and with --do_random_cropping (planted rectangles: _pre_crops), flips alternating,
+  the colour draws at the ends of their ranges.  Without cropping also the evaluation call (is_training=False: the kernel still
+  runs saturate(c, 1) and the clip, so the bound is asserted, not equality)."""
+  from twingan_amd import data as D
+  images = _pre_sources()
+  n = len(images)
+  aug = _pre_aug(n)
+  for mode in ('PAD', 'CROP', 'RESHAPE'):
+    for cs in ('rgb', 'yiq', 'bgr', 'gray'):
+      want, crop = None, None
+      for dname in sorted(EW_DTYPES):
+        pre = D.Preprocessor(hw, device='cpu', precision=PRE_PRECISION[dname], resize_mode=mode, do_random_cropping=cropping,
+                             color_space=cs)
+        if cropping:
+          assert pre.crops and pre.mid == int(hw / 0.8)
+          crop = _pre_crops(n, pre.mid, hw)
+        if want is None:
+          want = [N.preprocess_image(im, hw, mode, True, flip=bool(aug[i, 0]), saturation_first=bool(aug[i, 1]), delta=float(aug[i, 2]),
+                                     factor=float(aug[i, 3]), crop=None if crop is None else tuple(crop[i]), color_space=cs)
+                  for i, im in enumerate(images)]
+        _pre_check('preprocess hw %d %s %s %s%s' % (hw, mode, cs, dname, ' cropping' if cropping else ''), dname, pre, images, want,
+                   aug, crop)
+      if not cropping and cs in ('rgb', 'yiq'):
+        ev_want = [N.preprocess_image(im, hw, mode, False, color_space=cs) for im in images]
+        for dname in sorted(EW_DTYPES):
+          ev = D.Preprocessor(hw, device='cpu', precision=PRE_PRECISION[dname], resize_mode=mode, is_training=False, color_space=cs)
+          _pre_check('preprocess evaluation hw %d %s %s %s' % (hw, mode, cs, dname), dname, ev, images, ev_want)
+
+
+@pytest.mark.parametrize('hw', [1, 2, 5, 16, 33])
+def test_preprocess_random_crop_and_reshape_elementwise(hw):
+  """RANDOM_CROP_AND_RESHAPE with initial_crop_hw = hw (the second resize is 1 : 1) and hw + 7: a source smaller than the window
+  is resized up to it whole, a larger one gives a window at a planted corner (first / last possible offset)."""
+  from twingan_amd import data as D
+  images = _pre_sources()
+  aug = _pre_aug(len(images))
+  for c in (hw, hw + 7):
+    offs = [None if c > min(im.shape[:2]) else ((0, 0) if i % 2 else (im.shape[0] - c, im.shape[1] - c)) for i, im in enumerate(images)]
+    want = [N.preprocess_image(im, hw, 'RANDOM_CROP_AND_RESHAPE', True, flip=bool(aug[i, 0]), saturation_first=bool(aug[i, 1]),
+                               delta=float(aug[i, 2]), factor=float(aug[i, 3]), mode_offset=offs[i] or (0, 0), initial_crop_hw=c)
+            for i, im in enumerate(images)]
+    for dname in sorted(EW_DTYPES):
+      pre = D.Preprocessor(hw, device='cpu', precision=PRE_PRECISION[dname], resize_mode='RANDOM_CROP_AND_RESHAPE', initial_crop_hw=c)
+      _pre_check('preprocess window %d -> %d %s' % (c, hw, dname), dname, pre, images, want, aug, mode_offsets=offs)
+
+
+def test_preprocess_kernel_refuses_what_it_cannot_run():
+  """color_space = 4 and a crop table with an intermediate image smaller than the output (mid < hw: an up-sampling crop is not
+  built) are refused; the output keeps its fill."""
+  from twingan_amd import data as D
+  from twingan_amd._lib import TgError
+  images = _pre_sources()[:4]
+  pre = D.Preprocessor(5, device='cpu', precision='fp32', resize_mode='RESHAPE', do_random_cropping=True)
+  tables = pre.pack(images, _pre_aug(4), _pre_crops(4, pre.mid, 5))
+  with pytest.raises(TgError):
+    _pre_launch(pre, tables, color_space=4)
+  with pytest.raises(TgError):
+    _pre_launch(pre, tables, mid=4)
+  assert bool(torch.isfinite(_pre_launch(pre, tables)).all())
