@@ -629,6 +629,50 @@ int tg_msssim(const void* img1, const void* img2, int n, int h, int w, int c, in
               float k2, const float* weights, int levels, float* score, float* ssim, float* cs, float* mean, void* ws,
               size_t ws_bytes, void* stream);
 
+/* Sliced Wasserstein distance between image sets: the evaluation image_generation.py:868-941 (_calc_swd) names and cannot run
+ * (:926-927 raises; :931 asserts that the TF 1.8 implementation "is wrongly normalizing by patch").  The algorithm is section 5
+ * of the PGGAN paper with the reference's parameters (:938: 128 patches per image, 4 repeats of 128 directions), its list of
+ * resolutions hw, hw/2, ... >= 16 (:912-916), its refusal below 16 (:869-871) and the normalisation its comment at :931 asks
+ * for: per channel over all descriptors of a level.  The 1e3 scale (:910) and the result file (:918-925) are the caller's.
+ * Every entry point enqueues on `stream` and returns; none synchronises the host.  N = number of descriptors of a set.
+ *
+ * tg_swd_pyramid: x [n, hw, hw, 3] NHWC (dtype), hw a power of two in 16..512; a pixel enters as float32(pixel) * scale, with
+ * quantize != 0 as clip(rintf(.), 0, 255).  Writes the Laplacian pyramid, fp32, level after level (sides hw, hw/2, ..., 16;
+ * level l at the float offset of the levels before it) into ws (tg_swd_pyramid_workspace_bytes(n, hw); 0 = refused shape).
+ * down = the 5x5 binomial filter [1,4,6,4,1]^2/256 with mirror boundary (d c b | a b c d | c b a) at the even positions, from
+ * LDS-staged halo tiles; up = zero insertion and the same filter times 4, evaluated in polyphase form (no zero-inserted tensor
+ * exists); level l = gauss_l - up(gauss_l+1), the coarsest level stays Gaussian.  Two launches per level transition. */
+size_t tg_swd_pyramid_workspace_bytes(int n, int hw);
+int tg_swd_pyramid(const void* x, int n, int hw, int c, int dtype, float scale, int quantize, void* ws, size_t ws_bytes,
+                   void* stream);
+/* Descriptor gather of one level [n, s, s, 3] (fp32): centres int32 [n * per][2] = (y, x) on the DEVICE, each in [3, s - 3)
+ * (checked by the caller on the host table before upload), descriptor i of image i / per; row i of the result is the 7x7x3
+ * neighbourhood flattened as k = c * 49 + dy * 7 + dx, written to out[row_offset + i][147] (out holds out_rows rows). */
+int tg_swd_descriptors(const float* level, const int* centres, int n, int s, int per, float* out, int64_t row_offset,
+                       int64_t out_rows, void* stream);
+/* Statistics and projection of one set desc [N][147]: per channel mean and 1 / population standard deviation over all N * 49
+ * values (fp64 sums over a partition that depends on N alone; sigma = 0 gives rstd 0, i.e. normalised values 0) -> stats[6]
+ * = mean[3], rstd[3] (fp32, may be NULL); dirs [repeats][147][dirs_per] (unit columns); proj [repeats * dirs_per][Npad]
+ * column-major = the normalised descriptors times the directions (the statistics are folded into the directions: normalised
+ * descriptors are never written), Npad = the next power of two >= N, rows N..Npad-1 = +inf. */
+size_t tg_swd_project_workspace_bytes(int64_t n, int repeats, int dirs_per);
+int tg_swd_project(const float* desc, const float* dirs, int64_t n, int repeats, int dirs_per, float* proj, float* stats, void* ws,
+                   size_t ws_bytes, void* stream);
+/* Sorts each of the `cols` columns keys[col][npad] ascending in place (npad a power of two): a bitonic network, blocks of
+ * tg_swd_sort_block() keys in LDS, the steps whose partner distance reaches the block length as global passes. */
+int tg_swd_sort_block(void);
+int tg_swd_sort_columns(float* keys, int cols, int64_t npad, void* stream);
+/* out[r] = mean over rows i < N and the dirs_per columns of repeat r of |a - b| (a, b [repeats * dirs_per][npad], sorted);
+ * out[repeats] = the mean of those.  Two ordered stages in double: bit-reproducible, no atomics. */
+size_t tg_swd_mean_abs_diff_workspace_bytes(int64_t n, int repeats, int dirs_per);
+int tg_swd_mean_abs_diff(const float* a, const float* b, int64_t n, int64_t npad, int repeats, int dirs_per, float* out, void* ws,
+                         size_t ws_bytes, void* stream);
+/* project (both sets) + sort + mean |difference|: out[repeats + 1] as above, stats[12] (may be NULL) = the two sets' statistics.
+ * n_a != n_b is TG_EINVAL.  ws begins with the two sorted key arrays [repeats * dirs_per][Npad], one after the other. */
+size_t tg_swd_distance_workspace_bytes(int64_t n, int repeats, int dirs_per);
+int tg_swd_distance(const float* desc_a, int64_t n_a, const float* desc_b, int64_t n_b, const float* dirs, int repeats,
+                    int dirs_per, float* out, float* stats, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,17 @@ SIGNATURES = {
     'tg_msssim_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     'tg_msssim': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, POINTER(c_float), c_int,
                           _FP, _FP, _FP, _FP, _P, c_size_t, _P]),
+    'tg_swd_pyramid_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'tg_swd_pyramid': (c_int, [_P, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
+    'tg_swd_descriptors': (c_int, [_FP, _P, c_int, c_int, c_int, _FP, c_int64, c_int64, _P]),
+    'tg_swd_project_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
+    'tg_swd_project': (c_int, [_FP, _FP, c_int64, c_int, c_int, _FP, _FP, _P, c_size_t, _P]),
+    'tg_swd_sort_block': (c_int, []),
+    'tg_swd_sort_columns': (c_int, [_FP, c_int, c_int64, _P]),
+    'tg_swd_mean_abs_diff_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
+    'tg_swd_mean_abs_diff': (c_int, [_FP, _FP, c_int64, c_int64, c_int, c_int, _FP, _P, c_size_t, _P]),
+    'tg_swd_distance_workspace_bytes': (c_size_t, [c_int64, c_int, c_int]),
+    'tg_swd_distance': (c_int, [_FP, c_int64, _FP, c_int64, _FP, c_int, c_int, _FP, _FP, _P, c_size_t, _P]),
     'tg_conv2d_fwd_pool_supported': (c_int, [_D]),
     'tg_conv2d_fwd_pool': (c_int, [_D, _P, _P, _FP, _P, _P, _P]),
     'tg_conv2d_fwd_pool_signs': (c_int, [_D, _P, _P, _FP, _P, _P, _P]),

@@ -465,3 +465,522 @@ extern "C" int tg_msssim(const void* img1, const void* img2, int n, int h, int w
   TG_LAUNCH_CHECK("tg_msssim");
   return TG_OK;
 }
+
+// ---- sliced Wasserstein distance --------------------------------------------------------------------------------------------
+// The evaluation the reference names but cannot run (image_generation.py:868-941 _calc_swd: one route raises :926-927, the other
+// asserts :931 that TF 1.8 "is wrongly normalizing by patch"): section 5 of the PGGAN paper with the reference's parameters
+// (:938: 128 patches per image, 4 x 128 directions; :912-916 resolutions hw, hw/2, ... >= 16; :910 the 1e3 scale).  Stages:
+// Laplacian pyramid (two launches per level transition), descriptor gather, per-channel statistics (fp64, fixed partition)
+// folded into the directions, projection to column-major sort keys, bitonic column sort, mean |difference|.
+namespace {
+
+enum { SW_C = 3, SW_P = 7, SW_K = SW_C * SW_P * SW_P, SW_T = 16, SW_IN = 2 * SW_T + 3, SW_ROWS = 64, SW_COLS = 32,
+       SW_STAT_ROWS = 256, SW_MAD_ROWS = 4096, SW_SORT = 4096, SW_MAXHW = 512 };
+
+// a pixel of the stored image as the metric sees it: float32(pixel) * scale, rounded to the uint8 grid with `quantize`
+template <typename T, bool RAW>
+__device__ __forceinline__ float sw_pixel(const T* p, float scale, int quantize) {
+#pragma clang fp contract(off)
+  float v = ld(p);
+  if (RAW) {
+    v = v * scale;
+    if (quantize) v = fminf(fmaxf(rintf(v), 0.f), 255.f);
+  }
+  return v;
+}
+
+__device__ __forceinline__ int sw_mirror(int i, int s) { return i < 0 ? -i : (i >= s ? 2 * (s - 1) - i : i); }
+
+// down(x): the 5 x 5 binomial filter with mirror boundary at the even positions.  One workgroup = a 16 x 16 tile of the coarse
+// level of one image, from the 35 x 35 fine pixels under it staged in LDS (the coarse side is a power of two >= 16: no ragged tile).
+template <typename T, bool RAW>
+__global__ __launch_bounds__(256) void swd_down_kernel(const T* __restrict__ fine, float* __restrict__ coarse, int s, float scale,
+                                                       int quantize) {
+  __shared__ float tile[SW_IN * SW_IN * SW_C];
+  const int tid = threadIdx.x, sc = s >> 1;
+  const int oy0 = blockIdx.y * SW_T, ox0 = blockIdx.x * SW_T;
+  const T* img = fine + (int64_t)blockIdx.z * s * s * SW_C;
+#pragma unroll 5
+  for (int i = tid; i < SW_IN * SW_IN * SW_C; i += 256) {
+    const int r = i / (SW_IN * SW_C), e = i - r * (SW_IN * SW_C), cx = e / SW_C, ch = e - cx * SW_C;
+    const int gy = sw_mirror(2 * oy0 - 2 + r, s), gx = sw_mirror(2 * ox0 - 2 + cx, s);
+    tile[i] = sw_pixel<T, RAW>(img + ((int64_t)gy * s + gx) * SW_C + ch, scale, quantize);
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+  const float g[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+  float acc[SW_C] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int dy = 0; dy < 5; ++dy) {
+    float row[SW_C] = {0.f, 0.f, 0.f};
+    const float* p = tile + ((2 * ty + dy) * SW_IN + 2 * tx) * SW_C;
+#pragma unroll
+    for (int dx = 0; dx < 5; ++dx)
+#pragma unroll
+      for (int ch = 0; ch < SW_C; ++ch) row[ch] = fmaf(g[dx], p[dx * SW_C + ch], row[ch]);
+#pragma unroll
+    for (int ch = 0; ch < SW_C; ++ch) acc[ch] = fmaf(g[dy], row[ch], acc[ch]);
+  }
+  float* o = coarse + (((int64_t)blockIdx.z * sc + oy0 + ty) * sc + ox0 + tx) * SW_C;
+#pragma unroll
+  for (int ch = 0; ch < SW_C; ++ch) o[ch] = acc[ch];
+}
+
+// up(x) along one axis in polyphase form: output o of 2h reads at most three coarse samples.  The mirror acts on the
+// zero-inserted grid, so the low border reflects (sample -1 is sample 1) and the high border repeats sample h - 1.
+__device__ __forceinline__ void sw_up_taps(int o, int h, int* idx, float* w) {
+  const int i = o >> 1, hi = min(i + 1, h - 1);
+  if (o & 1) {
+    idx[0] = i, idx[1] = hi, idx[2] = i;
+    w[0] = 0.5f, w[1] = 0.5f, w[2] = 0.f;
+  } else {
+    idx[0] = i == 0 ? 1 : i - 1, idx[1] = i, idx[2] = hi;
+    w[0] = 0.125f, w[1] = 0.75f, w[2] = 0.125f;
+  }
+}
+
+// lap = fine - up(coarse), one thread per fine pixel; coarse == nullptr: the level itself (a one-level pyramid).  `out` may be
+// `fine` (levels >= 1 are rewritten in place: a thread reads only its own fine pixel).
+template <typename T, bool RAW>
+__global__ __launch_bounds__(256) void swd_lap_kernel(const T* fine, const float* __restrict__ coarse, float* out, int s,
+                                                      int64_t pixels, float scale, int quantize) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= pixels) return;
+  const int x = (int)(idx & (s - 1)), y = (int)((idx / s) & (s - 1)), h = s >> 1;
+  const int64_t b = idx / ((int64_t)s * s);
+  float v[SW_C], u[SW_C] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ch = 0; ch < SW_C; ++ch) v[ch] = sw_pixel<T, RAW>(fine + idx * SW_C + ch, scale, quantize);
+  if (coarse) {
+    int iy[3], ix[3];
+    float wy[3], wx[3];
+    sw_up_taps(y, h, iy, wy);
+    sw_up_taps(x, h, ix, wx);
+    const float* cimg = coarse + b * h * h * SW_C;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      float row[SW_C] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const float* p = cimg + ((int64_t)iy[a] * h + ix[q]) * SW_C;
+#pragma unroll
+        for (int ch = 0; ch < SW_C; ++ch) row[ch] = fmaf(wx[q], p[ch], row[ch]);
+      }
+#pragma unroll
+      for (int ch = 0; ch < SW_C; ++ch) u[ch] = fmaf(wy[a], row[ch], u[ch]);
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < SW_C; ++ch) out[idx * SW_C + ch] = v[ch] - u[ch];
+}
+
+// rows [N, 147] of 7 x 7 x 3 neighbourhoods, k = c * 49 + dy * 7 + dx; one thread per output value, so a row is one contiguous
+// 588-byte write.  The host checked the centres; the clamp only keeps a corrupted table inside the image.
+__global__ __launch_bounds__(256) void swd_desc_kernel(const float* __restrict__ level, const int* __restrict__ centres,
+                                                       float* __restrict__ out, int s, int per, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t row = idx / SW_K;
+  const int k = (int)(idx - row * SW_K), ch = k / (SW_P * SW_P), r = k - ch * (SW_P * SW_P), dy = r / SW_P, dx = r - dy * SW_P;
+  const int cy = min(max(centres[2 * row], 3), s - 4), cx = min(max(centres[2 * row + 1], 3), s - 4);
+  out[idx] = level[(((row / per) * s + cy - 3 + dy) * s + cx - 3 + dx) * SW_C + ch];
+}
+
+// block-wide sum in double; the result is valid in every thread.  red: __shared__ double[>= blockDim / 64]
+__device__ __forceinline__ double sw_block_sum(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  double r = 0.0;
+  for (int i = 0; i < nw; ++i) r += red[i];
+  return r;
+}
+
+// statistics, stage 1: per channel sum and sum of squares of (x - x0[c]) over a FIXED chunk of 256 rows, in double (x0 = the
+// set's first value of the channel: a flat channel sums exact zeros, and the squares stay small next to a large DC offset).
+// The partition depends on N alone, never on the launch.
+__global__ __launch_bounds__(256) void swd_stats_kernel(const float* __restrict__ desc, double* __restrict__ partial, int64_t N) {
+  __shared__ double red[4];
+  const int64_t r0 = (int64_t)blockIdx.x * SW_STAT_ROWS;
+  const int n = (int)(N - r0 < SW_STAT_ROWS ? N - r0 : SW_STAT_ROWS) * SW_K;
+  const float x0[SW_C] = {desc[0], desc[SW_P * SW_P], desc[2 * SW_P * SW_P]};
+  double s1[SW_C] = {0.0, 0.0, 0.0}, s2[SW_C] = {0.0, 0.0, 0.0};
+  const float* p = desc + r0 * SW_K;
+  for (int e = threadIdx.x; e < n; e += 256) {
+    const int ch = (e % SW_K) / (SW_P * SW_P);
+    const double d = (double)p[e] - (double)x0[ch];
+    s1[ch] += d;
+    s2[ch] += d * d;
+  }
+  for (int ch = 0; ch < SW_C; ++ch) {
+    const double a = sw_block_sum(s1[ch], red), q = sw_block_sum(s2[ch], red);
+    if (threadIdx.x == 0) {
+      partial[blockIdx.x * 6 + ch] = a;
+      partial[blockIdx.x * 6 + 3 + ch] = q;
+    }
+  }
+}
+
+// statistics, stage 2, and the fold: every workgroup adds the chunk sums in the same fixed order, then a thread per column
+// writes dirs'[k][col] = dirs[r][k][d] * rstd[c(k)] and the column's offset.  The projection subtracts the fp32 mean while it
+// stages a row (so no large products cancel); the offset carries what that rounding of the mean left: (mean - fp32(mean)) . dirs'.
+__global__ __launch_bounds__(256) void swd_fold_kernel(const float* __restrict__ desc, const double* __restrict__ partial,
+                                                       const float* __restrict__ dirs, float* __restrict__ dirs2,
+                                                       float* __restrict__ off, float* __restrict__ statf, float* __restrict__ stats_out,
+                                                       int64_t N, int nparts, int R, int D) {
+  __shared__ double red[4];
+  double mean[SW_C], rstd[SW_C];
+  for (int ch = 0; ch < SW_C; ++ch) {
+    double a = 0.0, q = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+      a += partial[i * 6 + ch];
+      q += partial[i * 6 + 3 + ch];
+    }
+    a = sw_block_sum(a, red);
+    q = sw_block_sum(q, red);
+    const double m = (double)N * (SW_P * SW_P), d = a / m, var = q / m - d * d;
+    mean[ch] = (double)desc[ch * SW_P * SW_P] + d;
+    rstd[ch] = var > 0.0 ? 1.0 / sqrt(var) : 0.0;      // sigma = 0: the channel's normalised values are 0
+  }
+  if (blockIdx.x == 0 && threadIdx.x < SW_C) {
+    const int ch = threadIdx.x;
+    statf[ch] = (float)mean[ch];
+    statf[3 + ch] = (float)rstd[ch];
+    if (stats_out) {
+      stats_out[ch] = (float)mean[ch];
+      stats_out[3 + ch] = (float)rstd[ch];
+    }
+  }
+  const int RD = R * D, col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= RD) return;
+  const int r = col / D, d = col - r * D;
+  double o = 0.0;
+  for (int k = 0; k < SW_K; ++k) {
+    const int ch = k / (SW_P * SW_P);
+    const float w = (float)((double)dirs[((int64_t)r * SW_K + k) * D + d] * rstd[ch]);
+    dirs2[(int64_t)k * RD + col] = w;
+    o += (mean[ch] - (double)(float)mean[ch]) * (double)w;
+  }
+  off[col] = (float)o;
+}
+
+// proj[col][row] = sum_k (desc[row][k] - mean[c(k)]) * dirs'[k][col] - off[col], column-major [R D][Npad] so that a sort key
+// stream is contiguous; rows N .. Npad - 1 are +inf.  One workgroup stages 64 centred rows in LDS once and walks all R D
+// columns in chunks of 32 (lane = row: stride 147 floats is odd, no bank conflict; a wave shares its 8 directions: broadcast reads).
+__global__ __launch_bounds__(256) void swd_project_kernel(const float* __restrict__ desc, const float* __restrict__ dirs2,
+                                                          const float* __restrict__ off, const float* __restrict__ statf,
+                                                          float* __restrict__ proj, int64_t N, int64_t Npad, int RD) {
+  __shared__ float rows[SW_ROWS * SW_K];
+  __shared__ __attribute__((aligned(16))) float dch[SW_K * SW_COLS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t r0 = (int64_t)blockIdx.x * SW_ROWS;
+  const float m[SW_C] = {statf[0], statf[1], statf[2]};
+#pragma unroll 4
+  for (int i = tid; i < SW_ROWS * SW_K; i += 256) {
+    const int row = i / SW_K, k = i - row * SW_K;
+    rows[i] = r0 + row < N ? desc[(r0 + row) * SW_K + k] - m[k / (SW_P * SW_P)] : 0.f;
+  }
+  const int64_t gr = r0 + lane;
+  for (int c0 = 0; c0 < RD; c0 += SW_COLS) {
+    __syncthreads();
+    for (int i = tid; i < SW_K * SW_COLS; i += 256) {
+      const int k = i / SW_COLS, j = i - k * SW_COLS;
+      dch[i] = c0 + j < RD ? dirs2[(int64_t)k * RD + c0 + j] : 0.f;
+    }
+    __syncthreads();
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float* a = rows + lane * SW_K;
+    const float* d = dch + wv * 8;
+#pragma unroll 7
+    for (int k = 0; k < SW_K; ++k) {
+      const float av = a[k];
+      const f32x4 d0 = *reinterpret_cast<const f32x4*>(d + k * SW_COLS), d1 = *reinterpret_cast<const f32x4*>(d + k * SW_COLS + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[j] = fmaf(av, d0[j], acc[j]);
+        acc[4 + j] = fmaf(av, d1[j], acc[4 + j]);
+      }
+    }
+    if (gr < Npad) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int col = c0 + wv * 8 + j;
+        if (col < RD) proj[(int64_t)col * Npad + gr] = gr < N ? acc[j] - off[col] : INFINITY;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void sw_cmpx(float& a, float& b, bool up) {
+  if (up ? a > b : a < b) {
+    const float t = a;
+    a = b;
+    b = t;
+  }
+}
+
+// Bitonic network over a column of Npad = 2^m keys.  One workgroup holds `nloc` = min(SW_SORT, Npad) keys in LDS.  FULL: every
+// merge up to nloc (the start of the sort).  Otherwise the steps j = nloc / 2 .. 1 of the merge of size k, whose steps
+// j >= nloc ran as global passes.  The direction of a compare-exchange comes from the key's index in the whole column.
+template <bool FULL>
+__global__ __launch_bounds__(256) void swd_sort_local_kernel(float* __restrict__ keys, int64_t Npad, int nloc, int64_t kmerge) {
+  __shared__ float sk[SW_SORT];
+  const int tid = threadIdx.x;
+  const int64_t g0 = (int64_t)blockIdx.x * nloc;
+  float* base = keys + (int64_t)blockIdx.y * Npad + g0;
+  for (int i = tid; i < nloc; i += 256) sk[i] = base[i];
+  __syncthreads();
+  for (int64_t k = FULL ? 2 : kmerge; k <= (FULL ? (int64_t)nloc : kmerge); k <<= 1) {
+    for (int j = k >> 1 < nloc >> 1 ? (int)(k >> 1) : nloc >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (nloc >> 1); t += 256) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        sw_cmpx(sk[i], sk[i + j], ((g0 + i) & k) == 0);
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = tid; i < nloc; i += 256) base[i] = sk[i];
+}
+
+// one step j >= SW_SORT of the merge of size k, in global memory: a thread owns four adjacent pairs (i, i + j)
+__global__ __launch_bounds__(256) void swd_sort_global_kernel(float* __restrict__ keys, int64_t Npad, int64_t k, int64_t j) {
+  const int64_t t = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (t >= (Npad >> 1)) return;
+  const int64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+  float* base = keys + (int64_t)blockIdx.y * Npad;
+  f32x4 a = *reinterpret_cast<const f32x4*>(base + i), b = *reinterpret_cast<const f32x4*>(base + i + j);
+  const bool up = (i & k) == 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float x = a[q], y = b[q];
+    sw_cmpx(x, y, up);
+    a[q] = x, b[q] = y;
+  }
+  *reinterpret_cast<f32x4*>(base + i) = a;
+  *reinterpret_cast<f32x4*>(base + i + j) = b;
+}
+
+// mean |a - b|, stage 1: one workgroup per (fixed chunk of 4096 rows, column), in double
+__global__ __launch_bounds__(256) void swd_mad_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                      double* __restrict__ partial, int64_t N, int64_t Npad) {
+  __shared__ double red[4];
+  const int64_t r0 = (int64_t)blockIdx.x * SW_MAD_ROWS, o = (int64_t)blockIdx.y * Npad;
+  const int n = (int)(N - r0 < SW_MAD_ROWS ? N - r0 : SW_MAD_ROWS);
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)fabsf(a[o + r0 + i] - b[o + r0 + i]);
+  s = sw_block_sum(s, red);
+  if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// stage 2: the chunk sums of a repeat's D columns in a fixed order -> out[r]; out[R] = the mean over the repeats
+__global__ __launch_bounds__(256) void swd_mad_final_kernel(const double* __restrict__ partial, float* __restrict__ out, int64_t N,
+                                                            int nchunks, int R, int D) {
+  __shared__ double red[4];
+  double total = 0.0;
+  for (int r = 0; r < R; ++r) {
+    const double* p = partial + (int64_t)r * D * nchunks;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < D * nchunks; i += 256) s += p[i];
+    s = sw_block_sum(s, red) / ((double)N * (double)D);
+    total += s;
+    if (threadIdx.x == 0) out[r] = (float)s;
+  }
+  if (threadIdx.x == 0) out[R] = (float)(total / (double)R);
+}
+
+inline bool sw_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
+inline bool sw_hw_ok(int hw) { return hw >= 16 && hw <= SW_MAXHW && sw_pow2(hw); }
+inline int64_t sw_npad(int64_t n) {
+  int64_t p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+inline bool sw_count_ok(int64_t n, int r, int d) {
+  return n > 0 && n <= ((int64_t)1 << 24) && r > 0 && d > 0 && (int64_t)r * d <= 65535;
+}
+inline size_t sw_project_parts(int64_t n) { return (size_t)((n + SW_STAT_ROWS - 1) / SW_STAT_ROWS); }
+inline size_t sw_mad_chunks(int64_t n) { return (size_t)((n + SW_MAD_ROWS - 1) / SW_MAD_ROWS); }
+
+}  // namespace
+
+extern "C" int tg_swd_sort_block(void) { return SW_SORT; }
+
+extern "C" size_t tg_swd_pyramid_workspace_bytes(int n, int hw) {
+  if (n <= 0 || n > 65535 || !sw_hw_ok(hw)) return 0;
+  size_t bytes = 0;
+  for (int s = hw; s >= 16; s >>= 1) bytes += (size_t)n * s * s * SW_C * sizeof(float);
+  return bytes;
+}
+
+extern "C" int tg_swd_pyramid(const void* x, int n, int hw, int c, int dtype, float scale, int quantize, void* ws, size_t ws_bytes,
+                              void* stream) {
+  TG_CHECK(x && ws, TG_EINVAL, "tg_swd_pyramid: null argument");
+  TG_CHECK(sw_hw_ok(hw), TG_EINVAL, "tg_swd_pyramid: hw must be a power of two in 16..%d (got %d; the reference refuses < 16)",
+           SW_MAXHW, hw);
+  TG_CHECK(c == SW_C, TG_EINVAL, "tg_swd_pyramid: descriptors are 7 x 7 x 3: need c = 3 (got %d)", c);
+  TG_CHECK(n > 0 && n <= 65535, TG_EINVAL, "tg_swd_pyramid: 1..65535 images per call (got %d)", n);
+  TG_CHECK(dtype == TG_F32 || dtype == TG_BF16 || dtype == TG_F16, TG_EINVAL, "tg_swd_pyramid: unsupported dtype %d", dtype);
+  TG_CHECK(ws_bytes >= tg_swd_pyramid_workspace_bytes(n, hw), TG_EINVAL, "tg_swd_pyramid: pyramid storage too small");
+  TG_CHECK(tg_aligned16(ws), TG_EALIGN, "tg_swd_pyramid: pyramid storage must be 16-byte aligned");
+  hipStream_t st_ = (hipStream_t)stream;
+  float* lvl = (float*)ws;
+  const int64_t px0 = (int64_t)n * hw * hw;
+  float* next = lvl + px0 * SW_C;
+  if (hw >= 32) {      // level 1 from the stored image, then level 0 = image - up(level 1)
+    const dim3 grid(hw / 2 / SW_T, hw / 2 / SW_T, n);
+    TG_DISPATCH_DTYPE(dtype, "tg_swd_pyramid", {
+      hipLaunchKernelGGL((swd_down_kernel<T, true>), grid, dim3(256), 0, st_, (const T*)x, next, hw, scale, quantize);
+    });
+    TG_LAUNCH_CHECK("tg_swd_pyramid");
+  }
+  TG_DISPATCH_DTYPE(dtype, "tg_swd_pyramid", {
+    hipLaunchKernelGGL((swd_lap_kernel<T, true>), dim3((unsigned)((px0 + 255) / 256)), dim3(256), 0, st_, (const T*)x,
+                       hw >= 32 ? (const float*)next : (const float*)nullptr, lvl, hw, px0, scale, quantize);
+  });
+  TG_LAUNCH_CHECK("tg_swd_pyramid");
+  for (int s = hw / 2; s >= 32; s >>= 1) {
+    lvl = next;
+    const int64_t px = (int64_t)n * s * s;
+    next = lvl + px * SW_C;
+    hipLaunchKernelGGL((swd_down_kernel<float, false>), dim3(s / 2 / SW_T, s / 2 / SW_T, n), dim3(256), 0, st_, (const float*)lvl,
+                       next, s, 1.f, 0);
+    TG_LAUNCH_CHECK("tg_swd_pyramid");
+    hipLaunchKernelGGL((swd_lap_kernel<float, false>), dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st_, (const float*)lvl,
+                       (const float*)next, lvl, s, px, 1.f, 0);
+    TG_LAUNCH_CHECK("tg_swd_pyramid");
+  }
+  return TG_OK;
+}
+
+extern "C" int tg_swd_descriptors(const float* level, const int* centres, int n, int s, int per, float* out, int64_t row_offset,
+                                  int64_t out_rows, void* stream) {
+  TG_CHECK(level && centres && out, TG_EINVAL, "tg_swd_descriptors: null argument");
+  TG_CHECK(sw_hw_ok(s), TG_EINVAL, "tg_swd_descriptors: level side must be a power of two in 16..%d (got %d)", SW_MAXHW, s);
+  TG_CHECK(n > 0 && per > 0 && (int64_t)n * per <= ((int64_t)1 << 24), TG_EINVAL,
+           "tg_swd_descriptors: need n, per > 0 and n * per <= 2^24 (got %d, %d)", n, per);
+  TG_CHECK(row_offset >= 0 && row_offset + (int64_t)n * per <= out_rows, TG_EINVAL,
+           "tg_swd_descriptors: rows %lld..%lld do not fit a buffer of %lld rows", (long long)row_offset,
+           (long long)(row_offset + (int64_t)n * per), (long long)out_rows);
+  const int64_t total = (int64_t)n * per * SW_K;
+  hipLaunchKernelGGL(swd_desc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, level, centres,
+                     out + row_offset * SW_K, s, per, total);
+  TG_LAUNCH_CHECK("tg_swd_descriptors");
+  return TG_OK;
+}
+
+extern "C" size_t tg_swd_project_workspace_bytes(int64_t n, int repeats, int dirs) {
+  if (!sw_count_ok(n, repeats, dirs)) return 0;
+  const size_t rd = (size_t)repeats * dirs;
+  return ms_align(sw_project_parts(n) * 6 * sizeof(double)) + ms_align(SW_K * rd * sizeof(float)) + ms_align(rd * sizeof(float)) +
+         ms_align(8 * sizeof(float));
+}
+
+extern "C" int tg_swd_project(const float* desc, const float* dirs, int64_t n, int repeats, int dirs_per, float* proj, float* stats,
+                              void* ws, size_t ws_bytes, void* stream) {
+  TG_CHECK(desc && dirs && proj && ws, TG_EINVAL, "tg_swd_project: null argument");
+  TG_CHECK(sw_count_ok(n, repeats, dirs_per), TG_EINVAL,
+           "tg_swd_project: need 1 <= N <= 2^24 rows and 1 <= repeats * dirs <= 65535 (got %lld, %d x %d)", (long long)n, repeats,
+           dirs_per);
+  TG_CHECK(ws_bytes >= tg_swd_project_workspace_bytes(n, repeats, dirs_per), TG_EINVAL, "tg_swd_project: workspace too small");
+  TG_CHECK(tg_aligned16(ws), TG_EALIGN, "tg_swd_project: workspace must be 16-byte aligned");
+  hipStream_t st_ = (hipStream_t)stream;
+  const int rd = repeats * dirs_per, parts = (int)sw_project_parts(n);
+  const int64_t npad = sw_npad(n);
+  char* wp = (char*)ws;
+  double* partial = (double*)wp;
+  wp += ms_align((size_t)parts * 6 * sizeof(double));
+  float* dirs2 = (float*)wp;
+  wp += ms_align((size_t)SW_K * rd * sizeof(float));
+  float* off = (float*)wp;
+  wp += ms_align((size_t)rd * sizeof(float));
+  float* statf = (float*)wp;
+  hipLaunchKernelGGL(swd_stats_kernel, dim3(parts), dim3(256), 0, st_, desc, partial, n);
+  TG_LAUNCH_CHECK("tg_swd_project");
+  hipLaunchKernelGGL(swd_fold_kernel, dim3((rd + 255) / 256), dim3(256), 0, st_, desc, (const double*)partial, dirs, dirs2, off, statf,
+                     stats, n, parts, repeats, dirs_per);
+  TG_LAUNCH_CHECK("tg_swd_project");
+  hipLaunchKernelGGL(swd_project_kernel, dim3((unsigned)((npad + SW_ROWS - 1) / SW_ROWS)), dim3(256), 0, st_, desc,
+                     (const float*)dirs2, (const float*)off, (const float*)statf, proj, n, npad, rd);
+  TG_LAUNCH_CHECK("tg_swd_project");
+  return TG_OK;
+}
+
+extern "C" int tg_swd_sort_columns(float* keys, int cols, int64_t npad, void* stream) {
+  TG_CHECK(keys, TG_EINVAL, "tg_swd_sort_columns: null argument");
+  TG_CHECK(cols > 0 && cols <= 65535 && sw_pow2(npad) && npad <= ((int64_t)1 << 24), TG_EINVAL,
+           "tg_swd_sort_columns: need 1..65535 columns of a power-of-two length <= 2^24 (got %d x %lld)", cols, (long long)npad);
+  TG_CHECK(npad < 4 || tg_aligned16(keys), TG_EALIGN, "tg_swd_sort_columns: keys must be 16-byte aligned");
+  hipStream_t st_ = (hipStream_t)stream;
+  const int nloc = (int)(npad < SW_SORT ? npad : SW_SORT);
+  const dim3 lgrid((unsigned)(npad / nloc), cols);
+  hipLaunchKernelGGL((swd_sort_local_kernel<true>), lgrid, dim3(256), 0, st_, keys, npad, nloc, (int64_t)0);
+  TG_LAUNCH_CHECK("tg_swd_sort_columns");
+  for (int64_t k = 2 * (int64_t)SW_SORT; k <= npad; k <<= 1) {
+    for (int64_t j = k >> 1; j >= SW_SORT; j >>= 1) {
+      hipLaunchKernelGGL(swd_sort_global_kernel, dim3((unsigned)(npad / 2 / 4 / 256), cols), dim3(256), 0, st_, keys, npad, k, j);
+      TG_LAUNCH_CHECK("tg_swd_sort_columns");
+    }
+    hipLaunchKernelGGL((swd_sort_local_kernel<false>), lgrid, dim3(256), 0, st_, keys, npad, nloc, k);
+    TG_LAUNCH_CHECK("tg_swd_sort_columns");
+  }
+  return TG_OK;
+}
+
+extern "C" size_t tg_swd_mean_abs_diff_workspace_bytes(int64_t n, int repeats, int dirs) {
+  if (!sw_count_ok(n, repeats, dirs)) return 0;
+  return ms_align(sw_mad_chunks(n) * (size_t)repeats * dirs * sizeof(double));
+}
+
+extern "C" int tg_swd_mean_abs_diff(const float* a, const float* b, int64_t n, int64_t npad, int repeats, int dirs, float* out,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  TG_CHECK(a && b && out && ws, TG_EINVAL, "tg_swd_mean_abs_diff: null argument");
+  TG_CHECK(sw_count_ok(n, repeats, dirs) && npad >= n, TG_EINVAL,
+           "tg_swd_mean_abs_diff: need 1 <= N <= Npad, N <= 2^24 and 1 <= repeats * dirs <= 65535 (got %lld, %lld, %d x %d)",
+           (long long)n, (long long)npad, repeats, dirs);
+  TG_CHECK(ws_bytes >= tg_swd_mean_abs_diff_workspace_bytes(n, repeats, dirs), TG_EINVAL, "tg_swd_mean_abs_diff: workspace too small");
+  TG_CHECK(tg_aligned16(ws), TG_EALIGN, "tg_swd_mean_abs_diff: workspace must be 16-byte aligned");
+  const int chunks = (int)sw_mad_chunks(n);
+  hipLaunchKernelGGL(swd_mad_kernel, dim3(chunks, repeats * dirs), dim3(256), 0, (hipStream_t)stream, a, b, (double*)ws, n, npad);
+  TG_LAUNCH_CHECK("tg_swd_mean_abs_diff");
+  hipLaunchKernelGGL(swd_mad_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, out, n, chunks, repeats,
+                     dirs);
+  TG_LAUNCH_CHECK("tg_swd_mean_abs_diff");
+  return TG_OK;
+}
+
+extern "C" size_t tg_swd_distance_workspace_bytes(int64_t n, int repeats, int dirs) {
+  if (!sw_count_ok(n, repeats, dirs)) return 0;
+  const size_t keys = ms_align((size_t)repeats * dirs * (size_t)sw_npad(n) * sizeof(float));
+  const size_t pw = tg_swd_project_workspace_bytes(n, repeats, dirs), mw = tg_swd_mean_abs_diff_workspace_bytes(n, repeats, dirs);
+  return 2 * keys + (pw > mw ? pw : mw);
+}
+
+extern "C" int tg_swd_distance(const float* desc_a, int64_t n_a, const float* desc_b, int64_t n_b, const float* dirs, int repeats,
+                               int dirs_per, float* out, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  TG_CHECK(desc_a && desc_b && dirs && out && ws, TG_EINVAL, "tg_swd_distance: null argument");
+  TG_CHECK(n_a == n_b, TG_EINVAL, "tg_swd_distance: both sets must hold the same number of descriptors (got %lld and %lld)",
+           (long long)n_a, (long long)n_b);
+  TG_CHECK(sw_count_ok(n_a, repeats, dirs_per), TG_EINVAL,
+           "tg_swd_distance: need 1 <= N <= 2^24 rows and 1 <= repeats * dirs <= 65535 (got %lld, %d x %d)", (long long)n_a, repeats,
+           dirs_per);
+  TG_CHECK(ws_bytes >= tg_swd_distance_workspace_bytes(n_a, repeats, dirs_per), TG_EINVAL, "tg_swd_distance: workspace too small");
+  TG_CHECK(tg_aligned16(ws), TG_EALIGN, "tg_swd_distance: workspace must be 16-byte aligned");
+  const int rd = repeats * dirs_per;
+  const int64_t npad = sw_npad(n_a);
+  const size_t keys = ms_align((size_t)rd * (size_t)npad * sizeof(float));
+  float *pa = (float*)ws, *pb = (float*)((char*)ws + keys);
+  void* rest = (char*)ws + 2 * keys;
+  const size_t rest_bytes = ws_bytes - 2 * keys;
+  int rc = tg_swd_project(desc_a, dirs, n_a, repeats, dirs_per, pa, stats, rest, rest_bytes, stream);
+  if (rc != TG_OK) return rc;
+  rc = tg_swd_project(desc_b, dirs, n_b, repeats, dirs_per, pb, stats ? stats + 6 : nullptr, rest, rest_bytes, stream);
+  if (rc != TG_OK) return rc;
+  rc = tg_swd_sort_columns(pa, rd, npad, stream);
+  if (rc != TG_OK) return rc;
+  rc = tg_swd_sort_columns(pb, rd, npad, stream);
+  if (rc != TG_OK) return rc;
+  return tg_swd_mean_abs_diff(pa, pb, n_a, npad, repeats, dirs_per, out, rest, rest_bytes, stream);
+}

@@ -1,11 +1,17 @@
 """Evaluation of a trained stage on the GPU -- the step docs/infer_and_eval.md of the reference calls "Evaluation".
 
-MS-SSIM (libs/ms_ssim.py, the PGGAN diversity metric) is the one metric of the reference that can be run, so it is the
-one built here: ops.msssim is the fused HIP kernel, MsSsim the accumulator with the protocol of the reference's API class
-(ms_ssim.py:174-199), evaluate_translation the scores of a TwinGAN checkpoint: the diversity of what it generates and
-the similarity of the cycle s -> t' -> s_cyc to its source (the quantity the L1 cycle loss trains).  Images stay on the
-device in the model's dtype; nothing synchronises before the final read-out.  The sliced Wasserstein distance and the
-Inception score have no runnable reference (image_generation.py:926-931 raises) and are out of scope."""
+MS-SSIM (libs/ms_ssim.py, the PGGAN diversity metric): ops.msssim is the fused HIP kernel, MsSsim the accumulator with the
+protocol of the reference's API class (ms_ssim.py:174-199).  The sliced Wasserstein distance (--calc_swd,
+image_generation.py:868-941 _calc_swd) has no runnable reference -- one route raises (:926-927), the other asserts that TF
+1.8 "is wrongly normalizing by patch" (:931) -- but the algorithm is fixed: section 5 of the PGGAN paper with the reference's
+parameters (:938), resolutions (:912-916), 1e3 scale (:910) and result file (:918-925), normalised the way its comment asks
+for.  SlicedWasserstein is its accumulator over the ops.swd_* kernels, write_swd_result the file.  Two definitions are this
+project's own: the ``real`` column is the distance between the first and the second half of the reals in feed order (the
+estimator's noise floor at half the sample), and a channel with sigma = 0 normalises to 0 (not NaN).
+evaluate_translation scores a TwinGAN checkpoint: the diversity of what it generates, the similarity of the cycle
+s -> t' -> s_cyc to its source (the quantity the L1 cycle loss trains) and, given target-domain images, the SWD between them
+and the translations (real = targets, fake = t_prime_output: twingan.py:762-763).  Images stay on the device in the model's
+dtype; nothing synchronises before the final read-out.  The Inception score needs a pretrained classifier and is out of scope."""
 import torch
 
 from . import ops
@@ -45,14 +51,103 @@ class MsSsim:
     return float(self.sum.item()) / self.num_pairs
 
 
-def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cuda', translate_fn=None):
+class SlicedWasserstein:
+  """begin() / feed(reals, fakes) / end() like MsSsim, for NHWC device minibatches [n, hw, hw, 3] in [0, 1] (fp32 / bf16 /
+  fp16; hw a power of two in 16..512).  feed builds both Laplacian pyramids and gathers ``per`` 7 x 7 x 3 descriptors per image
+  and level into buffers preallocated for ``num_images`` (the reference's swd_num_images) -- no synchronisation; end()
+  normalises, projects on ``repeats`` x ``dirs`` unit directions per level, sorts and returns
+    {'resolutions': [hw, hw/2, ..., 16], 'real': [...], 'fake': [...], 'average': (real, fake)}      (all times 1e3)
+  fake = distance(reals, fakes); real = distance(first half of the reals in feed order, second half) -- this project's
+  definition of the reference's ``real`` column; it needs an even number of images.  Patch centres and directions are inputs of
+  the kernels: drawn from a CPU torch.Generator seeded at begin() (so a seed fixes the result bit for bit) unless injected."""
+
+  def __init__(self, hw, num_images, per=128, repeats=4, dirs=128, scale=255., quantize=True, seed=0):
+    self.resolutions = ops.swd_resolutions(hw)
+    if not self.resolutions or hw & (hw - 1) or hw > 512:      # image_generation.py:869-871: no SWD on small images
+      raise ValueError('SlicedWasserstein: hw must be a power of two in 16..512 (got %d)' % hw)
+    self.hw, self.num_images, self.per, self.repeats, self.dirs = hw, int(num_images), int(per), int(repeats), int(dirs)
+    self.scale, self.quantize, self.seed = float(scale), bool(quantize), seed
+    self.gen = torch.Generator().manual_seed(seed)
+    self.desc = None
+    self.count = 0
+
+  def begin(self, mode=None):
+    self.gen.manual_seed(self.seed)
+    self.count = 0
+
+  def draw_centres(self, n):
+    """One feed's tables: per level (centres of the reals, of the fakes), int32 [n * per, 2] in [3, s - 3), independent draws."""
+    return [tuple(torch.randint(3, s - 3, (n * self.per, 2), generator=self.gen, dtype=torch.int32) for _ in range(2))
+            for s in self.resolutions]
+
+  def draw_dirs(self):
+    """Per level: [repeats, 147, dirs] fp32 Gaussian directions of unit L2 norm over the 147 axis."""
+    out = []
+    for _ in self.resolutions:
+      d = torch.randn(self.repeats, ops.SWD_K, self.dirs, generator=self.gen, dtype=torch.float32)
+      out.append(d / d.norm(dim=1, keepdim=True))
+    return out
+
+  def feed(self, reals, fakes, centres=None):
+    n = reals.shape[0]
+    if tuple(reals.shape) != tuple(fakes.shape) or tuple(reals.shape[1:]) != (self.hw, self.hw, 3):
+      raise ops._lib.TgError('SlicedWasserstein.feed: reals and fakes must both be [n, %d, %d, 3] (got %s and %s)'
+                             % (self.hw, self.hw, tuple(reals.shape), tuple(fakes.shape)))
+    if self.count + n > self.num_images:
+      raise ops._lib.TgError('SlicedWasserstein.feed: %d images fed, the buffers hold %d' % (self.count + n, self.num_images))
+    if self.desc is None:
+      self.desc = [tuple(torch.empty(self.num_images * self.per, ops.SWD_K, dtype=torch.float32, device=reals.device)
+                         for _ in range(2)) for _ in self.resolutions]
+    centres = self.draw_centres(n) if centres is None else centres
+    assert len(centres) == len(self.resolutions), 'centres: one (reals, fakes) pair of tables per level'
+    for which, x in enumerate((reals, fakes)):
+      levels = ops.swd_pyramid(x.contiguous(), self.scale, self.quantize)
+      for l, level in enumerate(levels):
+        ops.swd_descriptors(level, centres[l][which], self.per, out=self.desc[l][which], row_offset=self.count * self.per)
+    self.count += n
+
+  def distances(self, dirs=None):
+    """-> per level (real, fake) device tensors [1], not yet scaled; no synchronisation."""
+    if self.count == 0 or self.count % 2:
+      raise ops._lib.TgError('SlicedWasserstein.end: the real column compares two halves of the reals: feed an even, non-zero '
+                             'number of images (got %d)' % self.count)
+    dirs = self.draw_dirs() if dirs is None else dirs
+    assert len(dirs) == len(self.resolutions), 'dirs: one [repeats, 147, dirs] tensor per level'
+    n, out = self.count * self.per, []
+    for l, (dr, df) in enumerate(self.desc):
+      d = torch.as_tensor(dirs[l], dtype=torch.float32).to(dr.device).contiguous()
+      fake = ops.swd_distance(dr[:n], df[:n], d)[0]
+      real = ops.swd_distance(dr[:n // 2], dr[n // 2:n], d)[0]
+      out.append((real, fake))
+    return out
+
+  def end(self, dirs=None, mode=None):
+    table = torch.stack([torch.cat(p) for p in self.distances(dirs)]).double().cpu() * 1e3      # the only synchronisation
+    real, fake = [float(v) for v in table[:, 0]], [float(v) for v in table[:, 1]]
+    return {'resolutions': list(self.resolutions), 'real': real, 'fake': fake,
+            'average': (sum(real) / len(real), sum(fake) / len(fake))}
+
+
+def write_swd_result(path, result, num_images):
+  """The reference's result file (image_generation.py:918-925) for what SlicedWasserstein.end() returned."""
+  with open(path, 'w') as f:
+    f.write('swd sliced wasserstein score evaluated on %d images.\n' % num_images)
+    f.write('res\treal\tfake\n')
+    for hw, real, fake in zip(result['resolutions'], result['real'], result['fake']):
+      f.write('%d\t%f\t%f\n' % (hw, real, fake))
+    f.write('Average\t%f\t%f\n' % tuple(result['average']))
+
+
+def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cuda', translate_fn=None, targets=None):
   """Scores a TwinGAN stage on ``sources`` (float [N, hw, hw, 3] in [0, 1], N even; tensor or array):
     ms_ssim_diversity: MS-SSIM between consecutive generated images translate(source, to) (pairs 0-1, 2-3, ...; lower =
                        more diverse, the reference's use of the metric);
     ms_ssim_cycle:     MS-SSIM(source, translate(translate(source, to), from)).
   Style-embedding configurations use the encoded style of each translation's own input, as ImageInferer.infer does for
   custom_generated_*_style_source.  ``translate_fn(x, to) -> image batch`` replaces the model (tests: an identity stand-in);
-  with it ``state_dict`` is not read."""
+  with it ``state_dict`` is not read.  With ``targets`` (images of the domain translated to, same shape as ``sources``) the
+  result also holds swd_real, swd_fake (per resolution, times 1e3) and swd_resolutions: SlicedWasserstein at its defaults
+  fed (targets, translate(sources)) batch by batch."""
   assert to in ('s', 't'), to
   cfg = cfg if isinstance(cfg, Config) else Config(**cfg)
   device = torch.device(device)
@@ -72,6 +167,12 @@ def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cud
   diversity, cycle = MsSsim(scale=255.), MsSsim(scale=255.)
   diversity.begin()
   cycle.begin()
+  swd, t_all = None, None
+  if targets is not None:
+    t_all = torch.as_tensor(targets)
+    assert tuple(t_all.shape) == tuple(x_all.shape), 'targets: as many images as sources, of the same size'
+    swd = SlicedWasserstein(x_all.shape[1], x_all.shape[0])
+    swd.begin()
   with torch.cuda.device(device), torch.no_grad():
     for i in range(0, x_all.shape[0], batch):
       x = x_all[i:i + batch].to(device).to(dtype).contiguous()
@@ -79,7 +180,12 @@ def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cud
       back = translate_fn(y, frm).detach()
       diversity.feed(y)
       cycle.feed_pairs(x, back)
+      if swd is not None:
+        swd.feed(t_all[i:i + batch].to(device).to(dtype).contiguous(), y)
     out = {'ms_ssim_diversity': diversity.end(), 'ms_ssim_cycle': cycle.end()}
+    if swd is not None:
+      res = swd.end()
+      out.update(swd_real=res['real'], swd_fake=res['fake'], swd_resolutions=res['resolutions'])
   if store is not None:
     store.close()
   return out

@@ -3003,3 +3003,140 @@ def msssim(img1, img2, max_val=255., scale=1., weights=None, k1=0.01, k2=0.03, r
        (ctypes.c_float * levels)(*wts), levels, _p(score), _p(ssim), _p(cs), _p(mean_), _p(ws), nbytes, _stream(),
        work=('msssim', 0, 2 * img1.numel() * img1.element_size()))
   return (score, ssim, cs, mean_) if return_mean else (score, ssim, cs)
+
+
+# ------------------------------------------------------------------------------------------------
+# sliced Wasserstein distance (image_generation.py:868-941 _calc_swd; PGGAN paper section 5)
+# ------------------------------------------------------------------------------------------------
+SWD_SORT_BLOCK = 4096      # keys one workgroup sorts in LDS (tg_swd_sort_block(); 16 KiB: several workgroups per CU)
+SWD_K = 147                # a descriptor: 7 x 7 x 3, k = c * 49 + dy * 7 + dx
+
+
+def swd_resolutions(hw):
+  """image_generation.py:912-916: hw, hw / 2, ... >= 16."""
+  out = []
+  while hw >= 16:
+    out.append(hw)
+    hw //= 2
+  return out
+
+
+def swd_pyramid(x, scale=255., quantize=True):
+  """Laplacian pyramid of the NHWC batch x [n, hw, hw, 3] (fp32 / bf16 / fp16; hw a power of two in 16..512): a list of fp32
+  levels [n, s, s, 3], s = hw, hw / 2, ..., 16 (views of one buffer); the coarsest level is Gaussian.  A pixel enters as
+  float32(pixel) * scale, with ``quantize`` as clip(rint(.), 0, 255) (the paper's uint8 protocol).  No synchronisation."""
+  if x.dim() != 4:
+    raise _lib.TgError('swd_pyramid: images must have four dimensions [n, hw, hw, 3], not %d' % x.dim())
+  x = x.detach()
+  _chk(x)
+  n, h, w, c = x.shape
+  if h != w:
+    raise _lib.TgError('swd_pyramid: images must be square (got %d x %d)' % (h, w))
+  nbytes = _lib.load().tg_swd_pyramid_workspace_bytes(n, h)      # 0 for a shape the kernel refuses: tg_swd_pyramid says why
+  buf = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=x.device)
+  call('tg_swd_pyramid', _p(x), n, h, c, _dt(x), float(scale), int(bool(quantize)), _p(buf), nbytes, _stream(),
+       work=('swd_pyramid', 0, x.numel() * x.element_size() + nbytes))
+  levels, o = [], 0
+  for s in swd_resolutions(h):
+    levels.append(buf[o:o + n * s * s * 3].view(n, s, s, 3))
+    o += n * s * s * 3
+  return levels
+
+
+def swd_descriptors(level, centres, per, out=None, row_offset=0):
+  """Gathers the 7 x 7 x 3 neighbourhoods of one pyramid level [n, s, s, 3] (fp32) around ``centres``: a HOST table (CPU
+  tensor or array) of n * per integer (y, x) pairs, each in [3, s - 3), descriptor i of image i // per.  Rows
+  [row_offset, row_offset + n * per) of ``out`` [rows, 147] (fp32; allocated when None) are written.  The table is checked here,
+  on the host, before it is uploaded (pinned, asynchronously)."""
+  if level.dim() != 4 or level.dtype != torch.float32 or level.shape[1] != level.shape[2] or level.shape[3] != 3:
+    raise _lib.TgError('swd_descriptors: a level is an fp32 tensor [n, s, s, 3] (got %s %s)' % (tuple(level.shape), level.dtype))
+  _chk(level, out)
+  n, s = level.shape[0], level.shape[1]
+  tab = torch.as_tensor(centres, device='cpu')
+  if tab.is_floating_point() or tuple(tab.shape) != (n * per, 2):
+    raise _lib.TgError('swd_descriptors: centres must be an integer table [%d, 2] (got %s %s)' % (n * per, tuple(tab.shape), tab.dtype))
+  if tab.numel() and (int(tab.min()) < 3 or int(tab.max()) >= s - 3):
+    raise _lib.TgError('swd_descriptors: a centre lies outside [3, %d) (table spans %d..%d)' % (s - 3, int(tab.min()), int(tab.max())))
+  tab = tab.to(torch.int32).contiguous()
+  if level.is_cuda:
+    tab = tab.pin_memory()
+  tab = tab.to(level.device, non_blocking=True)
+  if out is None:
+    out = torch.empty(row_offset + n * per, SWD_K, dtype=torch.float32, device=level.device)
+  if out.dim() != 2 or out.shape[1] != SWD_K or out.dtype != torch.float32:
+    raise _lib.TgError('swd_descriptors: out must be an fp32 tensor [rows, 147]')
+  call('tg_swd_descriptors', _p(level), _p(tab), n, s, int(per), _p(out), int(row_offset), out.shape[0], _stream(),
+       work=('swd_descriptors', 0, 2 * n * per * SWD_K * 4))
+  return out
+
+
+def _swd_sets(desc, dirs, what):
+  if desc.dim() != 2 or desc.shape[1] != SWD_K or desc.dtype != torch.float32:
+    raise _lib.TgError('%s: descriptors are an fp32 tensor [N, 147] (got %s %s)' % (what, tuple(desc.shape), desc.dtype))
+  if dirs.dim() != 3 or dirs.shape[1] != SWD_K or dirs.dtype != torch.float32:
+    raise _lib.TgError('%s: directions are an fp32 tensor [R, 147, D] (got %s %s)' % (what, tuple(dirs.shape), dirs.dtype))
+  _chk(desc, dirs)
+
+
+def swd_npad(n):
+  return 1 << max(int(n) - 1, 0).bit_length()
+
+
+def swd_project(desc, dirs):
+  """desc [N, 147] (one set's descriptors), dirs [R, 147, D] (unit columns) -> (proj [R * D, Npad], mean [3], rstd [3]):
+  the set normalised per channel by its own statistics (over all N * 49 values; sigma = 0 gives 0) times the directions,
+  column-major, Npad = next power of two, rows N.. filled with +inf."""
+  _swd_sets(desc, dirs, 'swd_project')
+  n, (r, _, d) = desc.shape[0], dirs.shape
+  proj = torch.empty(r * d, swd_npad(n), dtype=torch.float32, device=desc.device)
+  stats = torch.empty(6, dtype=torch.float32, device=desc.device)
+  nbytes = _lib.load().tg_swd_project_workspace_bytes(n, r, d)
+  ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=desc.device)
+  call('tg_swd_project', _p(desc), _p(dirs), n, r, d, _p(proj), _p(stats), _p(ws), nbytes, _stream(),
+       work=('swd_project', 2 * n * SWD_K * r * d, 2 * desc.numel() * 4 + proj.numel() * 4))
+  return proj, stats[:3], stats[3:]
+
+
+def swd_sort_columns(proj):
+  """Sorts every row of proj [columns, Npad] (a key stream of the column-major projection; Npad a power of two) ascending, in
+  place; returns it."""
+  if proj.dim() != 2 or proj.dtype != torch.float32:
+    raise _lib.TgError('swd_sort_columns: keys are an fp32 tensor [columns, Npad]')
+  _chk(proj)
+  call('tg_swd_sort_columns', _p(proj), proj.shape[0], proj.shape[1], _stream(), work=('swd_sort', 0, 2 * proj.numel() * 4))
+  return proj
+
+
+def swd_mean_abs_diff(sorted_a, sorted_b, n, repeats):
+  """(mean [1], per_repeat [R]) of |a - b| over the first n rows of the sorted projections [R * D, Npad] (the +inf tail of a
+  column is left out); two ordered reduction stages, bit-reproducible."""
+  if sorted_a.shape != sorted_b.shape or sorted_a.dim() != 2 or sorted_a.dtype != torch.float32 or sorted_b.dtype != torch.float32 \
+      or sorted_a.shape[0] % repeats:
+    raise _lib.TgError('swd_mean_abs_diff: two fp32 tensors [R * D, Npad] of the same shape (got %s and %s)'
+                       % (tuple(sorted_a.shape), tuple(sorted_b.shape)))
+  _chk(sorted_a, sorted_b)
+  d = sorted_a.shape[0] // repeats
+  out = torch.empty(repeats + 1, dtype=torch.float32, device=sorted_a.device)
+  nbytes = _lib.load().tg_swd_mean_abs_diff_workspace_bytes(n, repeats, d)
+  ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=sorted_a.device)
+  call('tg_swd_mean_abs_diff', _p(sorted_a), _p(sorted_b), n, sorted_a.shape[1], repeats, d, _p(out), _p(ws), nbytes, _stream(),
+       work=('swd_mean_abs_diff', 0, 2 * n * sorted_a.shape[0] * 4))
+  return out[repeats:], out[:repeats]
+
+
+def swd_distance(desc_a, desc_b, dirs, return_sorted=False):
+  """Sliced Wasserstein distance between two descriptor sets [N, 147] along dirs [R, 147, D]: (mean [1], per_repeat [R]) on
+  the device (not yet times 1e3), mean_r mean_{i,d} |sort(A dirs_r) - sort(B dirs_r)| of the per-set normalised descriptors;
+  with ``return_sorted`` also the two sorted projections [R * D, Npad].  No synchronisation."""
+  _swd_sets(desc_a, dirs, 'swd_distance')
+  _swd_sets(desc_b, dirs, 'swd_distance')
+  n, (r, _, d) = desc_a.shape[0], dirs.shape
+  out = torch.empty(r + 1, dtype=torch.float32, device=desc_a.device)
+  nbytes = _lib.load().tg_swd_distance_workspace_bytes(n, r, d)
+  ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=desc_a.device)
+  call('tg_swd_distance', _p(desc_a), n, _p(desc_b), desc_b.shape[0], _p(dirs), r, d, _p(out), None, _p(ws), nbytes, _stream(),
+       work=('swd_distance', 4 * n * SWD_K * r * d, 0))
+  if not return_sorted:
+    return out[r:], out[:r]
+  npad, keys = swd_npad(n), (r * d * swd_npad(n) + 3) // 4 * 4
+  return out[r:], out[:r], ws[:r * d * npad].view(r * d, npad), ws[keys:keys + r * d * npad].view(r * d, npad)
