@@ -489,6 +489,31 @@ int tg_adam_step(float* theta, const float* grad, float* m, float* v, void* thet
 int tg_adam_tick(int64_t* step_dev, float* lr_t_dev, float lr, float beta1, float beta2, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Moving averages of the model variables -- replaces tf.train.ExponentialMovingAverage(decay, global_step).apply
+ * of --moving_average_decay (model/model_inheritor.py:53-56, built at :1063-1066, appended to the update ops
+ * at :1090-1092; the eval branch restores every model variable from its shadow, :1150-1155).  TF 1.8's
+ * assign_moving_average, per element in fp32:   avg <- avg - (avg - var) * w,   w = 1 - decay of this run,
+ * read from the device scalar w_dev so that a captured hipGraph replays it with the current value (the caller
+ * computes min(decay, (1 + n) / (10 + n)) on the host).  The product and the subtraction are one fused
+ * multiply-add; an element with avg == var keeps its bits.
+ * tg_adam_ema_step: the Adam apply of tg_adam_step (rate from lr_t_dev, no bf16 shadow) and the update of `avg`
+ * from the freshly written theta in one pass -- 36 bytes per element instead of 28 + 12; theta, m, v come out
+ * bit-identical to tg_adam_step's.  tg_ema_update: the update alone on a flat buffer (the optimiser group a run
+ * did not apply).  Both move 16 bytes per lane when every pointer is 16-byte aligned and work element by
+ * element for any 4-byte-aligned pointers; any numel >= 1.
+ * tg_ema_update_multi: the update of MANY separately allocated small tensors (the non-trainable state: moving /
+ * renorm statistics, spectral-norm u) in one launch.  The caller builds a job table in HOST memory with
+ * tg_ema_table_fill (job j of njobs; *total_blocks accumulates the grid size, start it at 0), copies its
+ * tg_ema_table_bytes(njobs) bytes to the device once and passes njobs and the final total_blocks on every call.
+ * ------------------------------------------------------------------------------------------- */
+int tg_adam_ema_step(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel, const float* lr_t_dev,
+                     float beta1, float beta2, float eps, float grad_scale, const float* w_dev, void* stream);
+int tg_ema_update(float* avg, const float* var, int64_t numel, const float* w_dev, void* stream);
+size_t tg_ema_table_bytes(int njobs);
+int tg_ema_table_fill(float* avg, const float* var, int64_t numel, int job, void* table_host, int32_t* total_blocks);
+int tg_ema_update_multi(const void* table_device, int njobs, int total_blocks, const float* w_dev, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * SAGAN self-attention -- replaces tf.matmul (x2), tf.nn.softmax, tf.nn.tanh and gamma * o + layer of
  * libs/self_attention.py:57-69 (called from nets/pggan_utils.py:301-308 under --do_self_attention).  The layer is
  * composed on the host from these entry points; each is closed under differentiation (the backward of a product is two

@@ -155,6 +155,11 @@ SIGNATURES = {
     'tg_gp_penalty': (c_int, [_FP, _FP, _FP, c_int, c_float, _P]),
     'tg_adam_step': (c_int, [_FP, _FP, _FP, _FP, _P, c_int64, c_float, _FP, c_float, c_float, c_float, c_float, _P]),
     'tg_adam_tick': (c_int, [_P, _FP, c_float, c_float, c_float, _P]),
+    'tg_adam_ema_step': (c_int, [_FP, _FP, _FP, _FP, _FP, c_int64, _FP, c_float, c_float, c_float, c_float, _FP, _P]),
+    'tg_ema_update': (c_int, [_FP, _FP, c_int64, _FP, _P]),
+    'tg_ema_table_bytes': (c_size_t, [c_int]),
+    'tg_ema_table_fill': (c_int, [_FP, _FP, c_int64, c_int, _P, POINTER(c_int32)]),
+    'tg_ema_update_multi': (c_int, [_P, c_int, c_int, _FP, _P]),
     'tg_batched_gemm': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64,
                                 c_int64, c_float, c_int, c_int, c_int, _P]),
     'tg_softmax_rows_fwd': (c_int, [_P, _P, c_int64, c_int, c_int, _P]),

@@ -453,17 +453,30 @@ def _all_checkpoint_paths(directory):
 RNG_DRAWS_KEY = 'twingan_amd/gp_alpha_draws'      # the one tensor of a checkpoint that is not a variable of the reference
 
 
+def variables_to_restore(names, moving_average):
+  """tf.train.ExponentialMovingAverage.variables_to_restore as the reference's eval branch uses it
+  (model/model_inheritor.py:1150-1155): {checkpoint key: variable name} for the variables ``names``.  With
+  ``moving_average`` every model variable (params.is_model_variable: the trainable ones and the non-trainable state, all
+  but the attention gate sa_gamma) is read from its shadow ``<var>/ExponentialMovingAverage``, the rest from their own
+  names; without it the map is the identity."""
+  from .params import EMA_SUFFIX, is_model_variable
+  return {(k + EMA_SUFFIX if moving_average and is_model_variable(k) else k): k for k in names}
+
+
 def save(trainer, train_dir, global_step=None, max_to_keep=5):
   """What the reference's Saver leaves for a stage: every model variable (TF names, TF layouts), the non-trainable
   state (moving / renorm statistics, spectral-norm u), ``global_step``, and the shared Adam optimiser's slots
   (``<var>/Adam``, ``<var>/Adam_1``, ``beta1_power``, ``beta2_power``) -> <train_dir>/model.ckpt-<step> + checkpoint
-  (the ``max_to_keep`` most recent ones are retained)."""
+  (the ``max_to_keep`` most recent ones are retained).  Under --moving_average_decay (Config.moving_average_decay) also the
+  shadow ``<var>/ExponentialMovingAverage`` of every model variable; without it the key set is unchanged."""
   store = trainer.store
   step = int(trainer.global_step if global_step is None else global_step)
   tensors = {k: v.detach().float().cpu().numpy() for k, v in store.state_dict(include_state=True).items()}
   for k, (m, v) in store.adam_dict().items():
     tensors[k + '/Adam'] = m.detach().float().cpu().numpy()
     tensors[k + '/Adam_1'] = v.detach().float().cpu().numpy()
+  if store.averaged:
+    tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.averages_dict().items()})
   t = int(trainer.adam_t)
   tensors['beta1_power'] = np.float32(trainer.cfg.adam_beta1 ** (t + 1))       # TF keeps beta^(t+1) after t applies
   tensors['beta2_power'] = np.float32(trainer.cfg.adam_beta2 ** (t + 1))
@@ -505,7 +518,10 @@ def init_from_checkpoint(trainer, checkpoint_path, checkpoint_exclude_scopes=Non
   (a checkpoint prefix, or a directory -> its latest checkpoint).  Nothing is restored when ``train_dir`` already holds
   a checkpoint (the run resumes from that one instead).  A variable the checkpoint lacks is an error unless
   ``ignore_missing_vars`` (growing stages: the new resolution's layers keep their fresh initialisation,
-  pggan_runner.py:136-146); a shape mismatch is always an error, as in TensorFlow.  Returns the restored names."""
+  pggan_runner.py:136-146); a shape mismatch is always an error, as in TensorFlow.  Returns the restored names.
+  Variables are restored by their own names only: the moving averages of Config.moving_average_decay are not touched and
+  stay at this stage's initial values, as in the reference, whose shadows are no model variables.  The stage's global_step
+  starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs."""
   if checkpoint_path is None:
     return []
   if train_dir is not None and latest_checkpoint(train_dir):
@@ -538,7 +554,9 @@ def init_from_checkpoint(trainer, checkpoint_path, checkpoint_exclude_scopes=Non
 def restore(trainer, prefix):
   """tf.train.Saver.restore of a checkpoint this trainer's stage wrote (resuming a run, model_inheritor.py:596-602:
   a checkpoint in train_dir takes precedence over --checkpoint_path): model variables, state, the shared optimiser's
-  slots and beta powers, global_step.  Every variable of the model must be present with its shape."""
+  slots and beta powers, global_step.  Every variable of the model must be present with its shape.  A trainer that keeps
+  moving averages (Config.moving_average_decay) also loads ``<var>/ExponentialMovingAverage`` of every model variable and
+  raises KeyError naming the first one the file lacks, as a TF Saver would; one that keeps none ignores such keys."""
   import math
   import torch
   store = trainer.store
@@ -547,7 +565,14 @@ def restore(trainer, prefix):
   missing = [k for k in names if k not in arrays]
   if missing:
     raise KeyError('checkpoint %s lacks %d variable(s), e.g. %s' % (prefix, len(missing), missing[0]))
+  if store.averaged:
+    shadows = [k for k in variables_to_restore(names, True) if k not in names]
+    missing = [k for k in shadows if k not in arrays]
+    if missing:
+      raise KeyError('checkpoint %s lacks %d moving average(s), e.g. %s' % (prefix, len(missing), missing[0]))
   store.load_state_dict({k: torch.from_numpy(arrays[k].astype(np.float32)) for k in names}, strict=False)
+  if store.averaged:
+    store.load_averages_dict({k: torch.from_numpy(arrays[k].astype(np.float32)) for k in shadows})
   slots = {k: (arrays[k + '/Adam'], arrays[k + '/Adam_1']) for k in store.specs if k + '/Adam' in arrays}
   store.load_adam_dict(slots)
   if 'global_step' in arrays:

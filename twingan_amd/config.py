@@ -60,3 +60,12 @@ class Config:
   overlap_cut_hw: int = 32            # data-parallel runs: the backward is cut where the feature maps grow past this size and
                                       # the all-reduce of the (large) lower-resolution gradients overlaps the rest of it
   loss_scale: float = 1.0             # --mix_precision_loss_scale (model_inheritor.py:568-570); bf16 needs none
+  # --moving_average_decay (model/model_inheritor.py:53-56): None = no averaging; a decay in (0, 1) keeps
+  # tf.train.ExponentialMovingAverage(decay, global_step) shadows of every model variable, updated by every run
+  # (:1063-1092); evaluation reads the shadows (:1150-1155).  DESIGN.md section 7
+  moving_average_decay: object = None
+
+  def __post_init__(self):
+    d = self.moving_average_decay
+    if d is not None and not (0.0 < float(d) < 1.0):
+      raise ValueError('moving_average_decay must lie in (0, 1) or be None (got %r)' % (d,))

@@ -742,20 +742,131 @@ __global__ void small_gemm_wave_kernel(const float* __restrict__ a, const float*
   }
 }
 
-// TF-1.x Adam (model/model_inheritor.py:537-542): epsilon OUTSIDE the bias-corrected sqrt.
+// TF-1.x Adam (model/model_inheritor.py:537-542): epsilon OUTSIDE the bias-corrected sqrt.  One element, shared by
+// adam_kernel and adam_ema_kernel so that both write the same bits: the two multiply-adds are spelled as the fused
+// operations the compiler's contraction made of `b1 * m + (1 - b1) * g` and `b2 * v + (1 - b2) * g * g`, so their
+// rounding does not depend on the loop they are inlined into.
+__device__ __forceinline__ float adam_element(float th, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
+                                              float gscale) {
+  const float gi = g * gscale;
+  const float mi = fmaf(b1, m, (1.f - b1) * gi);
+  const float vi = fmaf(b2, v, (1.f - b2) * gi * gi);
+  m = mi;
+  v = vi;
+  return th - lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// tf.train.ExponentialMovingAverage's assign_moving_average (TF 1.8 moving_averages.py): avg -= (avg - var) * (1 - decay),
+// the product and the subtraction as one fused multiply-add.  avg == var gives avg back bit for bit.
+__device__ __forceinline__ float ema_element(float avg, float var, float w) { return fmaf(-(avg - var), w, avg); }
+
 __global__ void adam_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, bf16* __restrict__ shadow, int64_t numel, float lr_t,
                             const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale) {
   if (lr_t_dev) lr_t = lr_t_dev[0];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    const float t = th[i] - lr_t * mi / (sqrtf(vi) + eps);
+    float mi = m[i], vi = v[i];
+    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
     m[i] = mi;
     v[i] = vi;
     th[i] = t;
     if (shadow) shadow[i] = (bf16)t;
+  }
+}
+
+// The Adam apply and the moving average of the parameters it just wrote, in one pass over the group's flat buffers: 36 bytes
+// per element (read theta, g, m, v, avg; write theta, m, v, avg) against 28 + 12 for adam_kernel followed by ema_kernel.
+// VEC: every pointer is 16-byte aligned -- one 16-byte access per lane and array; the numel % 4 elements behind the last
+// whole vector are taken one by one.  Otherwise (any 4-byte-aligned pointers) element by element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ th, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       float* __restrict__ avg, int64_t numel,
+                                                       const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
+                                                       float gscale, const float* __restrict__ w_dev) {
+  const float lr_t = lr_t_dev[0], w = w_dev[0];
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  int64_t done = 0;
+  if constexpr (VEC) {
+    const int64_t nvec = numel >> 2;
+    for (int64_t i = tid; i < nvec; i += nthr) {
+      Vec16<float> t4 = ldv(th + 4 * i), m4 = ldv(m + 4 * i), v4 = ldv(v + 4 * i), a4 = ldv(avg + 4 * i);
+      const Vec16<float> g4 = ldv(g + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float mi = m4.v[e], vi = v4.v[e];
+        const float t = adam_element(t4.v[e], g4.v[e], mi, vi, lr_t, b1, b2, eps, gscale);
+        m4.v[e] = mi;
+        v4.v[e] = vi;
+        t4.v[e] = t;
+        a4.v[e] = ema_element(a4.v[e], t, w);
+      }
+      stv(m + 4 * i, m4);
+      stv(v + 4 * i, v4);
+      stv(th + 4 * i, t4);
+      stv(avg + 4 * i, a4);
+    }
+    done = nvec << 2;
+  }
+  for (int64_t i = done + tid; i < numel; i += nthr) {
+    float mi = m[i], vi = v[i];
+    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
+    m[i] = mi;
+    v[i] = vi;
+    th[i] = t;
+    avg[i] = ema_element(avg[i], t, w);
+  }
+}
+
+// The moving average alone on a flat buffer (the group a run did not apply): 12 bytes per element.  VEC as above.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const float* __restrict__ var, int64_t numel,
+                                                  const float* __restrict__ w_dev) {
+  const float w = w_dev[0];
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  int64_t done = 0;
+  if constexpr (VEC) {
+    const int64_t nvec = numel >> 2;
+    for (int64_t i = tid; i < nvec; i += nthr) {
+      Vec16<float> a4 = ldv(avg + 4 * i);
+      const Vec16<float> x4 = ldv(var + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a4.v[e] = ema_element(a4.v[e], x4.v[e], w);
+      stv(avg + 4 * i, a4);
+    }
+    done = nvec << 2;
+  }
+  for (int64_t i = done + tid; i < numel; i += nthr) avg[i] = ema_element(avg[i], var[i], w);
+}
+
+// ---- the moving averages of MANY small tensors in one launch (the non-trainable state: a few hundred separately allocated
+// tensors of 1 to a few hundred elements).  A host-built job table as for pack_weights_multi (conv_mfma.hip).
+struct EmaJob {
+  float* avg;
+  const float* var;
+  int64_t numel;
+  int block_begin, block_end;      // this job's slice of the grid (EMA_EPB elements per block)
+};
+constexpr int EMA_EPB = 1024;
+
+__global__ __launch_bounds__(256) void ema_multi_kernel(const EmaJob* __restrict__ jobs, int njobs,
+                                                        const float* __restrict__ w_dev) {
+  // binary search: the job whose [block_begin, block_end) holds this block (uniform -> scalar loads)
+  int lo = 0, hi = njobs - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (b >= jobs[mid].block_end) lo = mid + 1;
+    else hi = mid;
+  }
+  const EmaJob j = jobs[lo];
+  if (b < j.block_begin || b >= j.block_end) return;      // a grid larger than the table's total: nothing to do
+  const float w = w_dev[0];
+  const int64_t i0 = (int64_t)(b - j.block_begin) * EMA_EPB;
+#pragma unroll
+  for (int e = threadIdx.x; e < EMA_EPB; e += 256) {
+    const int64_t i = i0 + e;
+    if (i < j.numel) j.avg[i] = ema_element(j.avg[i], j.var[i], w);
   }
 }
 
@@ -1041,6 +1152,62 @@ int tg_adam_step(float* theta, const float* grad, float* m, float* v, void* thet
   hipLaunchKernelGGL(adam_kernel, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta, grad, m, v,
                      (bf16*)theta_bf16, numel, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale);
   TG_LAUNCH_CHECK("tg_adam_step");
+  return TG_OK;
+}
+
+int tg_adam_ema_step(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel, const float* lr_t_dev,
+                     float beta1, float beta2, float eps, float grad_scale, const float* w_dev, void* stream) {
+  TG_CHECK(theta && grad && m && v && avg && lr_t_dev && w_dev, TG_EINVAL, "tg_adam_ema_step: null pointer");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step: numel must be positive (got %lld)", (long long)numel);
+  const bool vec = tg_aligned16(theta) && tg_aligned16(grad) && tg_aligned16(m) && tg_aligned16(v) && tg_aligned16(avg);
+  if (vec)
+    hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(tg_grid_for((numel + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, theta,
+                       grad, m, v, avg, numel, lr_t_dev, beta1, beta2, eps, grad_scale, w_dev);
+  else
+    hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta, grad,
+                       m, v, avg, numel, lr_t_dev, beta1, beta2, eps, grad_scale, w_dev);
+  TG_LAUNCH_CHECK("tg_adam_ema_step");
+  return TG_OK;
+}
+
+int tg_ema_update(float* avg, const float* var, int64_t numel, const float* w_dev, void* stream) {
+  TG_CHECK(avg && var && w_dev, TG_EINVAL, "tg_ema_update: null pointer");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_ema_update: numel must be positive (got %lld)", (long long)numel);
+  if (tg_aligned16(avg) && tg_aligned16(var))
+    hipLaunchKernelGGL(ema_kernel<true>, dim3(tg_grid_for((numel + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, avg, var,
+                       numel, w_dev);
+  else
+    hipLaunchKernelGGL(ema_kernel<false>, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, avg, var, numel,
+                       w_dev);
+  TG_LAUNCH_CHECK("tg_ema_update");
+  return TG_OK;
+}
+
+size_t tg_ema_table_bytes(int njobs) { return (size_t)(njobs > 0 ? njobs : 0) * sizeof(EmaJob); }
+
+int tg_ema_table_fill(float* avg, const float* var, int64_t numel, int job, void* table_host, int32_t* total_blocks) {
+  TG_CHECK(avg && var && table_host && total_blocks && job >= 0, TG_EINVAL, "tg_ema_table_fill: bad arguments");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_ema_table_fill: numel must be positive (got %lld)", (long long)numel);
+  const int64_t blocks = (numel + EMA_EPB - 1) / EMA_EPB;
+  TG_CHECK(*total_blocks >= 0 && *total_blocks + blocks <= 0x7fffffff, TG_EINVAL, "tg_ema_table_fill: grid too large");
+  EmaJob j;
+  j.avg = avg;
+  j.var = var;
+  j.numel = numel;
+  j.block_begin = *total_blocks;
+  j.block_end = j.block_begin + (int)blocks;
+  *total_blocks = j.block_end;
+  ((EmaJob*)table_host)[job] = j;
+  return TG_OK;
+}
+
+int tg_ema_update_multi(const void* table_device, int njobs, int total_blocks, const float* w_dev, void* stream) {
+  TG_CHECK(table_device && w_dev, TG_EINVAL, "tg_ema_update_multi: null pointer");
+  TG_CHECK(njobs > 0 && total_blocks > 0, TG_EINVAL, "tg_ema_update_multi: njobs and total_blocks must be positive (got %d, %d)",
+           njobs, total_blocks);
+  hipLaunchKernelGGL(ema_multi_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, (const EmaJob*)table_device, njobs,
+                     w_dev);
+  TG_LAUNCH_CHECK("tg_ema_update_multi");
   return TG_OK;
 }
 

@@ -11,7 +11,8 @@ estimator's noise floor at half the sample), and a channel with sigma = 0 normal
 evaluate_translation scores a TwinGAN checkpoint: the diversity of what it generates, the similarity of the cycle
 s -> t' -> s_cyc to its source (the quantity the L1 cycle loss trains) and, given target-domain images, the SWD between them
 and the translations (real = targets, fake = t_prime_output: twingan.py:762-763).  Images stay on the device in the model's
-dtype; nothing synchronises before the final read-out.  The Inception score needs a pretrained classifier and is out of scope."""
+dtype; nothing synchronises before the final read-out.  Which weights are scored is the caller's choice of state dict: the
+raw iterate or, under Config.moving_average_decay, the moving averages (ParamStore.averaged_state_dict).  The Inception score needs a pretrained classifier and is out of scope."""
 import torch
 
 from . import ops
@@ -147,7 +148,10 @@ def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cud
   custom_generated_*_style_source.  ``translate_fn(x, to) -> image batch`` replaces the model (tests: an identity stand-in);
   with it ``state_dict`` is not read.  With ``targets`` (images of the domain translated to, same shape as ``sources``) the
   result also holds swd_real, swd_fake (per resolution, times 1e3) and swd_resolutions: SlicedWasserstein at its defaults
-  fed (targets, translate(sources)) batch by batch."""
+  fed (targets, translate(sources)) batch by batch.
+  ``state_dict`` names the weights that are scored: ParamStore.state_dict(include_state=True) for the last optimiser
+  iterate, ParamStore.averaged_state_dict() for the moving averages of a run under Config.moving_average_decay -- the
+  weights the reference's eval branch restores (model/model_inheritor.py:1150-1155) and the PGGAN paper scores."""
   assert to in ('s', 't'), to
   cfg = cfg if isinstance(cfg, Config) else Config(**cfg)
   device = torch.device(device)

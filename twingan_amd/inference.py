@@ -36,7 +36,9 @@ def resize_bilinear_tf1(img, hw):
 
 class ImageInferer:
   """ImageInferer of inference/image_translation_infer.py:46-99 without the TF session: variables come from a state
-  dict keyed by the reference's variable names (ParamStore.state_dict(include_state=True), or a converted checkpoint)."""
+  dict keyed by the reference's variable names (ParamStore.state_dict(include_state=True), or a converted checkpoint).  To
+  translate with the moving averages of a run under Config.moving_average_decay -- the weights PGGAN-family generators are
+  judged on -- pass ParamStore.averaged_state_dict(), or load a checkpoint with from_checkpoint(..., moving_average=True)."""
 
   def __init__(self, cfg, state_dict, device='cuda', output_tensor_name='custom_generated_t_style_source'):
     assert output_tensor_name in OUTPUT_TENSORS, output_tensor_name
@@ -49,9 +51,13 @@ class ImageInferer:
     self.dtype = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[self.cfg.precision]
 
   @classmethod
-  def from_checkpoint(cls, cfg, model_path, device='cuda', output_tensor_name='custom_generated_t_style_source'):
+  def from_checkpoint(cls, cfg, model_path, device='cuda', output_tensor_name='custom_generated_t_style_source',
+                      moving_average=False):
     """``model_path``: a TF-format checkpoint prefix or the train_dir that holds one (image_translation_infer.py:60-74
-    restores tf.train.latest_checkpoint(model_path)): the model's variables are read by name (checkpoint.py)."""
+    restores tf.train.latest_checkpoint(model_path)): the model's variables are read by name (checkpoint.py).
+    ``moving_average``: read every model variable from its ``<var>/ExponentialMovingAverage`` shadow instead
+    (checkpoint.variables_to_restore -- the reference's eval branch under --moving_average_decay,
+    model/model_inheritor.py:1150-1155); the checkpoint must come from a run that kept the averages."""
     import os
     from . import checkpoint as ckpt
     cfg = cfg if isinstance(cfg, Config) else Config(**cfg)
@@ -59,13 +65,13 @@ class ImageInferer:
     if prefix is None:
       raise FileNotFoundError('no checkpoint in %s' % model_path)
     probe = declare_twingan(ParamStore(torch.device('cpu')), cfg).build(0)
-    names = set(probe.specs) | set(probe.state_specs)
+    keys = ckpt.variables_to_restore(list(probe.specs) + list(probe.state_specs), moving_average)      # file key -> variable
     probe.close()
-    arrays = ckpt.read_checkpoint(prefix, names=names)
-    missing = sorted(names - set(arrays))
+    arrays = ckpt.read_checkpoint(prefix, names=set(keys))
+    missing = sorted(set(keys) - set(arrays))
     if missing:
       raise KeyError('checkpoint %s lacks %d variable(s) of this configuration, e.g. %s' % (prefix, len(missing), missing[0]))
-    return cls(cfg, {k: torch.from_numpy(v.astype(np.float32)) for k, v in arrays.items()}, device, output_tensor_name)
+    return cls(cfg, {keys[k]: torch.from_numpy(v.astype(np.float32)) for k, v in arrays.items()}, device, output_tensor_name)
 
   def preprocess(self, images):
     """uint8 [H,W,3] / [B,H,W,3] (or floats already in [0,1]) -> device tensor [B, hw, hw, 3] of the model's dtype."""

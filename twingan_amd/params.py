@@ -61,6 +61,11 @@ class ParamStore:
     self.phase_bounds = {}             # group -> {phase: (lo, hi)} element range of each phase in the flat buffers
     self.phase = {}                    # name -> phase
     self.pairs = {}                    # 'discriminator_*/<rest>' -> [2, *phys] view over the two domains' adjacent variables
+    # --moving_average_decay (Config.moving_average_decay): set before build() by the trainer; build() then allocates the
+    # moving averages of the model variables -- avg[g] flat buffers laid out like flat[g] / m[g], state_avg[name] per state variable
+    self.averaged = False
+    self.avg = {}
+    self.state_avg = {}
 
   # ---- declaration ----------------------------------------------------------------------------
   def add(self, name, shape, group, kind, phys=None):
@@ -174,6 +179,9 @@ class ParamStore:
     if 'gdrop_strength' in self.state_specs:      # the controller's coefficient of the current global step (Trainer._set_gdrop_coef)
       self.state['gdrop/coef'] = torch.zeros(1, dtype=torch.float32, device=self.device)
     self.P.state = self.state
+    if self.averaged:      # TF creates the shadow from var.initialized_value(): the average starts as the initial value
+      self.avg = {g: self.flat[g].detach().clone() for g in self.GROUPS}
+      self.state_avg = {k: self.state[k].clone() for k in self.state_specs if is_model_variable(k)}
     PackCache.version += 1
     return self
 
@@ -241,6 +249,46 @@ class ParamStore:
         for dst, src in ((self.m[g], m), (self.v[g], v)):
           self._logical(dst[off:off + n].view(s['phys']), s).copy_(torch.as_tensor(src, dtype=torch.float32).reshape(s['shape']))
 
+  # ---- moving averages (tf.train.ExponentialMovingAverage shadows; model/model_inheritor.py:1063-1092,1150-1155) -------------
+  def _avg_view(self, k):
+    s = self.specs[k]
+    g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
+    return self._logical(self.avg[g][off:off + n].view(s['phys']), s)
+
+  def averages_dict(self):
+    """{'<var>/ExponentialMovingAverage': logical (TF-shaped) copy} for every MODEL variable (is_model_variable: all but the
+    attention gate sa_gamma), trainable and state alike -- the shadow variables TF's Saver writes."""
+    assert self.averaged, 'this store keeps no moving averages (Config.moving_average_decay is None)'
+    out = {k + EMA_SUFFIX: self._avg_view(k).clone() for k in self.specs if is_model_variable(k)}
+    out.update({k + EMA_SUFFIX: (v.reshape(()) if k in self.scalar_state else v).clone() for k, v in self.state_avg.items()})
+    return out
+
+  def load_averages_dict(self, avgs):
+    """Inverse of averages_dict for the keys given."""
+    assert self.averaged, 'this store keeps no moving averages (Config.moving_average_decay is None)'
+    with torch.no_grad():
+      for key, src in avgs.items():
+        assert key.endswith(EMA_SUFFIX), key
+        k = key[:-len(EMA_SUFFIX)]
+        src = torch.as_tensor(src).to(device=self.device, dtype=torch.float32)
+        if k in self.state_avg:
+          self.state_avg[k].copy_(src.reshape(self.state_avg[k].shape))
+        else:
+          assert tuple(src.shape) == self.specs[k]['shape'], (key, tuple(src.shape), self.specs[k]['shape'])
+          self._avg_view(k).copy_(src)
+
+  def averaged_state_dict(self, include_state=True):
+    """state_dict() with the averaged value of every model variable under its PLAIN name and the live value of the rest
+    (sa_gamma) -- what restoring through the reference's variables_to_restore map loads for evaluation
+    (model/model_inheritor.py:1150-1155); goes straight to ImageInferer(cfg, sd) / evaluate_translation(cfg, sd, ...)."""
+    assert self.averaged, 'this store keeps no moving averages (Config.moving_average_decay is None)'
+    sd = self.state_dict(include_state=include_state)
+    for key, v in self.averages_dict().items():
+      k = key[:-len(EMA_SUFFIX)]
+      if k in sd:
+        sd[k] = v
+    return sd
+
   def grad_dict(self):
     GradSink.flush()                             # filter gradients held back for pairing
     if self.device.type == 'cuda':
@@ -281,9 +329,13 @@ class ParamStore:
       GradSink.unregister(p)
     for buf in self.P.__dict__.pop('sn_wbar', {}).values():      # persistent spectrally-normalised kernels (pggan._sn_compute)
       PackCache.unregister(buf)
+    self.avg, self.state_avg = {}, {}
 
   def numel(self, group):
     return sum(int(math.prod(s['shape'])) for s in self.specs.values() if s['group'] == group)
+
+
+EMA_SUFFIX = '/ExponentialMovingAverage'      # tf.train.ExponentialMovingAverage.average_name(var): '<var.op.name>/' + its name
 
 
 _HW_IN_NAME = __import__('re').compile(r'/(?:encoder_block|from_rgb|self_attention|block|generator_to_rgb)_(\d+)x\d+')

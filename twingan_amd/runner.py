@@ -40,7 +40,10 @@ def alpha_grow(global_step, max_number_of_steps, grow_start_number_of_steps=0):
 def warm_start(trainer, previous_state):
   """Loads every variable of ``previous_state`` (a ParamStore.state_dict()) that this stage also has and whose
   shape matches; the rest keep their fresh initialisation -- slim's assign_from_checkpoint_fn with
-  ignore_missing_vars (model/model_inheritor.py:576-644).  Returns the names that were loaded."""
+  ignore_missing_vars (model/model_inheritor.py:576-644).  Returns the names that were loaded.
+  Under Config.moving_average_decay the moving averages are NOT warm-started: the reference's _get_init_fn restores model
+  variables by their own names only, so the averages stay at this stage's fresh initial values.  The stage's global_step
+  starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs."""
   from .params import is_model_variable
   specs, state = trainer.store.specs, trainer.store.state
   usable = {k: v for k, v in previous_state.items()

@@ -475,7 +475,9 @@ class Trainer:
     self._rng_seed = 1000003 * (seed + 1) + rank
     self._rng_state = torch.zeros(2, dtype=torch.int32, device=self.device)
     self.reducer = GradReducer(world_size, process_group)
-    self.store = self._declare(ParamStore(self.device), cfg).build(seed)
+    store = self._declare(ParamStore(self.device), cfg)
+    store.averaged = cfg.moving_average_decay is not None      # --moving_average_decay: shadows of the model variables
+    self.store = store.build(seed)
     self.P = self.store.P
     self.n_critic_counter = 0       # image_generation.py:622-623
     self.global_step = 0            # advanced once per n_critic cycle, see _advance_counters
@@ -500,10 +502,17 @@ class Trainer:
     self.capture_note = None        # set when the segmented capture had to be replaced by one graph per step kind
     self._graphs = None
     self._static = None
+    if self.store.averaged:
+      # 1 - decay of the current run (_set_ema_weight), in a device scalar so that a replayed graph reads the current value
+      self._ema_w_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+      self._ema_w = None
+      self._ema_table = self._build_ema_table()
+      self._set_ema_weight()
 
   def close(self):
     """Releases the captured graphs and this trainer's entries in the pack / gradient-sink registries."""
     self._graphs = self._static = None
+    self._ema_table = None
     self.store.close()
 
   # ---- optimiser --------------------------------------------------------------------------------
@@ -542,11 +551,65 @@ class Trainer:
     self.adam_t += 1
     step_dev, lr_dev, lr = self._adam_step_dev, self._lr_t_dev, c.learning_rate
     call('tg_adam_tick', step_dev.data_ptr(), lr_dev.data_ptr(), lr, c.adam_beta1, c.adam_beta2, st)
-    call('tg_adam_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
-         s.v[group].data_ptr(), None, s.flat[group].numel(), 0.0, lr_dev.data_ptr(), c.adam_beta1,
-         c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale, st,
-         work=('adam:numel%d' % s.flat[group].numel(), 0, 28 * s.flat[group].numel()))
+    if s.averaged:
+      self._adam_ema(group, st)
+    else:
+      call('tg_adam_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
+           s.v[group].data_ptr(), None, s.flat[group].numel(), 0.0, lr_dev.data_ptr(), c.adam_beta1,
+           c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale, st,
+           work=('adam:numel%d' % s.flat[group].numel(), 0, 28 * s.flat[group].numel()))
     PackCache.refresh(self._group_weights[group])
+
+  # ---- moving averages (--moving_average_decay) ---------------------------------------------------------------
+  def _adam_ema(self, group, st):
+    """The apply of ``group`` fused with the moving average of its variables, then the averages of everything the run did
+    not apply: tf.train.ExponentialMovingAverage.apply is ONE op group over all model variables in every session.run
+    (model/model_inheritor.py:1063-1066,1090-1092), so a discriminator run also moves the generator's averages towards the
+    (unchanged) generator weights and vice versa.  The reference leaves the op unordered against the Adam apply and the
+    state updates; here it reads the post-run values: the three launches follow the apply on the main stream, after the
+    run's moving statistics / spectral-norm u / gdrop updates (all joined before the apply) -- under graph capture they are
+    part of the captured apply graph.  Data-parallel runs need no communication: every clone applies the same all-reduced
+    gradients to the same parameters, so the averages agree wherever the parameters do."""
+    c, s, w = self.cfg, self.store, self._ema_w_dev.data_ptr()
+    n = s.flat[group].numel()
+    call('tg_adam_ema_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(), s.v[group].data_ptr(),
+         s.avg[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale,
+         w, st, work=('adam_ema:numel%d' % n, 0, 36 * n))
+    for other in s.GROUPS:
+      if other != group:
+        n = s.flat[other].numel()
+        call('tg_ema_update', s.avg[other].data_ptr(), s.flat[other].data_ptr(), n, w, st, work=('ema:numel%d' % n, 0, 12 * n))
+    if self._ema_table is not None:
+      tab = self._ema_table
+      call('tg_ema_update_multi', tab[0].data_ptr(), tab[1], tab[2], w, st, work=('ema_multi:%d' % tab[1], 0, tab[3]))
+
+  def _build_ema_table(self):
+    """Device job table of tg_ema_update_multi over the state variables' (average, variable) pairs: built once, the
+    buffers keep their addresses for the trainer's life."""
+    from . import _lib
+    items = list(self.store.state_avg.items())
+    if not items:
+      return None
+    host = ctypes.create_string_buffer(_lib.load().tg_ema_table_bytes(len(items)))
+    blocks = ctypes.c_int32(0)
+    for j, (k, a) in enumerate(items):
+      call('tg_ema_table_fill', a.data_ptr(), self.store.state[k].data_ptr(), a.numel(), j, ctypes.addressof(host),
+           ctypes.byref(blocks))
+    dev = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.device)
+    return dev, len(items), blocks.value, 12 * sum(a.numel() for _, a in items)
+
+  def _set_ema_weight(self):
+    """TF 1.8 ExponentialMovingAverage with num_updates = global_step, in float32 as TF computes it:
+    decay = min(decay, (1 + n) / (10 + n)), w = 1 - decay.  n is the global step as it stands when run() is entered -- the
+    value alpha_grow and the renorm clipping of that run see (the reference leaves the read unordered against
+    increase_global_step).  Written into the device scalar only when it changes (_set_renorm_clipping's pattern)."""
+    import numpy as np
+    n = np.float32(self.global_step)
+    d = min(np.float32(self.cfg.moving_average_decay), (np.float32(1) + n) / (np.float32(10) + n))
+    w = float(np.float32(1) - np.float32(d))
+    if self._ema_w != w:
+      self._ema_w = w
+      self._ema_w_dev.fill_(w)
 
   # ---- steps ------------------------------------------------------------------------------------
   def _grad_segments(self, group, sources, targets, gp_alpha_s=None, gp_alpha_t=None):
@@ -640,7 +703,10 @@ class Trainer:
     return dict(flat={g: s.flat[g].clone() for g in s.GROUPS}, m={g: s.m[g].clone() for g in s.GROUPS},
                 v={g: s.v[g].clone() for g in s.GROUPS}, state={k: v.clone() for k, v in s.state.items()},
                 step=self._adam_step_dev.clone(), lr=self._lr_t_dev.clone(), draws=self._rng_state.clone(),
-                host=(self.n_critic_counter, self.global_step, self.adam_t), rng=torch.cuda.get_rng_state(self.device))
+                host=(self.n_critic_counter, self.global_step, self.adam_t), rng=torch.cuda.get_rng_state(self.device),
+                # the moving averages and their weight: the undone warm-up of a capture must leave no trace in them
+                avg={g: v.clone() for g, v in s.avg.items()}, state_avg={k: v.clone() for k, v in s.state_avg.items()},
+                ema_w=(self._ema_w, self._ema_w_dev.clone()) if s.averaged else None)
 
   def _restore(self, snap):
     s = self.store
@@ -655,6 +721,13 @@ class Trainer:
       self._adam_step_dev.copy_(snap['step'])
       self._lr_t_dev.copy_(snap['lr'])
       self._rng_state.copy_(snap['draws'])
+      for g, v in snap['avg'].items():
+        s.avg[g].copy_(v)
+      for k, v in snap['state_avg'].items():
+        s.state_avg[k].copy_(v)
+      if snap['ema_w'] is not None:
+        self._ema_w = snap['ema_w'][0]
+        self._ema_w_dev.copy_(snap['ema_w'][1])
     self.n_critic_counter, self.global_step, self.adam_t = snap['host']
     torch.cuda.set_rng_state(snap['rng'], self.device)
     for g in s.GROUPS:                      # the packs follow the restored masters
@@ -804,6 +877,8 @@ class Trainer:
         self._set_renorm_clipping()
       if self.cfg.use_gdrop:
         self._set_gdrop_coef()
+      if self.store.averaged:
+        self._set_ema_weight()
       if self.use_graph:
         assert gp_alpha_s is None and gp_alpha_t is None, 'graph mode draws the GP alphas on the device'
         out = self._run_graph('g' if is_g else 'd', sources, targets)
