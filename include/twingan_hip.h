@@ -514,6 +514,46 @@ int tg_ema_table_fill(float* avg, const float* var, int64_t numel, int job, void
 int tg_ema_update_multi(const void* table_device, int njobs, int total_blocks, const float* w_dev, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Dynamic loss scaling with the decision on the device (Config.dynamic_loss_scale).  The reference has no counterpart
+ * (its fp16 mode takes a static --mix_precision_loss_scale on faith, model/model_inheritor.py:568-570): the rule below is
+ * this project's own, DESIGN.md section 7.  One TgLossScaleState per optimiser group, in device memory; the trainer
+ * mirrors the layout (twingan_amd/_lib.py TgLossScaleState).  Per apply of a group, in stream order:
+ *   tg_nonfinite_check   found |= some element of the flat fp32 range is +-inf or NaN (exponent bits all ones).  It ORs:
+ *                        several ranges may be checked before one tick; nothing but `found` is written, x is only read.
+ *                        Any 4-byte-aligned x and any numel >= 1; 16-byte loads when x is 16-byte aligned.  The grid is at
+ *                        most 2048 workgroups of 256 threads, two 16-byte vectors per thread and trip (one sweep covers
+ *                        4 194 304 elements; element by element, 524 288).
+ *   tg_loss_scale_tick   one thread.  S = scale (what the backward just used).  found: skip = 1, S <- max(S / 2, 1),
+ *                        good_steps = 0, skipped += 1, step_dev and lr_t_dev untouched.  Otherwise skip = 0, step_dev
+ *                        and lr_t_dev exactly as tg_adam_tick writes them, good_steps += 1 and, when it reaches
+ *                        growth_interval, S <- min(2 S, max_scale) and good_steps = 0.  Either way found = 0,
+ *                        inv_scale = 1 / S of the OLD S (the apply in flight), seed = new S / world (the next backward).
+ *   tg_adam_step_guarded / tg_adam_ema_step_guarded
+ *                        tg_adam_step (rate from lr_t_dev, no shadow) / tg_adam_ema_step with grad_scale = inv_scale,
+ *                        bit for bit, when skip == 0.  skip != 0: theta, m, v are not stored; the fused form still
+ *                        updates avg from the unchanged theta, bit for bit what tg_ema_update gives.
+ * S must be a power of two in [1, 2^24] so that every 1 / S and S / 2 is exact.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct TgLossScaleState {
+  float scale;         /* S: the scale of this group's next backward                                  */
+  float seed;          /* S / world: d loss / d loss of that backward (a device fp32 scalar)          */
+  float inv_scale;     /* 1 / S of the apply in flight                                                */
+  int32_t found;       /* a checked range held a non-finite value since the last tick                 */
+  int32_t skip;        /* the apply in flight is skipped                                              */
+  int32_t good_steps;  /* applies made in a row since the last change of S                            */
+  int64_t skipped;     /* applies skipped in all (offset 24; the struct is 32 bytes)                  */
+} TgLossScaleState;
+size_t tg_loss_scale_state_bytes(void);
+int tg_nonfinite_check(const float* x, int64_t numel, TgLossScaleState* state, void* stream);
+int tg_loss_scale_tick(TgLossScaleState* state, int64_t* step_dev, float* lr_t_dev, float lr, float beta1, float beta2,
+                       int growth_interval, float max_scale, int world, void* stream);
+int tg_adam_step_guarded(float* theta, const float* grad, float* m, float* v, int64_t numel, const float* lr_t_dev,
+                         float beta1, float beta2, float eps, const TgLossScaleState* state, void* stream);
+int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel,
+                             const float* lr_t_dev, float beta1, float beta2, float eps, const TgLossScaleState* state,
+                             const float* w_dev, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * SAGAN self-attention -- replaces tf.matmul (x2), tf.nn.softmax, tf.nn.tanh and gamma * o + layer of
  * libs/self_attention.py:57-69 (called from nets/pggan_utils.py:301-308 under --do_self_attention).  The layer is
  * composed on the host from these entry points; each is closed under differentiation (the backward of a product is two

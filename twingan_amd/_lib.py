@@ -27,6 +27,12 @@ class TgConvDesc(Structure):
                                      'dtype', 'algo', 'epilogue')] + [('lrelu_alpha', c_float), ('groups', c_int32)]
 
 
+class TgLossScaleState(Structure):
+  """Dynamic loss scaling, one per optimiser group in device memory (include/twingan_hip.h TgLossScaleState)."""
+  _fields_ = [('scale', c_float), ('seed', c_float), ('inv_scale', c_float), ('found', c_int32), ('skip', c_int32),
+              ('good_steps', c_int32), ('skipped', c_int64)]
+
+
 _P = c_void_p
 _FP = c_void_p      # float* passed as raw address
 _D = POINTER(TgConvDesc)
@@ -160,6 +166,11 @@ SIGNATURES = {
     'tg_ema_table_bytes': (c_size_t, [c_int]),
     'tg_ema_table_fill': (c_int, [_FP, _FP, c_int64, c_int, _P, POINTER(c_int32)]),
     'tg_ema_update_multi': (c_int, [_P, c_int, c_int, _FP, _P]),
+    'tg_loss_scale_state_bytes': (c_size_t, []),
+    'tg_nonfinite_check': (c_int, [_FP, c_int64, _P, _P]),
+    'tg_loss_scale_tick': (c_int, [_P, _P, _FP, c_float, c_float, c_float, c_int, c_float, c_int, _P]),
+    'tg_adam_step_guarded': (c_int, [_FP, _FP, _FP, _FP, c_int64, _FP, c_float, c_float, c_float, _P, _P]),
+    'tg_adam_ema_step_guarded': (c_int, [_FP, _FP, _FP, _FP, _FP, c_int64, _FP, c_float, c_float, c_float, _P, _FP, _P]),
     'tg_batched_gemm': (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64,
                                 c_int64, c_float, c_int, c_int, c_int, _P]),
     'tg_softmax_rows_fwd': (c_int, [_P, _P, c_int64, c_int, c_int, _P]),

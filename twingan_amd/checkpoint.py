@@ -450,7 +450,12 @@ def _all_checkpoint_paths(directory):
     return [l.split(':', 1)[1].strip().strip('"') for l in fh if l.startswith('all_model_checkpoint_paths:')]
 
 
-RNG_DRAWS_KEY = 'twingan_amd/gp_alpha_draws'      # the one tensor of a checkpoint that is not a variable of the reference
+RNG_DRAWS_KEY = 'twingan_amd/gp_alpha_draws'      # a tensor of a checkpoint that is not a variable of the reference
+# Config.dynamic_loss_scale (no counterpart in the reference either): '<prefix><group>/scale' (float32), '/good_steps' (int32),
+# '/skipped' (int64) per optimiser group, and the applies the shared Adam optimiser actually MADE -- n_critic_counter counts the
+# attempted ones and stops being that number with the first skipped apply
+LOSS_SCALE_PREFIX = 'twingan_amd/loss_scale/'
+ADAM_APPLIES_KEY = 'twingan_amd/adam_applies'
 
 
 def variables_to_restore(names, moving_average):
@@ -468,7 +473,9 @@ def save(trainer, train_dir, global_step=None, max_to_keep=5):
   state (moving / renorm statistics, spectral-norm u), ``global_step``, and the shared Adam optimiser's slots
   (``<var>/Adam``, ``<var>/Adam_1``, ``beta1_power``, ``beta2_power``) -> <train_dir>/model.ckpt-<step> + checkpoint
   (the ``max_to_keep`` most recent ones are retained).  Under --moving_average_decay (Config.moving_average_decay) also the
-  shadow ``<var>/ExponentialMovingAverage`` of every model variable; without it the key set is unchanged."""
+  shadow ``<var>/ExponentialMovingAverage`` of every model variable; without it the key set is unchanged.  Under
+  Config.dynamic_loss_scale also each group's loss-scale state and the applies made (LOSS_SCALE_PREFIX, ADAM_APPLIES_KEY;
+  reading them waits for the device once); without it the key set is unchanged."""
   store = trainer.store
   step = int(trainer.global_step if global_step is None else global_step)
   tensors = {k: v.detach().float().cpu().numpy() for k, v in store.state_dict(include_state=True).items()}
@@ -478,6 +485,14 @@ def save(trainer, train_dir, global_step=None, max_to_keep=5):
   if store.averaged:
     tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.averages_dict().items()})
   t = int(trainer.adam_t)
+  if getattr(trainer, '_ls', None) is not None:
+    state = trainer.loss_scale_state()
+    t = state.pop('applies')      # the beta powers follow the device's apply count, which skipped applies did not advance
+    tensors[ADAM_APPLIES_KEY] = np.int64(t)
+    for g, st in state.items():
+      tensors[LOSS_SCALE_PREFIX + g + '/scale'] = np.float32(st['scale'])
+      tensors[LOSS_SCALE_PREFIX + g + '/good_steps'] = np.int32(st['good_steps'])
+      tensors[LOSS_SCALE_PREFIX + g + '/skipped'] = np.int64(st['skipped'])
   tensors['beta1_power'] = np.float32(trainer.cfg.adam_beta1 ** (t + 1))       # TF keeps beta^(t+1) after t applies
   tensors['beta2_power'] = np.float32(trainer.cfg.adam_beta2 ** (t + 1))
   tensors['global_step'] = np.int64(step)
@@ -521,7 +536,8 @@ def init_from_checkpoint(trainer, checkpoint_path, checkpoint_exclude_scopes=Non
   pggan_runner.py:136-146); a shape mismatch is always an error, as in TensorFlow.  Returns the restored names.
   Variables are restored by their own names only: the moving averages of Config.moving_average_decay are not touched and
   stay at this stage's initial values, as in the reference, whose shadows are no model variables.  The stage's global_step
-  starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs."""
+  starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs.  The loss-scale states of
+  Config.dynamic_loss_scale are not touched either: a new stage starts from the initial scale."""
   if checkpoint_path is None:
     return []
   if train_dir is not None and latest_checkpoint(train_dir):
@@ -556,7 +572,9 @@ def restore(trainer, prefix):
   a checkpoint in train_dir takes precedence over --checkpoint_path): model variables, state, the shared optimiser's
   slots and beta powers, global_step.  Every variable of the model must be present with its shape.  A trainer that keeps
   moving averages (Config.moving_average_decay) also loads ``<var>/ExponentialMovingAverage`` of every model variable and
-  raises KeyError naming the first one the file lacks, as a TF Saver would; one that keeps none ignores such keys."""
+  raises KeyError naming the first one the file lacks, as a TF Saver would; one that keeps none ignores such keys.  A
+  trainer with Config.dynamic_loss_scale takes each group's loss-scale state from the file, or Config.loss_scale and zero
+  counts where the file has none."""
   import math
   import torch
   store = trainer.store
@@ -581,18 +599,30 @@ def restore(trainer, prefix):
   if 'n_critic_counter' in arrays:
     trainer.n_critic_counter = int(arrays['n_critic_counter'])
   trainer.set_adam_step(_adam_applies(arrays, trainer.cfg, trainer.n_critic_counter))
+  if getattr(trainer, '_ls', None) is not None:
+    # an older, a TensorFlow-written or a static-scale checkpoint lacks the keys: the initial scale and zero counts
+    trainer.adam_t = int(trainer.n_critic_counter)      # the attempted applies; the device counter holds the ones made
+    for g in store.GROUPS:
+      key = LOSS_SCALE_PREFIX + g
+      if key + '/scale' in arrays:
+        trainer.set_loss_scale(g, float(arrays[key + '/scale']), int(arrays.get(key + '/good_steps', 0)),
+                               int(arrays.get(key + '/skipped', 0)))
+      else:
+        trainer.set_loss_scale(g, trainer.cfg.loss_scale)
   if RNG_DRAWS_KEY in arrays and getattr(trainer, '_rng_state', None) is not None:
     trainer._rng_state[0] = int(arrays[RNG_DRAWS_KEY])      # continue the device generator's sequence (see save)
   return trainer.global_step
 
 
 def _adam_applies(arrays, cfg, counter):
-  """Number of applies t the shared Adam optimiser has made.  The reference applies the one optimiser exactly once per
+  """Number of applies t the shared Adam optimiser has made: ADAM_APPLIES_KEY when the file has it.  The reference applies the one optimiser exactly once per
   n_critic_counter increment (image_generation.py:640-652), so the counter IS t when the checkpoint has it.  Without it:
   TF keeps beta^(t+1) in float32 (repeated float32 products, off by ~1.3e-8 relative per apply), so invert whichever power
   is still a normal number (beta1 = 0.5 underflows to exactly 0 at t = 149, beta2 = 0.999 near t = 87 000) -- exact for
   short runs, within a step or two for long ones; after that the caller's counter (global_step * n_critic)."""
   import math
+  if ADAM_APPLIES_KEY in arrays:      # dynamic loss scaling: skipped applies advance n_critic_counter but not the optimiser
+    return max(0, int(arrays[ADAM_APPLIES_KEY]))
   if 'n_critic_counter' in arrays:      # exact; TF's float32 beta powers drift by ~1.3e-5 steps per apply (half a step at 40 k)
     return max(0, int(arrays['n_critic_counter']))
   for key, beta in (('beta2_power', cfg.adam_beta2), ('beta1_power', cfg.adam_beta1)):

@@ -64,8 +64,22 @@ class Config:
   # tf.train.ExponentialMovingAverage(decay, global_step) shadows of every model variable, updated by every run
   # (:1063-1092); evaluation reads the shadows (:1150-1155).  DESIGN.md section 7
   moving_average_decay: object = None
+  # Dynamic loss scaling, decided on the device (this project's own rule, the reference has none: DESIGN.md section 7).  An
+  # apply whose summed gradients hold an inf / NaN is skipped and the group's scale halved; after
+  # loss_scale_growth_interval applies in a row it doubles.  loss_scale is then the INITIAL scale, a power of two in
+  # [1, 2**24] (every unscale is exact).  Only 'fp16' grows the scale; the other precisions keep theirs and gain the guard.
+  dynamic_loss_scale: bool = False
+  loss_scale_growth_interval: int = 2000
 
   def __post_init__(self):
     d = self.moving_average_decay
     if d is not None and not (0.0 < float(d) < 1.0):
       raise ValueError('moving_average_decay must lie in (0, 1) or be None (got %r)' % (d,))
+    if self.dynamic_loss_scale:
+      import math
+      s = float(self.loss_scale)
+      if not (1.0 <= s <= 2.0 ** 24) or math.frexp(s)[0] != 0.5:
+        raise ValueError('dynamic_loss_scale: loss_scale is the initial scale and must be a power of two in [1, 2**24] '
+                         '(got %r)' % (self.loss_scale,))
+      if int(self.loss_scale_growth_interval) != self.loss_scale_growth_interval or self.loss_scale_growth_interval < 1:
+        raise ValueError('loss_scale_growth_interval must be an integer >= 1 (got %r)' % (self.loss_scale_growth_interval,))

@@ -879,6 +879,146 @@ __global__ void adam_tick_kernel(int64_t* step, float* lr_t, float lr, float b1,
   }
 }
 
+// ---- dynamic loss scaling (Config.dynamic_loss_scale; this project's own rule): the scale, the skip
+// decision and their bookkeeping live in a TgLossScaleState on the device, so a captured apply graph replays the decision.
+// An fp32 value is +-inf or NaN exactly when its exponent bits are all ones.
+__device__ __forceinline__ int nonfinite_bits(float x) {
+  return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u;
+}
+
+// found |= any x[i] non-finite, i < numel: 4 bytes per element.  VEC (x 16-byte aligned): TG_NF_U 16-byte loads per lane in
+// flight per trip, the numel % 4 elements behind the last whole vector one by one; otherwise element by element.  A wave that
+// saw one stores 1 through its first lane -- every writer writes the same value, so the stores need no atomic and no order --
+// and nobody ever stores 0: several ranges may be checked before one tick.
+constexpr int TG_NF_U = 2, TG_NF_CAP = 2048;      // 16-byte loads in flight per lane and trip; the grid's workgroup cap
+template <bool VEC>
+__global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict__ x, int64_t numel,
+                                                        TgLossScaleState* __restrict__ ls) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  int bad = 0;
+  int64_t done = 0;
+  if constexpr (VEC) {
+    const int64_t nvec = numel >> 2;
+    for (int64_t i = tid; i < nvec; i += TG_NF_U * nthr) {
+      Vec16<float> a[TG_NF_U];
+#pragma unroll
+      for (int u = 0; u < TG_NF_U; ++u) {
+        const int64_t j = i + u * nthr;
+        a[u] = ldv(x + 4 * (j < nvec ? j : i));
+      }
+#pragma unroll
+      for (int u = 0; u < TG_NF_U; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bad |= nonfinite_bits(a[u].v[e]);
+    }
+    done = nvec << 2;
+  }
+  for (int64_t i = done + tid; i < numel; i += nthr) bad |= nonfinite_bits(x[i]);
+  if (__any(bad) && (threadIdx.x & 63) == 0) ls->found = 1;
+}
+
+// One thread, once per apply of a group.  S = the scale the backward just used; the apply in flight unscales with 1 / S
+// (exact: S is a power of two), the group's next backward is seeded with the new S / world.  found: the apply is skipped,
+// S <- max(S / 2, 1), the shared Adam step and rate stay; otherwise adam_tick_kernel's step (the same double arithmetic, the
+// same bits) and, after `interval` good applies in a row, S <- min(2 S, max_scale).
+__global__ void loss_scale_tick_kernel(TgLossScaleState* ls, int64_t* step, float* lr_t, float lr, float b1, float b2,
+                                       int interval, float max_scale, int world) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float S = ls->scale;
+  const int found = ls->found != 0;
+  float next = S;
+  if (found) {
+    next = fmaxf(S * 0.5f, 1.f);
+    ls->good_steps = 0;
+    ls->skipped += 1;
+  } else {
+    const int64_t t = step[0] + 1;
+    step[0] = t;
+    lr_t[0] = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
+    const int good = ls->good_steps + 1;
+    if (good >= interval) next = fminf(2.f * S, max_scale);
+    ls->good_steps = good >= interval ? 0 : good;
+  }
+  ls->inv_scale = 1.f / S;
+  ls->skip = found;
+  ls->found = 0;
+  ls->scale = next;
+  ls->seed = (float)((double)next / (double)world);
+}
+
+// adam_kernel (rate from the device, no shadow) behind the state's decision: a skipped apply stores nothing.
+__global__ void adam_guarded_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m,
+                                    float* __restrict__ v, int64_t numel, const float* __restrict__ lr_t_dev, float b1, float b2,
+                                    float eps, const TgLossScaleState* __restrict__ ls) {
+  if (ls->skip) return;
+  const float lr_t = lr_t_dev[0], gscale = ls->inv_scale;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
+    float mi = m[i], vi = v[i];
+    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
+    m[i] = mi;
+    v[i] = vi;
+    th[i] = t;
+  }
+}
+
+// adam_ema_kernel behind the state's decision: a skipped apply is ema_kernel over the unchanged theta (12 bytes per element
+// instead of 36) -- every run updates every average.
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_ema_guarded_kernel(float* __restrict__ th, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               float* __restrict__ avg, int64_t numel,
+                                                               const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
+                                                               const TgLossScaleState* __restrict__ ls,
+                                                               const float* __restrict__ w_dev) {
+  const float lr_t = lr_t_dev[0], w = w_dev[0], gscale = ls->inv_scale;
+  const bool skip = ls->skip != 0;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  int64_t done = 0;
+  if constexpr (VEC) {
+    const int64_t nvec = numel >> 2;
+    if (skip) {
+      for (int64_t i = tid; i < nvec; i += nthr) {
+        Vec16<float> a4 = ldv(avg + 4 * i);
+        const Vec16<float> t4 = ldv(th + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a4.v[e] = ema_element(a4.v[e], t4.v[e], w);
+        stv(avg + 4 * i, a4);
+      }
+    } else {
+      for (int64_t i = tid; i < nvec; i += nthr) {
+        Vec16<float> t4 = ldv(th + 4 * i), m4 = ldv(m + 4 * i), v4 = ldv(v + 4 * i), a4 = ldv(avg + 4 * i);
+        const Vec16<float> g4 = ldv(g + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float mi = m4.v[e], vi = v4.v[e];
+          const float t = adam_element(t4.v[e], g4.v[e], mi, vi, lr_t, b1, b2, eps, gscale);
+          m4.v[e] = mi;
+          v4.v[e] = vi;
+          t4.v[e] = t;
+          a4.v[e] = ema_element(a4.v[e], t, w);
+        }
+        stv(m + 4 * i, m4);
+        stv(v + 4 * i, v4);
+        stv(th + 4 * i, t4);
+        stv(avg + 4 * i, a4);
+      }
+    }
+    done = nvec << 2;
+  }
+  for (int64_t i = done + tid; i < numel; i += nthr) {
+    if (skip) {
+      avg[i] = ema_element(avg[i], th[i], w);
+      continue;
+    }
+    float mi = m[i], vi = v[i];
+    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
+    m[i] = mi;
+    v[i] = vi;
+    th[i] = t;
+    avg[i] = ema_element(avg[i], t, w);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1215,6 +1355,60 @@ int tg_adam_tick(int64_t* step_dev, float* lr_t_dev, float lr, float beta1, floa
   TG_CHECK(step_dev && lr_t_dev, TG_EINVAL, "tg_adam_tick: null pointer");
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev, lr_t_dev, lr, beta1, beta2);
   TG_LAUNCH_CHECK("tg_adam_tick");
+  return TG_OK;
+}
+
+size_t tg_loss_scale_state_bytes(void) { return sizeof(TgLossScaleState); }
+
+int tg_nonfinite_check(const float* x, int64_t numel, TgLossScaleState* state, void* stream) {
+  TG_CHECK(x && state, TG_EINVAL, "tg_nonfinite_check: null pointer");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_nonfinite_check: numel must be positive (got %lld)", (long long)numel);
+  // at most 2048 workgroups (8 per CU, 32 KiB of loads in flight per CU with 16 bytes per lane); the rest is the grid stride
+  if (tg_aligned16(x))
+    hipLaunchKernelGGL(nonfinite_kernel<true>, dim3(tg_grid_for((numel + 4 * TG_NF_U - 1) / (4 * TG_NF_U), 256, TG_NF_CAP)), dim3(256), 0, (hipStream_t)stream,
+                       x, numel, state);
+  else
+    hipLaunchKernelGGL(nonfinite_kernel<false>, dim3(tg_grid_for(numel, 256, 2048)), dim3(256), 0, (hipStream_t)stream, x,
+                       numel, state);
+  TG_LAUNCH_CHECK("tg_nonfinite_check");
+  return TG_OK;
+}
+
+int tg_loss_scale_tick(TgLossScaleState* state, int64_t* step_dev, float* lr_t_dev, float lr, float beta1, float beta2,
+                       int growth_interval, float max_scale, int world, void* stream) {
+  TG_CHECK(state && step_dev && lr_t_dev, TG_EINVAL, "tg_loss_scale_tick: null pointer");
+  TG_CHECK(growth_interval >= 1 && max_scale >= 1.f && world >= 1, TG_EINVAL,
+           "tg_loss_scale_tick: growth_interval (%d), max_scale (%g) and world (%d) must be at least 1", growth_interval,
+           (double)max_scale, world);
+  hipLaunchKernelGGL(loss_scale_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, step_dev, lr_t_dev, lr, beta1,
+                     beta2, growth_interval, max_scale, world);
+  TG_LAUNCH_CHECK("tg_loss_scale_tick");
+  return TG_OK;
+}
+
+int tg_adam_step_guarded(float* theta, const float* grad, float* m, float* v, int64_t numel, const float* lr_t_dev,
+                         float beta1, float beta2, float eps, const TgLossScaleState* state, void* stream) {
+  TG_CHECK(theta && grad && m && v && lr_t_dev && state, TG_EINVAL, "tg_adam_step_guarded: null pointer");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_step_guarded: numel must be positive (got %lld)", (long long)numel);
+  hipLaunchKernelGGL(adam_guarded_kernel, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta, grad, m, v,
+                     numel, lr_t_dev, beta1, beta2, eps, state);
+  TG_LAUNCH_CHECK("tg_adam_step_guarded");
+  return TG_OK;
+}
+
+int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel,
+                             const float* lr_t_dev, float beta1, float beta2, float eps, const TgLossScaleState* state,
+                             const float* w_dev, void* stream) {
+  TG_CHECK(theta && grad && m && v && avg && lr_t_dev && state && w_dev, TG_EINVAL, "tg_adam_ema_step_guarded: null pointer");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step_guarded: numel must be positive (got %lld)", (long long)numel);
+  const bool vec = tg_aligned16(theta) && tg_aligned16(grad) && tg_aligned16(m) && tg_aligned16(v) && tg_aligned16(avg);
+  if (vec)
+    hipLaunchKernelGGL(adam_ema_guarded_kernel<true>, dim3(tg_grid_for((numel + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream,
+                       theta, grad, m, v, avg, numel, lr_t_dev, beta1, beta2, eps, state, w_dev);
+  else
+    hipLaunchKernelGGL(adam_ema_guarded_kernel<false>, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta,
+                       grad, m, v, avg, numel, lr_t_dev, beta1, beta2, eps, state, w_dev);
+  TG_LAUNCH_CHECK("tg_adam_ema_step_guarded");
   return TG_OK;
 }
 

@@ -115,6 +115,8 @@ def run_progressive(base_cfg, batch_fn, start_hw=4, max_hw=256, hw_to_batch_size
       ckpt.save(tr, cur_dir, global_step=steps, max_to_keep=max_to_keep)
       last_dir = cur_dir
     history.append(dict(stage=name, hw=hw, is_growing=growing, batch_size=bsz, steps=steps, warm_started=len(loaded)))
+    if cfg.dynamic_loss_scale:      # where the stage ended: each group's scale and skipped applies, the applies made
+      history[-1]['loss_scale'] = tr.loss_scale_state()
     if on_stage_end is not None:
       on_stage_end(name, tr)
     tr.close()

@@ -508,6 +508,15 @@ class Trainer:
       self._ema_w = None
       self._ema_table = self._build_ema_table()
       self._set_ema_weight()
+    # Config.dynamic_loss_scale: one TgLossScaleState per optimiser group, on the device (an overflow in the discriminator's
+    # penalty pass says nothing about the generator); the seed of a group's backward is a view of its state
+    self._ls = None
+    if cfg.dynamic_loss_scale:
+      self._ls = {g: torch.zeros(8, dtype=torch.int32, device=self.device) for g in self.store.GROUPS}
+      self._ls_seed = {g: t.view(torch.float32)[1:2] for g, t in self._ls.items()}
+      self._ls_max = 2.0 ** 24 if cfg.precision == 'fp16' else float(cfg.loss_scale)      # only fp16 grows its scale
+      for g in self.store.GROUPS:
+        self.set_loss_scale(g, cfg.loss_scale)
 
   def close(self):
     """Releases the captured graphs and this trainer's entries in the pack / gradient-sink registries."""
@@ -537,6 +546,26 @@ class Trainer:
     self.adam_t = int(t)
     self._adam_step_dev.fill_(int(t))
 
+  def set_loss_scale(self, group, scale, good_steps=0, skipped=0):
+    """Writes ``group``'s loss-scale state from the host (construction, restoring a checkpoint)."""
+    from ._lib import TgLossScaleState
+    st = TgLossScaleState(scale=float(scale), seed=loss_scale_for_clones(scale, self.world), inv_scale=1.0 / float(scale),
+                          found=0, skip=0, good_steps=int(good_steps), skipped=int(skipped))
+    self._ls[group].copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+
+  def loss_scale_state(self):
+    """-> {'g': {'scale', 'good_steps', 'skipped'}, 'd': {...}, 'applies': applies the shared optimiser actually made (the
+    device step counter; ``adam_t`` counts the attempted ones)}.  The ONE place of the dynamic path that waits for the
+    device: call it every few hundred runs (a log line, a stage's end), not every run."""
+    from ._lib import TgLossScaleState
+    assert self._ls is not None, 'this trainer has a static loss scale (Config.dynamic_loss_scale)'
+    out = {}
+    for g, t in self._ls.items():
+      st = TgLossScaleState.from_buffer_copy(t.cpu().numpy().tobytes())
+      out[g] = dict(scale=float(st.scale), good_steps=int(st.good_steps), skipped=int(st.skipped))
+    out['applies'] = int(self._adam_step_dev.item())
+    return out
+
   def _uniform(self, n):
     """n fp32 U[0, 1) draws on the device (ops.uniform: the draw counter lives on the device, so a captured step draws
     new numbers on every replay)."""
@@ -550,6 +579,10 @@ class Trainer:
     st = torch.cuda.current_stream().cuda_stream
     self.adam_t += 1
     step_dev, lr_dev, lr = self._adam_step_dev, self._lr_t_dev, c.learning_rate
+    if self._ls is not None:
+      self._adam_guarded(group, st)
+      PackCache.refresh(self._group_weights[group])      # unconditional: after a skipped apply it repacks the same bits
+      return
     call('tg_adam_tick', step_dev.data_ptr(), lr_dev.data_ptr(), lr, c.adam_beta1, c.adam_beta2, st)
     if s.averaged:
       self._adam_ema(group, st)
@@ -560,8 +593,25 @@ class Trainer:
            work=('adam:numel%d' % s.flat[group].numel(), 0, 28 * s.flat[group].numel()))
     PackCache.refresh(self._group_weights[group])
 
+  def _adam_guarded(self, group, st):
+    """Config.dynamic_loss_scale: check -> tick -> guarded apply on the main stream, so a captured apply graph replays the
+    decision.  The check reads the group's WHOLE flat gradient buffer after the clones' sum (reducer.finish() precedes
+    _adam; inf + finite, inf - inf and NaN all stay non-finite through a sum), so every clone decides the same.  The host
+    neither learns nor asks whether the apply was made: n_critic_counter, global_step and adam_t advance as ever."""
+    c, s, ls = self.cfg, self.store, self._ls[group].data_ptr()
+    n = s.flat[group].numel()
+    call('tg_nonfinite_check', s.grad[group].data_ptr(), n, ls, st, work=('nonfinite:numel%d' % n, 0, 4 * n))
+    call('tg_loss_scale_tick', ls, self._adam_step_dev.data_ptr(), self._lr_t_dev.data_ptr(), c.learning_rate, c.adam_beta1,
+         c.adam_beta2, int(c.loss_scale_growth_interval), self._ls_max, self.world, st)
+    if s.averaged:
+      self._adam_ema(group, st, ls)
+    else:
+      call('tg_adam_step_guarded', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
+           s.v[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2, c.opt_epsilon, ls, st,
+           work=('adam_guarded:numel%d' % n, 0, 28 * n))
+
   # ---- moving averages (--moving_average_decay) ---------------------------------------------------------------
-  def _adam_ema(self, group, st):
+  def _adam_ema(self, group, st, ls=None):
     """The apply of ``group`` fused with the moving average of its variables, then the averages of everything the run did
     not apply: tf.train.ExponentialMovingAverage.apply is ONE op group over all model variables in every session.run
     (model/model_inheritor.py:1063-1066,1090-1092), so a discriminator run also moves the generator's averages towards the
@@ -569,12 +619,18 @@ class Trainer:
     state updates; here it reads the post-run values: the three launches follow the apply on the main stream, after the
     run's moving statistics / spectral-norm u / gdrop updates (all joined before the apply) -- under graph capture they are
     part of the captured apply graph.  Data-parallel runs need no communication: every clone applies the same all-reduced
-    gradients to the same parameters, so the averages agree wherever the parameters do."""
+    gradients to the same parameters, so the averages agree wherever the parameters do.  ``ls`` (dynamic loss scaling): the
+    guarded apply -- a skipped one still moves the group's averages, towards its unchanged parameters."""
     c, s, w = self.cfg, self.store, self._ema_w_dev.data_ptr()
     n = s.flat[group].numel()
-    call('tg_adam_ema_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(), s.v[group].data_ptr(),
-         s.avg[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale,
-         w, st, work=('adam_ema:numel%d' % n, 0, 36 * n))
+    if ls is not None:
+      call('tg_adam_ema_step_guarded', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
+           s.v[group].data_ptr(), s.avg[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2,
+           c.opt_epsilon, ls, w, st, work=('adam_ema_guarded:numel%d' % n, 0, 36 * n))
+    else:
+        call('tg_adam_ema_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(), s.v[group].data_ptr(),
+           s.avg[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale,
+           w, st, work=('adam_ema:numel%d' % n, 0, 36 * n))
     for other in s.GROUPS:
       if other != group:
         n = s.flat[other].numel()
@@ -637,16 +693,22 @@ class Trainer:
       out = (loss.detach(), {k: v.detach() for k, v in terms.items()})
       if group == 'g' and self.cfg.use_gdrop:
         self._update_gdrop(out[0])
-      k = loss_scale_for_clones(self.cfg.loss_scale, self.world)       # model_deploy.py:265-268,308-313
-      scaled = loss if k == 1.0 else loss * k
+      if self._ls is not None:      # the scale is the backward's seed, read from the group's device state (S / world)
+        scaled = loss
+      else:
+        k = loss_scale_for_clones(self.cfg.loss_scale, self.world)       # model_deploy.py:265-268,308-313
+        scaled = loss if k == 1.0 else loss * k
       ops.GradSink.pair = True
       # the slab reductions of the filter gradients that feed gradient sinks: queued, one launch per backward segment
       ops.defer_slab_reductions(True)
       for seg in range(nseg):
         if seg == 0:
-          if getattr(self, '_seed', None) is None or self._seed.device != scaled.device:
-            self._seed = torch.ones(1, dtype=torch.float32, device=scaled.device)      # d loss / d loss, made once
-          scaled.backward(self._seed)
+          if self._ls is not None:
+            scaled.backward(self._ls_seed[group])
+          else:
+            if getattr(self, '_seed', None) is None or self._seed.device != scaled.device:
+              self._seed = torch.ones(1, dtype=torch.float32, device=scaled.device)      # d loss / d loss, made once
+            scaled.backward(self._seed)
         else:
           roots, grads = ops.Cuts.roots(seg)
           torch.autograd.backward(roots, grads)
@@ -706,7 +768,9 @@ class Trainer:
                 host=(self.n_critic_counter, self.global_step, self.adam_t), rng=torch.cuda.get_rng_state(self.device),
                 # the moving averages and their weight: the undone warm-up of a capture must leave no trace in them
                 avg={g: v.clone() for g, v in s.avg.items()}, state_avg={k: v.clone() for k, v in s.state_avg.items()},
-                ema_w=(self._ema_w, self._ema_w_dev.clone()) if s.averaged else None)
+                ema_w=(self._ema_w, self._ema_w_dev.clone()) if s.averaged else None,
+                # the loss-scale states: an undone warm-up leaves the scale, the counts and the skipped totals untouched
+                ls={g: t.clone() for g, t in self._ls.items()} if self._ls is not None else None)
 
   def _restore(self, snap):
     s = self.store
@@ -728,6 +792,9 @@ class Trainer:
       if snap['ema_w'] is not None:
         self._ema_w = snap['ema_w'][0]
         self._ema_w_dev.copy_(snap['ema_w'][1])
+      if snap['ls'] is not None:
+        for g, t in snap['ls'].items():
+          self._ls[g].copy_(t)
     self.n_critic_counter, self.global_step, self.adam_t = snap['host']
     torch.cuda.set_rng_state(snap['rng'], self.device)
     for g in s.GROUPS:                      # the packs follow the restored masters
