@@ -3,6 +3,8 @@ runtime (hip/hip_runtime.h, emu.cpp), same C ABI as libtwingan_hip.so.  TEST INF
 own source (index arithmetic, LDS staging, lane exchanges, MFMA layouts) against the oracle; never loaded by the product.
 
   python tests/hipemu/build.py [--force]     -> path of the library (rebuilt when a source is newer)
+  python tests/hipemu/build.py --bounds      -> path of tests/hipemu/_build_asan/bounds, the stand-alone AddressSanitizer
+                                                driver of bounds_main.cpp (`bounds --list`, `bounds --case NAME`)
 """
 import os
 import re
@@ -33,13 +35,16 @@ except OSError:
 _DYN = re.compile(r'extern\s+__shared__\s+(?:__attribute__\(\(aligned\(\d+\)\)\)\s+)?([A-Za-z_][A-Za-z0-9_ ]*?)\s+([A-Za-z_][A-Za-z0-9_]*)\[\];')
 
 
-def translate(name):
+def translate(name, out=None):
   """The one construct a macro cannot reach: `extern __shared__ T name[];` becomes a pointer to the emulator's dynamic LDS."""
   src = open(os.path.join(CSRC, name + '.hip')).read()
   src = _DYN.sub(lambda m: '%s* const %s = (%s*)hipemu::dyn_lds;' % (m.group(1), m.group(2), m.group(1)), src)
-  dst = os.path.join(OUT, name + '.cpp')
+  dst = os.path.join(out or OUT, name + '.cpp')
   if not os.path.exists(dst) or open(dst).read() != src:
-    open(dst, 'w').write(src)
+    tmp = dst + '.tmp%d' % os.getpid()      # written aside, then renamed: another process may be building from dst
+    with open(tmp, 'w') as fh:
+      fh.write(src)
+    os.replace(tmp, dst)
   return dst
 
 
@@ -51,9 +56,9 @@ def stale(target, deps):
 
 
 def compile_one(job):
-  src, obj, deps, force = job
+  src, obj, deps, force = job[:4]
   if force or stale(obj, deps):
-    subprocess.check_call([CXX] + FLAGS + ['-c', src, '-o', obj])
+    subprocess.check_call([CXX] + (job[4] if len(job) > 4 else FLAGS) + ['-c', src, '-o', obj])
     return True
   return False
 
@@ -75,5 +80,37 @@ def build(force=False):
   return LIB
 
 
+# AddressSanitizer over the emulated kernels.  use-after-return=never keeps the sanitizer's fake stacks away from the
+# emulator's hand-switched fiber stacks (emu.cpp); the objects live in a directory of their own so that the plain library
+# keeps its flags and its cache.  The result is a PROGRAM: nothing loads it into python.
+OUT_ASAN = os.path.join(HERE, '_build_asan')
+BOUNDS = os.path.join(OUT_ASAN, 'bounds')
+ASAN_FLAGS = ['-fsanitize=address', '-fsanitize-address-use-after-return=never', '-fno-omit-frame-pointer', '-g1']
+
+
+def build_bounds(force=False):
+  """Builds the stand-alone sanitized bounds driver (bounds_main.cpp + every emulated object) and returns its path."""
+  os.makedirs(OUT_ASAN, exist_ok=True)
+  common = [os.path.join(CSRC, 'tg_common.h'), os.path.join(CSRC, 'conv_internal.h'), os.path.join(ROOT, 'include', 'twingan_hip.h'),
+            os.path.join(HERE, 'hip', 'hip_runtime.h'), os.path.abspath(__file__)]
+  flags = FLAGS + ASAN_FLAGS
+  jobs = []
+  for name in SOURCES:
+    jobs.append((translate(name, OUT_ASAN), os.path.join(OUT_ASAN, name + '.o'), [os.path.join(CSRC, name + '.hip')] + common, force, flags))
+  for name in ('emu', 'bounds_main'):
+    src = os.path.join(HERE, name + '.cpp')
+    jobs.append((src, os.path.join(OUT_ASAN, name + '.o'), [src, os.path.join(HERE, 'bounds_cases.inc')] + common, force, flags))
+  with ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, 16)) as ex:
+    changed = list(ex.map(compile_one, jobs))
+  if any(changed) or not os.path.exists(BOUNDS):
+    tmp = BOUNDS + '.tmp%d' % os.getpid()
+    subprocess.check_call([CXX] + ASAN_FLAGS + [j[1] for j in jobs] + ['-ldl', '-o', tmp])
+    os.replace(tmp, BOUNDS)
+  return BOUNDS
+
+
 if __name__ == '__main__':
-  print(build(force='--force' in sys.argv))
+  if '--bounds' in sys.argv:
+    print(build_bounds(force='--force' in sys.argv))
+  else:
+    print(build(force='--force' in sys.argv))

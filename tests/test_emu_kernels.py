@@ -59,3 +59,13 @@ def test_thin_output_kernels_over_the_emulated_kernels():
             '(thin_output_kernel_matches and 16-16-dtype0) or spectral_norm_of_many'], timeout=2400)
   assert r.returncode == 0, r.stdout[-3000:]
   assert ' passed' in r.stdout[-3000:]
+
+
+def test_wrapper_bounds_cases_over_the_emulated_kernels():
+  """tests/test_gpu_bounds.py (guard bands and poison round every tensor the wrappers allocate, tests/guarded.py) on the host:
+  the cases are sound before they meet a GPU.  All but the dispatch-table rows at their recorded batches (a minute each here)
+  and the preprocessor, which asks torch for a GPU itself."""
+  r = _run(['tests/test_gpu_bounds.py', '-n', '8', '-k', 'not edge_rows and not preprocessing'], timeout=1500)
+  tail = r.stdout[-3000:]
+  assert r.returncode == 0, tail
+  assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail.split('passed')[-1], tail

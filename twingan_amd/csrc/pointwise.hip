@@ -642,6 +642,18 @@ __global__ void pw_wgrad_kernel(const T* __restrict__ small, const T* __restrict
       for (int wv = 0; wv < nw; ++wv) t += sacc[(1 + wv) * ns * cb + i];
       sacc[i] = t;
     }
+  } else if (PART || gridDim.x == 1) {
+    // a fixed order is promised: by the ordered form on every run, and by the one-workgroup launch that the fp32 type and
+    // the deterministic mode get (launch_pw_wgrad).  The pixel lanes add in turn (threads of one turn own different channel
+    // vectors) instead of by LDS atomics in arrival order
+    for (int turn = 0; turn < lanes; ++turn) {
+      if (pl == turn) {
+        for (int s = 0; s < ns; ++s)
+#pragma unroll
+          for (int j = 0; j < V; ++j) sacc[s * cb + v * V + j] += acc[s][j];
+      }
+      __syncthreads();
+    }
   } else if (pl < lanes) {
     for (int s = 0; s < ns; ++s)
 #pragma unroll
