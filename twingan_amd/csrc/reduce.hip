@@ -743,7 +743,7 @@ __global__ void small_gemm_wave_kernel(const float* __restrict__ a, const float*
 }
 
 // TF-1.x Adam (model/model_inheritor.py:537-542): epsilon OUTSIDE the bias-corrected sqrt.  One element, shared by
-// adam_kernel and adam_ema_kernel so that both write the same bits: the two multiply-adds are spelled as the fused
+// both loops of apply_kernel so that every instantiation writes the same bits: the two multiply-adds are spelled as the fused
 // operations the compiler's contraction made of `b1 * m + (1 - b1) * g` and `b2 * v + (1 - b2) * g * g`, so their
 // rounding does not depend on the loop they are inlined into.
 __device__ __forceinline__ float adam_element(float th, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
@@ -760,70 +760,13 @@ __device__ __forceinline__ float adam_element(float th, float g, float& m, float
 // the product and the subtraction as one fused multiply-add.  avg == var gives avg back bit for bit.
 __device__ __forceinline__ float ema_element(float avg, float var, float w) { return fmaf(-(avg - var), w, avg); }
 
-__global__ void adam_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, bf16* __restrict__ shadow, int64_t numel, float lr_t,
-                            const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale) {
-  if (lr_t_dev) lr_t = lr_t_dev[0];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    float mi = m[i], vi = v[i];
-    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
-    m[i] = mi;
-    v[i] = vi;
-    th[i] = t;
-    if (shadow) shadow[i] = (bf16)t;
-  }
-}
-
-// The Adam apply and the moving average of the parameters it just wrote, in one pass over the group's flat buffers: 36 bytes
-// per element (read theta, g, m, v, avg; write theta, m, v, avg) against 28 + 12 for adam_kernel followed by ema_kernel.
-// VEC: every pointer is 16-byte aligned -- one 16-byte access per lane and array; the numel % 4 elements behind the last
-// whole vector are taken one by one.  Otherwise (any 4-byte-aligned pointers) element by element.
+// The moving average alone over a flat buffer, thread tid's share of nthr: 12 bytes per element.  VEC: both pointers are
+// 16-byte aligned -- one 16-byte access per lane and array; the numel % 4 elements behind the last whole vector are taken one
+// by one.  Otherwise (any 4-byte-aligned pointers) element by element.  The kernel hands tid and nthr in: read in here, the
+// workgroup size costs a vector load and 4 VGPRs.
 template <bool VEC>
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ th, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v,
-                                                       float* __restrict__ avg, int64_t numel,
-                                                       const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
-                                                       float gscale, const float* __restrict__ w_dev) {
-  const float lr_t = lr_t_dev[0], w = w_dev[0];
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  int64_t done = 0;
-  if constexpr (VEC) {
-    const int64_t nvec = numel >> 2;
-    for (int64_t i = tid; i < nvec; i += nthr) {
-      Vec16<float> t4 = ldv(th + 4 * i), m4 = ldv(m + 4 * i), v4 = ldv(v + 4 * i), a4 = ldv(avg + 4 * i);
-      const Vec16<float> g4 = ldv(g + 4 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float mi = m4.v[e], vi = v4.v[e];
-        const float t = adam_element(t4.v[e], g4.v[e], mi, vi, lr_t, b1, b2, eps, gscale);
-        m4.v[e] = mi;
-        v4.v[e] = vi;
-        t4.v[e] = t;
-        a4.v[e] = ema_element(a4.v[e], t, w);
-      }
-      stv(m + 4 * i, m4);
-      stv(v + 4 * i, v4);
-      stv(th + 4 * i, t4);
-      stv(avg + 4 * i, a4);
-    }
-    done = nvec << 2;
-  }
-  for (int64_t i = done + tid; i < numel; i += nthr) {
-    float mi = m[i], vi = v[i];
-    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
-    m[i] = mi;
-    v[i] = vi;
-    th[i] = t;
-    avg[i] = ema_element(avg[i], t, w);
-  }
-}
-
-// The moving average alone on a flat buffer (the group a run did not apply): 12 bytes per element.  VEC as above.
-template <bool VEC>
-__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const float* __restrict__ var, int64_t numel,
-                                                  const float* __restrict__ w_dev) {
-  const float w = w_dev[0];
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+__device__ __forceinline__ void ema_span(float* __restrict__ avg, const float* __restrict__ var, int64_t numel, float w,
+                                         int64_t tid, int64_t nthr) {
   int64_t done = 0;
   if constexpr (VEC) {
     const int64_t nvec = numel >> 2;
@@ -837,6 +780,80 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const
     done = nvec << 2;
   }
   for (int64_t i = done + tid; i < numel; i += nthr) avg[i] = ema_element(avg[i], var[i], w);
+}
+
+// The group a run did not apply.  Its own kernel, not an instantiation of apply_kernel: 18 VGPRs against 51.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const float* __restrict__ var, int64_t numel,
+                                                  const float* __restrict__ w_dev) {
+  ema_span<VEC>(avg, var, numel, w_dev[0], (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// What the four optimiser entry points (tg_adam_step, tg_adam_ema_step and their _guarded forms) hand to apply_kernel: what all
+// of them have, then what only some have.
+struct ApplyArgs {
+  float* th;
+  const float* g;
+  float *m, *v;
+  int64_t numel;
+  float b1, b2, eps;
+  const float* lr_t_dev = nullptr;           // the rate; null: lr_t
+  float lr_t = 0.f;
+  float gscale = 0.f;                        // multiplies g first, without ls
+  const TgLossScaleState* ls = nullptr;      // the guard: the gradient scale is its inv_scale, its skip decides
+  float* avg = nullptr;                      // the fused forms (EMA instantiations)
+  const float* w_dev = nullptr;
+  bf16* shadow = nullptr;                    // tg_adam_step's rounded copy of theta (the instantiation without EMA)
+};
+
+// The Adam apply of one group's flat buffers, 28 bytes per element (read theta, g, m, v; write theta, m, v).  EMA: the moving
+// average of the parameters it just wrote in the same pass, 36 bytes per element against 28 + 12 for the apply followed by
+// ema_kernel.  VEC as for ema_span, over all five pointers.  ls (dynamic loss scaling, below): the gradient scale is the
+// state's inv_scale, and a skipped apply stores nothing -- but for the average, which is then ema_span over the unchanged
+// theta (12 bytes per element): every run updates every average.
+template <bool VEC, bool EMA>
+__global__ __launch_bounds__(256) void apply_kernel(const ApplyArgs a) {
+  static_assert(EMA || !VEC, "the 16-byte loop is the fused one: it has the average and no bf16 shadow");
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  if (a.ls && a.ls->skip) {
+    if constexpr (EMA) ema_span<VEC>(a.avg, a.th, a.numel, a.w_dev[0], tid, nthr);
+    return;
+  }
+  const float lr_t = a.lr_t_dev ? a.lr_t_dev[0] : a.lr_t, gscale = a.ls ? a.ls->inv_scale : a.gscale;
+  float w = 0.f;
+  if constexpr (EMA) w = a.w_dev[0];
+  int64_t done = 0;
+  if constexpr (VEC) {
+    const int64_t nvec = a.numel >> 2;
+    for (int64_t i = tid; i < nvec; i += nthr) {
+      Vec16<float> t4 = ldv(a.th + 4 * i), m4 = ldv(a.m + 4 * i), v4 = ldv(a.v + 4 * i), a4 = ldv(a.avg + 4 * i);
+      const Vec16<float> g4 = ldv(a.g + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float mi = m4.v[e], vi = v4.v[e];
+        const float t = adam_element(t4.v[e], g4.v[e], mi, vi, lr_t, a.b1, a.b2, a.eps, gscale);
+        m4.v[e] = mi;
+        v4.v[e] = vi;
+        t4.v[e] = t;
+        a4.v[e] = ema_element(a4.v[e], t, w);
+      }
+      stv(a.m + 4 * i, m4);
+      stv(a.v + 4 * i, v4);
+      stv(a.th + 4 * i, t4);
+      stv(a.avg + 4 * i, a4);
+    }
+    done = nvec << 2;
+  }
+  for (int64_t i = done + tid; i < a.numel; i += nthr) {
+    float mi = a.m[i], vi = a.v[i], ai = 0.f;
+    if constexpr (EMA) ai = a.avg[i];      // with the other loads: behind a store it would wait for the whole update
+    const float t = adam_element(a.th[i], a.g[i], mi, vi, lr_t, a.b1, a.b2, a.eps, gscale);
+    a.m[i] = mi;
+    a.v[i] = vi;
+    a.th[i] = t;
+    if constexpr (EMA) a.avg[i] = ema_element(ai, t, w);
+    else if (a.shadow) a.shadow[i] = (bf16)t;
+  }
 }
 
 // ---- the moving averages of MANY small tensors in one launch (the non-trainable state: a few hundred separately allocated
@@ -870,13 +887,15 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const EmaJob* __restrict
   }
 }
 
-// One thread: t = ++step; lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)   (tf.train.AdamOptimizer._prepare/_apply_dense)
+// t = ++step; lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)   (tf.train.AdamOptimizer._prepare/_apply_dense).  One thread calls it.
+__device__ __forceinline__ void adam_tick(int64_t* step, float* lr_t, float lr, float b1, float b2) {
+  const int64_t t = step[0] + 1;
+  step[0] = t;
+  lr_t[0] = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
+}
+
 __global__ void adam_tick_kernel(int64_t* step, float* lr_t, float lr, float b1, float b2) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const int64_t t = step[0] + 1;
-    step[0] = t;
-    lr_t[0] = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-  }
+  if (threadIdx.x == 0 && blockIdx.x == 0) adam_tick(step, lr_t, lr, b1, b2);
 }
 
 // ---- dynamic loss scaling (Config.dynamic_loss_scale; this project's own rule): the scale, the skip
@@ -919,8 +938,8 @@ __global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict_
 
 // One thread, once per apply of a group.  S = the scale the backward just used; the apply in flight unscales with 1 / S
 // (exact: S is a power of two), the group's next backward is seeded with the new S / world.  found: the apply is skipped,
-// S <- max(S / 2, 1), the shared Adam step and rate stay; otherwise adam_tick_kernel's step (the same double arithmetic, the
-// same bits) and, after `interval` good applies in a row, S <- min(2 S, max_scale).
+// S <- max(S / 2, 1), the shared Adam step and rate stay; otherwise adam_tick_kernel's step and, after `interval` good applies
+// in a row, S <- min(2 S, max_scale).
 __global__ void loss_scale_tick_kernel(TgLossScaleState* ls, int64_t* step, float* lr_t, float lr, float b1, float b2,
                                        int interval, float max_scale, int world) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -932,9 +951,7 @@ __global__ void loss_scale_tick_kernel(TgLossScaleState* ls, int64_t* step, floa
     ls->good_steps = 0;
     ls->skipped += 1;
   } else {
-    const int64_t t = step[0] + 1;
-    step[0] = t;
-    lr_t[0] = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
+    adam_tick(step, lr_t, lr, b1, b2);
     const int good = ls->good_steps + 1;
     if (good >= interval) next = fminf(2.f * S, max_scale);
     ls->good_steps = good >= interval ? 0 : good;
@@ -946,77 +963,17 @@ __global__ void loss_scale_tick_kernel(TgLossScaleState* ls, int64_t* step, floa
   ls->seed = (float)((double)next / (double)world);
 }
 
-// adam_kernel (rate from the device, no shadow) behind the state's decision: a skipped apply stores nothing.
-__global__ void adam_guarded_kernel(float* __restrict__ th, const float* __restrict__ g, float* __restrict__ m,
-                                    float* __restrict__ v, int64_t numel, const float* __restrict__ lr_t_dev, float b1, float b2,
-                                    float eps, const TgLossScaleState* __restrict__ ls) {
-  if (ls->skip) return;
-  const float lr_t = lr_t_dev[0], gscale = ls->inv_scale;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
-    float mi = m[i], vi = v[i];
-    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
-    m[i] = mi;
-    v[i] = vi;
-    th[i] = t;
-  }
-}
-
-// adam_ema_kernel behind the state's decision: a skipped apply is ema_kernel over the unchanged theta (12 bytes per element
-// instead of 36) -- every run updates every average.
-template <bool VEC>
-__global__ __launch_bounds__(256) void adam_ema_guarded_kernel(float* __restrict__ th, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v,
-                                                               float* __restrict__ avg, int64_t numel,
-                                                               const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
-                                                               const TgLossScaleState* __restrict__ ls,
-                                                               const float* __restrict__ w_dev) {
-  const float lr_t = lr_t_dev[0], w = w_dev[0], gscale = ls->inv_scale;
-  const bool skip = ls->skip != 0;
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  int64_t done = 0;
-  if constexpr (VEC) {
-    const int64_t nvec = numel >> 2;
-    if (skip) {
-      for (int64_t i = tid; i < nvec; i += nthr) {
-        Vec16<float> a4 = ldv(avg + 4 * i);
-        const Vec16<float> t4 = ldv(th + 4 * i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a4.v[e] = ema_element(a4.v[e], t4.v[e], w);
-        stv(avg + 4 * i, a4);
-      }
-    } else {
-      for (int64_t i = tid; i < nvec; i += nthr) {
-        Vec16<float> t4 = ldv(th + 4 * i), m4 = ldv(m + 4 * i), v4 = ldv(v + 4 * i), a4 = ldv(avg + 4 * i);
-        const Vec16<float> g4 = ldv(g + 4 * i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float mi = m4.v[e], vi = v4.v[e];
-          const float t = adam_element(t4.v[e], g4.v[e], mi, vi, lr_t, b1, b2, eps, gscale);
-          m4.v[e] = mi;
-          v4.v[e] = vi;
-          t4.v[e] = t;
-          a4.v[e] = ema_element(a4.v[e], t, w);
-        }
-        stv(m + 4 * i, m4);
-        stv(v + 4 * i, v4);
-        stv(th + 4 * i, t4);
-        stv(avg + 4 * i, a4);
-      }
-    }
-    done = nvec << 2;
-  }
-  for (int64_t i = done + tid; i < numel; i += nthr) {
-    if (skip) {
-      avg[i] = ema_element(avg[i], th[i], w);
-      continue;
-    }
-    float mi = m[i], vi = v[i];
-    const float t = adam_element(th[i], g[i], mi, vi, lr_t, b1, b2, eps, gscale);
-    m[i] = mi;
-    v[i] = vi;
-    th[i] = t;
-    avg[i] = ema_element(avg[i], t, w);
-  }
+// The one launch of apply_kernel.  Only the fused forms (those with an average) have a 16-byte path: it is taken when all
+// five pointers are 16-byte aligned, else the apply goes element by element.  avg and shadow exclude each other: the EMA
+// instantiations store no shadow, and no entry point has both.
+int launch_apply(const ApplyArgs& a, void* stream, const char* name) {
+  const bool ema = a.avg != nullptr;
+  const bool vec =
+      ema && tg_aligned16(a.th) && tg_aligned16(a.g) && tg_aligned16(a.m) && tg_aligned16(a.v) && tg_aligned16(a.avg);
+  auto kernel = vec ? apply_kernel<true, true> : ema ? apply_kernel<false, true> : apply_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3(tg_grid_for(vec ? (a.numel + 3) / 4 : a.numel, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  TG_LAUNCH_CHECK(name);
+  return TG_OK;
 }
 
 }  // namespace
@@ -1289,25 +1246,17 @@ int tg_fc_bwd(const void* x, const float* w, const float* g, void* gx, float* gw
 int tg_adam_step(float* theta, const float* grad, float* m, float* v, void* theta_bf16, int64_t numel, float lr_t,
                  const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, void* stream) {
   TG_CHECK(theta && grad && m && v && numel > 0, TG_EINVAL, "tg_adam_step: bad arguments");
-  hipLaunchKernelGGL(adam_kernel, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta, grad, m, v,
-                     (bf16*)theta_bf16, numel, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale);
-  TG_LAUNCH_CHECK("tg_adam_step");
-  return TG_OK;
+  ApplyArgs a{theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, lr_t, grad_scale};
+  a.shadow = (bf16*)theta_bf16;
+  return launch_apply(a, stream, "tg_adam_step");
 }
 
 int tg_adam_ema_step(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel, const float* lr_t_dev,
                      float beta1, float beta2, float eps, float grad_scale, const float* w_dev, void* stream) {
   TG_CHECK(theta && grad && m && v && avg && lr_t_dev && w_dev, TG_EINVAL, "tg_adam_ema_step: null pointer");
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step: numel must be positive (got %lld)", (long long)numel);
-  const bool vec = tg_aligned16(theta) && tg_aligned16(grad) && tg_aligned16(m) && tg_aligned16(v) && tg_aligned16(avg);
-  if (vec)
-    hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(tg_grid_for((numel + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, theta,
-                       grad, m, v, avg, numel, lr_t_dev, beta1, beta2, eps, grad_scale, w_dev);
-  else
-    hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta, grad,
-                       m, v, avg, numel, lr_t_dev, beta1, beta2, eps, grad_scale, w_dev);
-  TG_LAUNCH_CHECK("tg_adam_ema_step");
-  return TG_OK;
+  return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, grad_scale, nullptr, avg, w_dev}, stream,
+                      "tg_adam_ema_step");
 }
 
 int tg_ema_update(float* avg, const float* var, int64_t numel, const float* w_dev, void* stream) {
@@ -1390,10 +1339,7 @@ int tg_adam_step_guarded(float* theta, const float* grad, float* m, float* v, in
                          float beta1, float beta2, float eps, const TgLossScaleState* state, void* stream) {
   TG_CHECK(theta && grad && m && v && lr_t_dev && state, TG_EINVAL, "tg_adam_step_guarded: null pointer");
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_step_guarded: numel must be positive (got %lld)", (long long)numel);
-  hipLaunchKernelGGL(adam_guarded_kernel, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta, grad, m, v,
-                     numel, lr_t_dev, beta1, beta2, eps, state);
-  TG_LAUNCH_CHECK("tg_adam_step_guarded");
-  return TG_OK;
+  return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, 0.f, state}, stream, "tg_adam_step_guarded");
 }
 
 int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel,
@@ -1401,15 +1347,8 @@ int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v
                              const float* w_dev, void* stream) {
   TG_CHECK(theta && grad && m && v && avg && lr_t_dev && state && w_dev, TG_EINVAL, "tg_adam_ema_step_guarded: null pointer");
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step_guarded: numel must be positive (got %lld)", (long long)numel);
-  const bool vec = tg_aligned16(theta) && tg_aligned16(grad) && tg_aligned16(m) && tg_aligned16(v) && tg_aligned16(avg);
-  if (vec)
-    hipLaunchKernelGGL(adam_ema_guarded_kernel<true>, dim3(tg_grid_for((numel + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream,
-                       theta, grad, m, v, avg, numel, lr_t_dev, beta1, beta2, eps, state, w_dev);
-  else
-    hipLaunchKernelGGL(adam_ema_guarded_kernel<false>, dim3(tg_grid_for(numel, 256)), dim3(256), 0, (hipStream_t)stream, theta,
-                       grad, m, v, avg, numel, lr_t_dev, beta1, beta2, eps, state, w_dev);
-  TG_LAUNCH_CHECK("tg_adam_ema_step_guarded");
-  return TG_OK;
+  return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, 0.f, state, avg, w_dev}, stream,
+                      "tg_adam_ema_step_guarded");
 }
 
 }  // extern "C"

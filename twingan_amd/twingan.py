@@ -572,73 +572,62 @@ class Trainer:
     return ops.uniform(n, self._rng_seed, self._rng_state)
 
   def _adam(self, group):
-    """tf.train.AdamOptimizer apply (model/model_inheritor.py:537-542) on the group's flat buffers, then
-    refresh the bf16 weight packs of the convs that just moved."""
-    c = self.cfg
-    s = self.store
+    """tf.train.AdamOptimizer apply (model/model_inheritor.py:537-542) on the group's flat buffers: tick, apply, the moving
+    averages, then refresh the bf16 weight packs of the convs that just moved.  All on the main stream, so a captured apply
+    graph holds (and replays) every decision made on the device.
+
+    Config.dynamic_loss_scale: check -> loss-scale tick -> guarded apply.  The check reads the group's WHOLE flat gradient
+    buffer after the clones' sum (reducer.finish() precedes _adam; inf + finite, inf - inf and NaN all stay non-finite
+    through a sum), so every clone decides the same.  The host neither learns nor asks whether the apply was made:
+    n_critic_counter, global_step and adam_t advance as ever.
+
+    --moving_average_decay: the apply fused with the moving average of the group's variables, then the averages of
+    everything the run did not apply: tf.train.ExponentialMovingAverage.apply is ONE op group over all model variables in
+    every session.run (model/model_inheritor.py:1063-1066,1090-1092), so a discriminator run also moves the generator's
+    averages towards the (unchanged) generator weights and vice versa.  The reference leaves the op unordered against the
+    Adam apply and the state updates; here it reads the post-run values: the launches follow the apply, after the run's
+    moving statistics / spectral-norm u / gdrop updates (all joined before the apply).  Data-parallel runs need no
+    communication: every clone applies the same all-reduced gradients to the same parameters, so the averages agree
+    wherever the parameters do.  A skipped guarded apply still moves the group's averages, towards its unchanged
+    parameters."""
+    c, s = self.cfg, self.store
     st = torch.cuda.current_stream().cuda_stream
     self.adam_t += 1
-    step_dev, lr_dev, lr = self._adam_step_dev, self._lr_t_dev, c.learning_rate
-    if self._ls is not None:
-      self._adam_guarded(group, st)
-      PackCache.refresh(self._group_weights[group])      # unconditional: after a skipped apply it repacks the same bits
-      return
-    call('tg_adam_tick', step_dev.data_ptr(), lr_dev.data_ptr(), lr, c.adam_beta1, c.adam_beta2, st)
-    if s.averaged:
-      self._adam_ema(group, st)
-    else:
-      call('tg_adam_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
-           s.v[group].data_ptr(), None, s.flat[group].numel(), 0.0, lr_dev.data_ptr(), c.adam_beta1,
-           c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale, st,
-           work=('adam:numel%d' % s.flat[group].numel(), 0, 28 * s.flat[group].numel()))
-    PackCache.refresh(self._group_weights[group])
-
-  def _adam_guarded(self, group, st):
-    """Config.dynamic_loss_scale: check -> tick -> guarded apply on the main stream, so a captured apply graph replays the
-    decision.  The check reads the group's WHOLE flat gradient buffer after the clones' sum (reducer.finish() precedes
-    _adam; inf + finite, inf - inf and NaN all stay non-finite through a sum), so every clone decides the same.  The host
-    neither learns nor asks whether the apply was made: n_critic_counter, global_step and adam_t advance as ever."""
-    c, s, ls = self.cfg, self.store, self._ls[group].data_ptr()
+    step, lr_t = self._adam_step_dev.data_ptr(), self._lr_t_dev.data_ptr()
+    th, g, m, v = (t[group].data_ptr() for t in (s.flat, s.grad, s.m, s.v))
     n = s.flat[group].numel()
-    call('tg_nonfinite_check', s.grad[group].data_ptr(), n, ls, st, work=('nonfinite:numel%d' % n, 0, 4 * n))
-    call('tg_loss_scale_tick', ls, self._adam_step_dev.data_ptr(), self._lr_t_dev.data_ptr(), c.learning_rate, c.adam_beta1,
-         c.adam_beta2, int(c.loss_scale_growth_interval), self._ls_max, self.world, st)
-    if s.averaged:
-      self._adam_ema(group, st, ls)
+    hyper = (c.adam_beta1, c.adam_beta2, c.opt_epsilon)
+    ls = self._ls[group].data_ptr() if self._ls is not None else None
+    avg = s.avg[group].data_ptr() if s.averaged else None
+    w = self._ema_w_dev.data_ptr() if s.averaged else None
+    if ls is not None:
+      call('tg_nonfinite_check', g, n, ls, st, work=('nonfinite:numel%d' % n, 0, 4 * n))
+      call('tg_loss_scale_tick', ls, step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2,
+           int(c.loss_scale_growth_interval), self._ls_max, self.world, st)
     else:
-      call('tg_adam_step_guarded', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
-           s.v[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2, c.opt_epsilon, ls, st,
-           work=('adam_guarded:numel%d' % n, 0, 28 * n))
+      call('tg_adam_tick', step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2, st)
+    if s.averaged and ls is not None:
+      call('tg_adam_ema_step_guarded', th, g, m, v, avg, n, lr_t, *hyper, ls, w, st,
+           work=('adam_ema_guarded:numel%d' % n, 0, 36 * n))
+    elif s.averaged:
+      call('tg_adam_ema_step', th, g, m, v, avg, n, lr_t, *hyper, 1.0 / c.loss_scale, w, st,
+           work=('adam_ema:numel%d' % n, 0, 36 * n))
+    elif ls is not None:
+      call('tg_adam_step_guarded', th, g, m, v, n, lr_t, *hyper, ls, st, work=('adam_guarded:numel%d' % n, 0, 28 * n))
+    else:
+      call('tg_adam_step', th, g, m, v, None, n, 0.0, lr_t, *hyper, 1.0 / c.loss_scale, st,
+           work=('adam:numel%d' % n, 0, 28 * n))
+    if s.averaged:
+      for other in s.GROUPS:
+        if other != group:
+          k = s.flat[other].numel()
+          call('tg_ema_update', s.avg[other].data_ptr(), s.flat[other].data_ptr(), k, w, st, work=('ema:numel%d' % k, 0, 12 * k))
+      if self._ema_table is not None:
+        tab = self._ema_table
+        call('tg_ema_update_multi', tab[0].data_ptr(), tab[1], tab[2], w, st, work=('ema_multi:%d' % tab[1], 0, tab[3]))
+    PackCache.refresh(self._group_weights[group])      # also after a skipped apply: it repacks the same bits
 
   # ---- moving averages (--moving_average_decay) ---------------------------------------------------------------
-  def _adam_ema(self, group, st, ls=None):
-    """The apply of ``group`` fused with the moving average of its variables, then the averages of everything the run did
-    not apply: tf.train.ExponentialMovingAverage.apply is ONE op group over all model variables in every session.run
-    (model/model_inheritor.py:1063-1066,1090-1092), so a discriminator run also moves the generator's averages towards the
-    (unchanged) generator weights and vice versa.  The reference leaves the op unordered against the Adam apply and the
-    state updates; here it reads the post-run values: the three launches follow the apply on the main stream, after the
-    run's moving statistics / spectral-norm u / gdrop updates (all joined before the apply) -- under graph capture they are
-    part of the captured apply graph.  Data-parallel runs need no communication: every clone applies the same all-reduced
-    gradients to the same parameters, so the averages agree wherever the parameters do.  ``ls`` (dynamic loss scaling): the
-    guarded apply -- a skipped one still moves the group's averages, towards its unchanged parameters."""
-    c, s, w = self.cfg, self.store, self._ema_w_dev.data_ptr()
-    n = s.flat[group].numel()
-    if ls is not None:
-      call('tg_adam_ema_step_guarded', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(),
-           s.v[group].data_ptr(), s.avg[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2,
-           c.opt_epsilon, ls, w, st, work=('adam_ema_guarded:numel%d' % n, 0, 36 * n))
-    else:
-        call('tg_adam_ema_step', s.flat[group].data_ptr(), s.grad[group].data_ptr(), s.m[group].data_ptr(), s.v[group].data_ptr(),
-           s.avg[group].data_ptr(), n, self._lr_t_dev.data_ptr(), c.adam_beta1, c.adam_beta2, c.opt_epsilon, 1.0 / c.loss_scale,
-           w, st, work=('adam_ema:numel%d' % n, 0, 36 * n))
-    for other in s.GROUPS:
-      if other != group:
-        n = s.flat[other].numel()
-        call('tg_ema_update', s.avg[other].data_ptr(), s.flat[other].data_ptr(), n, w, st, work=('ema:numel%d' % n, 0, 12 * n))
-    if self._ema_table is not None:
-      tab = self._ema_table
-      call('tg_ema_update_multi', tab[0].data_ptr(), tab[1], tab[2], w, st, work=('ema_multi:%d' % tab[1], 0, tab[3]))
-
   def _build_ema_table(self):
     """Device job table of tg_ema_update_multi over the state variables' (average, variable) pairs: built once, the
     buffers keep their addresses for the trainer's life."""
