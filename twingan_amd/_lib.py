@@ -1,4 +1,4 @@
-"""ctypes binding of libtwingan_hip.so (include/twingan_hip.h).
+"""ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a kernel call returns
 an error, this module raises.  (``oracle/`` is test infrastructure and is never imported here.)
@@ -32,6 +32,16 @@ class TgLossScaleState(Structure):
   _fields_ = [('scale', c_float), ('seed', c_float), ('inv_scale', c_float), ('found', c_int32), ('skip', c_int32),
               ('good_steps', c_int32), ('skipped', c_int64)]
 
+
+class TgOptimHyper(Structure):
+  """The by-value hyper-parameters of tg_optim_step (include/twingan_hip_optim.h TgOptimHyper)."""
+  _fields_ = [(k, c_float) for k in ('lr', 'momentum', 'decay_or_rho', 'eps', 'lr_power', 'l1', 'l2')]
+
+
+# include/twingan_hip_optim.h TG_OPT_*: the --optimizer rules besides Adam, which keeps its own entry points
+TG_OPT_SGD, TG_OPT_MOMENTUM, TG_OPT_ADAGRAD, TG_OPT_RMSPROP, TG_OPT_ADADELTA, TG_OPT_FTRL = range(6)
+OPTIM_RULES = {'sgd': TG_OPT_SGD, 'momentum': TG_OPT_MOMENTUM, 'adagrad': TG_OPT_ADAGRAD, 'rmsprop': TG_OPT_RMSPROP,
+               'adadelta': TG_OPT_ADADELTA, 'ftrl': TG_OPT_FTRL}
 
 _P = c_void_p
 _FP = c_void_p      # float* passed as raw address
@@ -192,6 +202,12 @@ SIGNATURES = {
     'tg_sn_assign_u': (c_int, [_P, c_int, _P]),
 }
 
+# include/twingan_hip_optim.h, one to one as above.
+OPTIM_SIGNATURES = {
+    'tg_optim_slot_count': (c_int, [c_int]),
+    'tg_optim_step': (c_int, [c_int, _FP, _FP, _FP, _FP, _FP, c_int64, POINTER(TgOptimHyper), c_float, _P, _FP, _P]),
+}
+
 _lib = None
 
 
@@ -204,7 +220,7 @@ def load():
     raise TgError('%s not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                   '(make -C twingan_amd/csrc). There is no CPU fallback.' % LIB_PATH)
   lib = ctypes.CDLL(LIB_PATH)
-  for name, (res, args) in SIGNATURES.items():
+  for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
     fn = getattr(lib, name)       # AttributeError if a declared symbol is missing
     fn.restype = res
     fn.argtypes = args

@@ -475,13 +475,19 @@ def save(trainer, train_dir, global_step=None, max_to_keep=5):
   (the ``max_to_keep`` most recent ones are retained).  Under --moving_average_decay (Config.moving_average_decay) also the
   shadow ``<var>/ExponentialMovingAverage`` of every model variable; without it the key set is unchanged.  Under
   Config.dynamic_loss_scale also each group's loss-scale state and the applies made (LOSS_SCALE_PREFIX, ADAM_APPLIES_KEY;
-  reading them waits for the device once); without it the key set is unchanged."""
+  reading them waits for the device once); without it the key set is unchanged.  Under Config.optimizer other than 'adam'
+  the slots are that rule's (``<var>/Momentum``; ``<var>/Adagrad``; ``<var>/RMSProp``, ``<var>/RMSProp_1``; ``<var>/Adadelta``,
+  ``<var>/Adadelta_1``; ``<var>/Ftrl``, ``<var>/Ftrl_1``; none for sgd) and no beta power is written, as TF's Saver would."""
   store = trainer.store
   step = int(trainer.global_step if global_step is None else global_step)
   tensors = {k: v.detach().float().cpu().numpy() for k, v in store.state_dict(include_state=True).items()}
-  for k, (m, v) in store.adam_dict().items():
-    tensors[k + '/Adam'] = m.detach().float().cpu().numpy()
-    tensors[k + '/Adam_1'] = v.detach().float().cpu().numpy()
+  adam = store.optimizer == 'adam'
+  if adam:
+    for k, (m, v) in store.adam_dict().items():
+      tensors[k + '/Adam'] = m.detach().float().cpu().numpy()
+      tensors[k + '/Adam_1'] = v.detach().float().cpu().numpy()
+  else:      # --optimizer: the rule's own slot names (params.OPTIM_SLOTS), no beta powers
+    tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.slot_dict().items()})
   if store.averaged:
     tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.averages_dict().items()})
   t = int(trainer.adam_t)
@@ -493,8 +499,9 @@ def save(trainer, train_dir, global_step=None, max_to_keep=5):
       tensors[LOSS_SCALE_PREFIX + g + '/scale'] = np.float32(st['scale'])
       tensors[LOSS_SCALE_PREFIX + g + '/good_steps'] = np.int32(st['good_steps'])
       tensors[LOSS_SCALE_PREFIX + g + '/skipped'] = np.int64(st['skipped'])
-  tensors['beta1_power'] = np.float32(trainer.cfg.adam_beta1 ** (t + 1))       # TF keeps beta^(t+1) after t applies
-  tensors['beta2_power'] = np.float32(trainer.cfg.adam_beta2 ** (t + 1))
+  if adam:
+    tensors['beta1_power'] = np.float32(trainer.cfg.adam_beta1 ** (t + 1))       # TF keeps beta^(t+1) after t applies
+    tensors['beta2_power'] = np.float32(trainer.cfg.adam_beta2 ** (t + 1))
   tensors['global_step'] = np.int64(step)
   # image_generation.py:622-623: a global (hence saved) int32 variable; every session.run adds 1 to it and applies the
   # shared Adam once, so it is also the number of Adam applies -- which the beta powers stop encoding once they
@@ -537,7 +544,8 @@ def init_from_checkpoint(trainer, checkpoint_path, checkpoint_exclude_scopes=Non
   Variables are restored by their own names only: the moving averages of Config.moving_average_decay are not touched and
   stay at this stage's initial values, as in the reference, whose shadows are no model variables.  The stage's global_step
   starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs.  The loss-scale states of
-  Config.dynamic_loss_scale are not touched either: a new stage starts from the initial scale."""
+  Config.dynamic_loss_scale are not touched either: a new stage starts from the initial scale.  Model variables only: the
+  file's optimiser slots are never read, so a stage may warm-start across optimisers (an rmsprop stage from an Adam one)."""
   if checkpoint_path is None:
     return []
   if train_dir is not None and latest_checkpoint(train_dir):
@@ -574,7 +582,8 @@ def restore(trainer, prefix):
   moving averages (Config.moving_average_decay) also loads ``<var>/ExponentialMovingAverage`` of every model variable and
   raises KeyError naming the first one the file lacks, as a TF Saver would; one that keeps none ignores such keys.  A
   trainer with Config.dynamic_loss_scale takes each group's loss-scale state from the file, or Config.loss_scale and zero
-  counts where the file has none."""
+  counts where the file has none.  The slots are those of the trainer's Config.optimizer; a file whose slots belong to
+  another optimiser raises ValueError naming both (TF's Saver fails there too)."""
   import math
   import torch
   store = trainer.store
@@ -591,8 +600,13 @@ def restore(trainer, prefix):
   store.load_state_dict({k: torch.from_numpy(arrays[k].astype(np.float32)) for k in names}, strict=False)
   if store.averaged:
     store.load_averages_dict({k: torch.from_numpy(arrays[k].astype(np.float32)) for k in shadows})
-  slots = {k: (arrays[k + '/Adam'], arrays[k + '/Adam_1']) for k in store.specs if k + '/Adam' in arrays}
-  store.load_adam_dict(slots)
+  _check_optimizer(prefix, arrays, store)
+  if store.optimizer == 'adam':
+    slots = {k: (arrays[k + '/Adam'], arrays[k + '/Adam_1']) for k in store.specs if k + '/Adam' in arrays}
+    store.load_adam_dict(slots)
+  else:
+    from .params import OPTIM_SLOTS
+    store.load_slot_dict({k + '/' + slot: arrays[k + '/' + slot] for k in store.specs for slot, _ in OPTIM_SLOTS[store.optimizer]})
   if 'global_step' in arrays:
     trainer.global_step = int(arrays['global_step'])
     trainer.n_critic_counter = trainer.global_step * trainer.cfg.n_critic
@@ -612,6 +626,21 @@ def restore(trainer, prefix):
   if RNG_DRAWS_KEY in arrays and getattr(trainer, '_rng_state', None) is not None:
     trainer._rng_state[0] = int(arrays[RNG_DRAWS_KEY])      # continue the device generator's sequence (see save)
   return trainer.global_step
+
+
+def _check_optimizer(prefix, arrays, store):
+  """A Saver restore needs every slot variable of the trainer's optimiser in the file and fails where one is missing: raises
+  ValueError naming the optimiser whose slots the file holds and the trainer's.  A file without any slot (sgd's, or one of
+  model variables only) restores into an sgd trainer, and into an Adam trainer as before."""
+  from .params import OPTIM_SLOTS
+  first = next(iter(store.specs))
+  found = [o for o, slots in OPTIM_SLOTS.items() if slots and all(first + '/' + slot in arrays for slot, _ in slots)]
+  # rmsprop / adadelta / ftrl / adam files also match no one-slot rule: the names differ per optimiser
+  have = found[0] if found else 'sgd'
+  want = store.optimizer
+  if have != want and not (want == 'adam' and not found):
+    raise ValueError('checkpoint %s holds the slots of optimizer=%s, this trainer has optimizer=%s: resume with the optimiser '
+                     'that wrote it, or warm-start the model variables alone (init_from_checkpoint)' % (prefix, have, want))
 
 
 def _adam_applies(arrays, cfg, counter):

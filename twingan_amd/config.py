@@ -70,8 +70,35 @@ class Config:
   # [1, 2**24] (every unscale is exact).  Only 'fp16' grows the scale; the other precisions keep theirs and gain the guard.
   dynamic_loss_scale: bool = False
   loss_scale_growth_interval: int = 2000
+  # --optimizer (model/model_inheritor.py:122-165, 516-565): adadelta | adagrad | adam | ftrl | momentum | rmsprop | sgd, each
+  # with the reference's defaults; learning_rate and opt_epsilon are shared.  DESIGN.md section 4
+  optimizer: str = 'adam'
+  adadelta_rho: float = 0.95
+  adagrad_initial_accumulator_value: float = 0.1
+  ftrl_learning_rate_power: float = -0.5
+  ftrl_initial_accumulator_value: float = 0.1
+  ftrl_l1: float = 0.0
+  ftrl_l2: float = 0.0
+  momentum: float = 0.9
+  rmsprop_momentum: float = 0.9
+  rmsprop_decay: float = 0.9
+
+  OPTIMIZERS = ('adadelta', 'adagrad', 'adam', 'ftrl', 'momentum', 'rmsprop', 'sgd')
 
   def __post_init__(self):
+    if self.optimizer not in self.OPTIMIZERS:
+      raise ValueError('optimizer must be one of %s (got %r)' % (' | '.join(self.OPTIMIZERS), self.optimizer))
+    if not float(self.ftrl_learning_rate_power) <= 0.0:
+      raise ValueError('ftrl_learning_rate_power must not be positive (got %r)' % (self.ftrl_learning_rate_power,))
+    for name in ('ftrl_l1', 'ftrl_l2'):
+      if not float(getattr(self, name)) >= 0.0:
+        raise ValueError('%s must not be negative (got %r)' % (name, getattr(self, name)))
+    for name in ('adagrad_initial_accumulator_value', 'ftrl_initial_accumulator_value'):
+      if not float(getattr(self, name)) > 0.0:
+        raise ValueError('%s must be positive (got %r)' % (name, getattr(self, name)))
+    for name in ('adadelta_rho', 'rmsprop_decay', 'momentum', 'rmsprop_momentum'):
+      if not 0.0 <= float(getattr(self, name)) < 1.0:
+        raise ValueError('%s must lie in [0, 1) (got %r)' % (name, getattr(self, name)))
     d = self.moving_average_decay
     if d is not None and not (0.0 < float(d) < 1.0):
       raise ValueError('moving_average_decay must lie in (0, 1) or be None (got %r)' % (d,))

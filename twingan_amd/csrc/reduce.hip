@@ -1,6 +1,7 @@
 // Minibatch-stddev (forward, backward, double backward), loss reductions, WGAN-GP tail, the small
-// dense layer and the fused Adam step.
+// dense layer, the fused Adam step and the other --optimizer rules' apply.
 #include "tg_common.h"
+#include "../../include/twingan_hip_optim.h"
 
 namespace {
 
@@ -856,6 +857,143 @@ __global__ __launch_bounds__(256) void apply_kernel(const ApplyArgs a) {
   }
 }
 
+// ---- the reference's other --optimizer rules (include/twingan_hip_optim.h; TF 1.8 core/kernels/training_ops.cc, the dense
+// functors).  One element each, in adam_element's style: g arrives unscaled-by-the-loss (g * gscale), every multiply that
+// feeds an add is an explicit fmaf, so the 16-byte loop and the tail loop of optim_kernel write the same bits, and so do the
+// fused and the unfused form; contraction is off inside them, so that the caller's g * gscale is not pulled into one of
+// their plain adds in one instantiation and left alone in another.  a, b: the rule's slots in slot0, slot1 order; a rule
+// touches only those it has.
+__device__ __forceinline__ float sgd_element(float th, float g, const TgOptimHyper& h) { return fmaf(-h.lr, g, th); }
+
+// ApplyMomentum, use_nesterov = false: accum = accum * momentum + grad; var -= lr * accum
+__device__ __forceinline__ float momentum_element(float th, float g, float& a, const TgOptimHyper& h) {
+#pragma clang fp contract(off)
+  a = fmaf(h.momentum, a, g);
+  return fmaf(-h.lr, a, th);
+}
+
+// ApplyAdagrad (TF 1.8: no epsilon): accum += grad^2; var -= lr * grad / sqrt(accum)
+__device__ __forceinline__ float adagrad_element(float th, float g, float& a, const TgOptimHyper& h) {
+#pragma clang fp contract(off)
+  a = fmaf(g, g, a);
+  return th - h.lr * g / sqrtf(a);
+}
+
+// ApplyRMSProp (not centred; epsilon inside the root): ms += (grad^2 - ms) * (1 - rho); mom = mom * momentum + lr * grad /
+// sqrt(ms + eps); var -= mom
+__device__ __forceinline__ float rmsprop_element(float th, float g, float& ms, float& mom, const TgOptimHyper& h) {
+#pragma clang fp contract(off)
+  ms = fmaf(fmaf(g, g, -ms), 1.f - h.decay_or_rho, ms);
+  mom = fmaf(h.momentum, mom, h.lr * g / sqrtf(ms + h.eps));
+  return th - mom;
+}
+
+// ApplyAdadelta: accum = rho accum + (1 - rho) grad^2; update = sqrt(accum_update + eps) / sqrt(accum + eps) * grad;
+// var -= lr * update; accum_update = rho accum_update + (1 - rho) update^2
+__device__ __forceinline__ float adadelta_element(float th, float g, float& accum, float& upd, const TgOptimHyper& h) {
+#pragma clang fp contract(off)
+  const float rho = h.decay_or_rho, omr = 1.f - rho;
+  accum = fmaf(rho, accum, omr * g * g);
+  const float u = sqrtf(upd + h.eps) / sqrtf(accum + h.eps) * g;
+  upd = fmaf(rho, upd, omr * u * u);
+  return fmaf(-h.lr, u, th);
+}
+
+// ApplyFtrl (no l2 shrinkage).  x^(-lr_power): the square root at the default -0.5, powf otherwise (lr_power <= 0; 0 gives 1).
+// |linear| <= l1 -- linear == 0 with l1 == 0 included -- writes 0: TF's rule.
+template <bool SQRT>
+__device__ __forceinline__ float ftrl_element(float th, float g, float& accum, float& linear, const TgOptimHyper& h) {
+#pragma clang fp contract(off)
+  const float n = fmaf(g, g, accum);
+  const float pn = SQRT ? sqrtf(n) : powf(n, -h.lr_power), pa = SQRT ? sqrtf(accum) : powf(accum, -h.lr_power);
+  const float sigma = (pn - pa) / h.lr;
+  const float lin = fmaf(-sigma, th, linear + g);
+  const float q = fmaf(2.f, h.l2, pn / h.lr);
+  accum = n;
+  linear = lin;
+  return fabsf(lin) > h.l1 ? (copysignf(h.l1, lin) - lin) / q : 0.f;
+}
+
+constexpr int TG_OPT_FTRL_POW = TG_OPT_FTRL + 1;      // kernel-side only: ftrl with lr_power != -0.5
+constexpr int optim_slots(int rule) {
+  return rule == TG_OPT_SGD ? 0 : (rule == TG_OPT_MOMENTUM || rule == TG_OPT_ADAGRAD) ? 1 : 2;
+}
+
+template <int RULE>
+__device__ __forceinline__ float optim_element(float th, float g, float& a, float& b, const TgOptimHyper& h) {
+  if constexpr (RULE == TG_OPT_SGD) return sgd_element(th, g, h);
+  else if constexpr (RULE == TG_OPT_MOMENTUM) return momentum_element(th, g, a, h);
+  else if constexpr (RULE == TG_OPT_ADAGRAD) return adagrad_element(th, g, a, h);
+  else if constexpr (RULE == TG_OPT_RMSPROP) return rmsprop_element(th, g, a, b, h);
+  else if constexpr (RULE == TG_OPT_ADADELTA) return adadelta_element(th, g, a, b, h);
+  else return ftrl_element<RULE == TG_OPT_FTRL>(th, g, a, b, h);
+}
+
+// What tg_optim_step hands to optim_kernel.
+struct OptimArgs {
+  float* th;
+  const float* g;
+  float *s0, *s1;                 // null where the rule has no such slot: never dereferenced then
+  int64_t numel;
+  TgOptimHyper h;
+  float gscale;                   // multiplies g first, without ls
+  const TgLossScaleState* ls;     // the guard: the gradient scale is its inv_scale, its skip decides
+  float* avg;                     // the fused moving average (EMA instantiations)
+  const float* w_dev;
+};
+
+// apply_kernel's sibling for the other rules: 12 (sgd), 20 (momentum, adagrad) or 28 bytes per element, 8 more with the moving
+// average.  VEC, EMA and ls as there, but every form has its 16-byte loop (there is no bf16 shadow here).
+template <int RULE, bool VEC, bool EMA>
+__global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
+  constexpr int NS = optim_slots(RULE);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  if (a.ls && a.ls->skip) {
+    if constexpr (EMA) ema_span<VEC>(a.avg, a.th, a.numel, a.w_dev[0], tid, nthr);
+    return;
+  }
+  const float gscale = a.ls ? a.ls->inv_scale : a.gscale;
+  const TgOptimHyper h = a.h;
+  float w = 0.f;
+  if constexpr (EMA) w = a.w_dev[0];
+  int64_t done = 0;
+  if constexpr (VEC) {
+    const int64_t nvec = a.numel >> 2;
+    for (int64_t i = tid; i < nvec; i += nthr) {
+      Vec16<float> t4 = ldv(a.th + 4 * i), p4 = {}, q4 = {}, a4 = {};
+      const Vec16<float> g4 = ldv(a.g + 4 * i);
+      if constexpr (NS >= 1) p4 = ldv(a.s0 + 4 * i);
+      if constexpr (NS >= 2) q4 = ldv(a.s1 + 4 * i);
+      if constexpr (EMA) a4 = ldv(a.avg + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pi = p4.v[e], qi = q4.v[e];
+        const float t = optim_element<RULE>(t4.v[e], g4.v[e] * gscale, pi, qi, h);
+        p4.v[e] = pi;
+        q4.v[e] = qi;
+        t4.v[e] = t;
+        if constexpr (EMA) a4.v[e] = ema_element(a4.v[e], t, w);
+      }
+      if constexpr (NS >= 1) stv(a.s0 + 4 * i, p4);
+      if constexpr (NS >= 2) stv(a.s1 + 4 * i, q4);
+      stv(a.th + 4 * i, t4);
+      if constexpr (EMA) stv(a.avg + 4 * i, a4);
+    }
+    done = nvec << 2;
+  }
+  for (int64_t i = done + tid; i < a.numel; i += nthr) {
+    float pi = 0.f, qi = 0.f, ai = 0.f;
+    if constexpr (NS >= 1) pi = a.s0[i];
+    if constexpr (NS >= 2) qi = a.s1[i];
+    if constexpr (EMA) ai = a.avg[i];      // with the other loads, as in apply_kernel
+    const float t = optim_element<RULE>(a.th[i], a.g[i] * gscale, pi, qi, h);
+    if constexpr (NS >= 1) a.s0[i] = pi;
+    if constexpr (NS >= 2) a.s1[i] = qi;
+    a.th[i] = t;
+    if constexpr (EMA) a.avg[i] = ema_element(ai, t, w);
+  }
+}
+
 // ---- the moving averages of MANY small tensors in one launch (the non-trainable state: a few hundred separately allocated
 // tensors of 1 to a few hundred elements).  A host-built job table as for pack_weights_multi (conv_mfma.hip).
 struct EmaJob {
@@ -973,6 +1111,21 @@ int launch_apply(const ApplyArgs& a, void* stream, const char* name) {
   auto kernel = vec ? apply_kernel<true, true> : ema ? apply_kernel<false, true> : apply_kernel<false, false>;
   hipLaunchKernelGGL(kernel, dim3(tg_grid_for(vec ? (a.numel + 3) / 4 : a.numel, 256)), dim3(256), 0, (hipStream_t)stream, a);
   TG_LAUNCH_CHECK(name);
+  return TG_OK;
+}
+
+// The one launch of optim_kernel, under launch_apply's workgroup cap.  The 16-byte loop is taken when every pointer in use
+// (theta, grad, the rule's slots, the average when there is one) is 16-byte aligned.
+template <int RULE>
+int launch_optim_rule(const OptimArgs& a, void* stream) {
+  constexpr int NS = optim_slots(RULE);
+  const bool ema = a.avg != nullptr;
+  const bool vec = tg_aligned16(a.th) && tg_aligned16(a.g) && (NS < 1 || tg_aligned16(a.s0)) && (NS < 2 || tg_aligned16(a.s1)) &&
+                   (!ema || tg_aligned16(a.avg));
+  auto kernel = vec ? (ema ? optim_kernel<RULE, true, true> : optim_kernel<RULE, true, false>)
+                    : (ema ? optim_kernel<RULE, false, true> : optim_kernel<RULE, false, false>);
+  hipLaunchKernelGGL(kernel, dim3(tg_grid_for(vec ? (a.numel + 3) / 4 : a.numel, 256)), dim3(256), 0, (hipStream_t)stream, a);
+  TG_LAUNCH_CHECK("tg_optim_step");
   return TG_OK;
 }
 
@@ -1349,6 +1502,34 @@ int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step_guarded: numel must be positive (got %lld)", (long long)numel);
   return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, 0.f, state, avg, w_dev}, stream,
                       "tg_adam_ema_step_guarded");
+}
+
+int tg_optim_slot_count(int rule) { return rule >= TG_OPT_SGD && rule <= TG_OPT_FTRL ? optim_slots(rule) : -1; }
+
+int tg_optim_step(int rule, float* theta, const float* grad, float* slot0, float* slot1, float* avg, int64_t numel,
+                  const TgOptimHyper* hyper, float grad_scale, const TgLossScaleState* guard, const float* w_dev, void* stream) {
+  const int ns = tg_optim_slot_count(rule);
+  TG_CHECK(ns >= 0, TG_EINVAL, "tg_optim_step: unknown rule %d", rule);
+  TG_CHECK(theta, TG_EINVAL, "tg_optim_step: theta is null");
+  TG_CHECK(grad, TG_EINVAL, "tg_optim_step: grad is null");
+  TG_CHECK(hyper, TG_EINVAL, "tg_optim_step: hyper is null");
+  TG_CHECK(numel > 0, TG_EINVAL, "tg_optim_step: numel must be positive (got %lld)", (long long)numel);
+  TG_CHECK(ns < 1 || slot0, TG_EINVAL, "tg_optim_step: slot0 is null and rule %d needs it", rule);
+  TG_CHECK(ns < 2 || slot1, TG_EINVAL, "tg_optim_step: slot1 is null and rule %d needs it", rule);
+  TG_CHECK(!avg || w_dev, TG_EINVAL, "tg_optim_step: avg without w_dev");
+  TG_CHECK(avg || !w_dev, TG_EINVAL, "tg_optim_step: w_dev without avg");
+  if (rule == TG_OPT_FTRL)
+    TG_CHECK(hyper->lr_power <= 0.f, TG_EINVAL, "tg_optim_step: hyper->lr_power must not be positive (got %g)",
+             (double)hyper->lr_power);
+  const OptimArgs a{theta, grad, ns >= 1 ? slot0 : nullptr, ns >= 2 ? slot1 : nullptr, numel, *hyper, grad_scale, guard, avg, w_dev};
+  switch (rule) {
+    case TG_OPT_SGD: return launch_optim_rule<TG_OPT_SGD>(a, stream);
+    case TG_OPT_MOMENTUM: return launch_optim_rule<TG_OPT_MOMENTUM>(a, stream);
+    case TG_OPT_ADAGRAD: return launch_optim_rule<TG_OPT_ADAGRAD>(a, stream);
+    case TG_OPT_RMSPROP: return launch_optim_rule<TG_OPT_RMSPROP>(a, stream);
+    case TG_OPT_ADADELTA: return launch_optim_rule<TG_OPT_ADADELTA>(a, stream);
+    default: return hyper->lr_power == -0.5f ? launch_optim_rule<TG_OPT_FTRL>(a, stream) : launch_optim_rule<TG_OPT_FTRL_POW>(a, stream);
+  }
 }
 
 }  // extern "C"

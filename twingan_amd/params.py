@@ -6,7 +6,9 @@ model/model_inheritor.py:537-542, deployment/model_deploy.py:473-503).
 Variables are addressed by the reference's TF names and keep TF layouts
 (conv HWIO, fc [in, out]) so reference checkpoints map 1:1.  A variable may have a *physical*
 shape larger than its logical one (the D tail conv sees the minibatch-stddev tensor padded to a
-multiple of 8 channels); the padding rows are zero and stay zero under Adam.
+multiple of 8 channels); the padding rows are zero and stay zero under Adam -- and under every other rule of
+Config.optimizer (their gradient is 0: sgd, momentum, adagrad, rmsprop and adadelta then keep theta bit for bit, ftrl
+writes 0), whose slots live in ``slots[group]`` instead of ``m`` / ``v``.
 """
 import math
 from collections import OrderedDict
@@ -66,6 +68,18 @@ class ParamStore:
     self.averaged = False
     self.avg = {}
     self.state_avg = {}
+    # --optimizer (Config.optimizer): set before build() by the trainer (set_optimizer).  'adam' keeps m / v; any other rule has
+    # slots[g] = its flat slot buffers in slot0, slot1 order (OPTIM_SLOTS), laid out like flat[g], and empty m / v
+    self.optimizer = 'adam'
+    self.slot_init = ()
+    self.slots = {}
+
+  def set_optimizer(self, cfg):
+    """Chooses the optimiser whose slots build() allocates: the initial value of each slot is the table's number or the
+    Config field it names."""
+    self.optimizer = cfg.optimizer
+    self.slot_init = tuple(float(getattr(cfg, v) if isinstance(v, str) else v) for _, v in OPTIM_SLOTS[cfg.optimizer])
+    return self
 
   # ---- declaration ----------------------------------------------------------------------------
   def add(self, name, shape, group, kind, phys=None):
@@ -141,8 +155,10 @@ class ParamStore:
       n = max(sizes[g], ALIGN)
       self.flat[g] = torch.zeros(n, dtype=torch.float32, device=self.device)
       self.grad[g] = torch.zeros(n, dtype=torch.float32, device=self.device)
-      self.m[g] = torch.zeros(n, dtype=torch.float32, device=self.device)
-      self.v[g] = torch.zeros(n, dtype=torch.float32, device=self.device)
+      self.m[g] = torch.zeros(n if self.optimizer == 'adam' else 0, dtype=torch.float32, device=self.device)
+      self.v[g] = torch.zeros(n if self.optimizer == 'adam' else 0, dtype=torch.float32, device=self.device)
+      if self.optimizer != 'adam':
+        self.slots[g] = [torch.full((n,), v, dtype=torch.float32, device=self.device) for v in self.slot_init]
     gen = torch.Generator().manual_seed(seed)
     for name, s in self.specs.items():
       g, off, n = s['group'], self.offsets[name], int(math.prod(s['phys']))
@@ -233,6 +249,7 @@ class ParamStore:
   def adam_dict(self):
     """{variable name: (m, v)} -- logical views of the shared Adam optimiser's slot variables (TF: <var>/Adam,
     <var>/Adam_1)."""
+    assert self.optimizer == 'adam', 'this store keeps the slots of %s: slot_dict()' % self.optimizer
     out = {}
     for k, s in self.specs.items():
       g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
@@ -248,6 +265,29 @@ class ParamStore:
         g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
         for dst, src in ((self.m[g], m), (self.v[g], v)):
           self._logical(dst[off:off + n].view(s['phys']), s).copy_(torch.as_tensor(src, dtype=torch.float32).reshape(s['shape']))
+
+  def slot_dict(self):
+    """{'<var>/<slot>': logical (TF-shaped) copy} of the slots of a store whose optimiser is not Adam, under the names TF's
+    Saver writes (OPTIM_SLOTS: '<var>/RMSProp', '<var>/RMSProp_1', ...); {} for sgd."""
+    assert self.optimizer != 'adam', 'the Adam slots: adam_dict()'
+    out = {}
+    for k, s in self.specs.items():
+      g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
+      for (slot, _), buf in zip(OPTIM_SLOTS[self.optimizer], self.slots[g]):
+        out[k + '/' + slot] = self._logical(buf[off:off + n].view(s['phys']), s).clone()
+    return out
+
+  def load_slot_dict(self, slots):
+    """Inverse of slot_dict for the keys given."""
+    assert self.optimizer != 'adam', 'the Adam slots: load_adam_dict()'
+    index = {slot: i for i, (slot, _) in enumerate(OPTIM_SLOTS[self.optimizer])}
+    with torch.no_grad():
+      for key, src in slots.items():
+        k, slot = key.rsplit('/', 1)
+        s = self.specs[k]
+        g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
+        dst = self.slots[g][index[slot]][off:off + n].view(s['phys'])
+        self._logical(dst, s).copy_(torch.as_tensor(src, dtype=torch.float32).reshape(s['shape']))
 
   # ---- moving averages (tf.train.ExponentialMovingAverage shadows; model/model_inheritor.py:1063-1092,1150-1155) -------------
   def _avg_view(self, k):
@@ -330,10 +370,24 @@ class ParamStore:
     for buf in self.P.__dict__.pop('sn_wbar', {}).values():      # persistent spectrally-normalised kernels (pggan._sn_compute)
       PackCache.unregister(buf)
     self.avg, self.state_avg = {}, {}
+    self.slots = {}
 
   def numel(self, group):
     return sum(int(math.prod(s['shape'])) for s in self.specs.values() if s['group'] == group)
 
+
+# --optimizer -> its slot variables in slot0, slot1 order (tg_optim_step): (the name TF's Saver appends to the variable's, the
+# initial value or the Config field that holds it).  TF 1.8 python/training/{momentum,adagrad,rmsprop,adadelta,ftrl,adam}.py
+# _create_slots; RMSProp's mean square starts at ONE.
+OPTIM_SLOTS = {
+    'sgd': (),
+    'momentum': (('Momentum', 0.0),),
+    'adagrad': (('Adagrad', 'adagrad_initial_accumulator_value'),),
+    'rmsprop': (('RMSProp', 1.0), ('RMSProp_1', 0.0)),
+    'adadelta': (('Adadelta', 0.0), ('Adadelta_1', 0.0)),
+    'ftrl': (('Ftrl', 'ftrl_initial_accumulator_value'), ('Ftrl_1', 0.0)),
+    'adam': (('Adam', 0.0), ('Adam_1', 0.0)),
+}
 
 EMA_SUFFIX = '/ExponentialMovingAverage'      # tf.train.ExponentialMovingAverage.average_name(var): '<var.op.name>/' + its name
 

@@ -43,7 +43,8 @@ def warm_start(trainer, previous_state):
   ignore_missing_vars (model/model_inheritor.py:576-644).  Returns the names that were loaded.
   Under Config.moving_average_decay the moving averages are NOT warm-started: the reference's _get_init_fn restores model
   variables by their own names only, so the averages stay at this stage's fresh initial values.  The stage's global_step
-  starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs."""
+  starts at 0, so the ramp min(decay, (1 + n) / (10 + n)) forgets that start within tens of runs.  Model variables only: no
+  optimiser slot is carried over, so a stage may warm-start across optimisers (Config.optimizer)."""
   from .params import is_model_variable
   specs, state = trainer.store.specs, trainer.store.state
   usable = {k: v for k, v in previous_state.items()

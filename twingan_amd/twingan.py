@@ -477,6 +477,7 @@ class Trainer:
     self.reducer = GradReducer(world_size, process_group)
     store = self._declare(ParamStore(self.device), cfg)
     store.averaged = cfg.moving_average_decay is not None      # --moving_average_decay: shadows of the model variables
+    store.set_optimizer(cfg)                                   # --optimizer: the slots build() allocates
     self.store = store.build(seed)
     self.P = self.store.P
     self.n_critic_counter = 0       # image_generation.py:622-623
@@ -617,6 +618,12 @@ class Trainer:
     else:
       call('tg_adam_step', th, g, m, v, None, n, 0.0, lr_t, *hyper, 1.0 / c.loss_scale, st,
            work=('adam:numel%d' % n, 0, 28 * n))
+    self._after_apply(group, w, st)
+
+  def _after_apply(self, group, w, st):
+    """What follows the apply of ``group`` whatever the rule: the moving averages of everything the run did not apply, then
+    the weight packs of the convs that just moved."""
+    s = self.store
     if s.averaged:
       for other in s.GROUPS:
         if other != group:
@@ -626,6 +633,44 @@ class Trainer:
         tab = self._ema_table
         call('tg_ema_update_multi', tab[0].data_ptr(), tab[1], tab[2], w, st, work=('ema_multi:%d' % tab[1], 0, tab[3]))
     PackCache.refresh(self._group_weights[group])      # also after a skipped apply: it repacks the same bits
+
+  def _apply(self, group):
+    """The apply of --optimizer: Adam's own path, or tg_optim_step for the other rules."""
+    return self._adam(group) if self.cfg.optimizer == 'adam' else self._optim(group)
+
+  def _optim(self, group):
+    """_adam's sibling for --optimizer sgd | momentum | adagrad | rmsprop | adadelta | ftrl (model/model_inheritor.py:516-565):
+    one tg_optim_step on the group's flat buffers, with the moving average and the dynamic-loss-scale guard exactly as _adam
+    has them.  Every hyper-parameter goes by value, the guard and the average's weight are device pointers: a captured apply
+    graph replays unchanged.  The tick is Adam's (tg_adam_tick, or tg_loss_scale_tick under the guard): it keeps the device
+    count of applies made; the bias-corrected rate it also writes is not read.  The learning rate is Config.learning_rate
+    (the reference asserts learning_rate_decay_type == 'fixed'); use_ttur changes nothing here either."""
+    from ._lib import OPTIM_RULES, TgOptimHyper
+    c, s = self.cfg, self.store
+    st = torch.cuda.current_stream().cuda_stream
+    self.adam_t += 1
+    step, lr_t = self._adam_step_dev.data_ptr(), self._lr_t_dev.data_ptr()
+    n = s.flat[group].numel()
+    th, g = s.flat[group].data_ptr(), s.grad[group].data_ptr()
+    slots = [t.data_ptr() for t in s.slots[group]] + [None, None]
+    ls = self._ls[group].data_ptr() if self._ls is not None else None
+    avg = s.avg[group].data_ptr() if s.averaged else None
+    w = self._ema_w_dev.data_ptr() if s.averaged else None
+    rule = c.optimizer
+    hyper = TgOptimHyper(lr=c.learning_rate, momentum=c.rmsprop_momentum if rule == 'rmsprop' else c.momentum,
+                         decay_or_rho=c.adadelta_rho if rule == 'adadelta' else c.rmsprop_decay, eps=c.opt_epsilon,
+                         lr_power=c.ftrl_learning_rate_power, l1=c.ftrl_l1, l2=c.ftrl_l2)
+    if ls is not None:
+      call('tg_nonfinite_check', g, n, ls, st, work=('nonfinite:numel%d' % n, 0, 4 * n))
+      call('tg_loss_scale_tick', ls, step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2,
+           int(c.loss_scale_growth_interval), self._ls_max, self.world, st)
+    else:
+      call('tg_adam_tick', step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2, st)
+    nbytes = (12 + 8 * len(s.slots[group]) + (8 if s.averaged else 0)) * n
+    tag = 'optim_%s%s%s:numel%d' % (rule, '_ema' if s.averaged else '', '_guarded' if ls is not None else '', n)
+    call('tg_optim_step', OPTIM_RULES[rule], th, g, slots[0], slots[1], avg, n, ctypes.byref(hyper), 1.0 / c.loss_scale, ls, w, st,
+         work=(tag, 0, nbytes))
+    self._after_apply(group, w, st)
 
   # ---- moving averages (--moving_average_decay) ---------------------------------------------------------------
   def _build_ema_table(self):
@@ -737,7 +782,7 @@ class Trainer:
     for seg, out in self._grad_segments(group, sources, targets, gp_alpha_s, gp_alpha_t):
       self._reduce_start(group, seg)
     self.reducer.finish()
-    self._adam(group)
+    self._apply(group)
     return out
 
   def g_step(self, sources, targets):
@@ -748,11 +793,12 @@ class Trainer:
 
   # ---- hipGraph capture ---------------------------------------------------------------------------
   def _snapshot(self):
-    """Everything a training run mutates: parameters, Adam moments and step, non-trainable state (BatchNorm moving /
-    renorm statistics, spectral-norm u), the host counters and the device RNG."""
+    """Everything a training run mutates: parameters, Adam moments (or the slots of Config.optimizer's rule) and step,
+    non-trainable state (BatchNorm moving / renorm statistics, spectral-norm u), the host counters and the device RNG."""
     s = self.store
     return dict(flat={g: s.flat[g].clone() for g in s.GROUPS}, m={g: s.m[g].clone() for g in s.GROUPS},
-                v={g: s.v[g].clone() for g in s.GROUPS}, state={k: v.clone() for k, v in s.state.items()},
+                v={g: s.v[g].clone() for g in s.GROUPS}, slots={g: [t.clone() for t in ts] for g, ts in s.slots.items()},
+                state={k: v.clone() for k, v in s.state.items()},
                 step=self._adam_step_dev.clone(), lr=self._lr_t_dev.clone(), draws=self._rng_state.clone(),
                 host=(self.n_critic_counter, self.global_step, self.adam_t), rng=torch.cuda.get_rng_state(self.device),
                 # the moving averages and their weight: the undone warm-up of a capture must leave no trace in them
@@ -768,6 +814,8 @@ class Trainer:
         s.flat[g].copy_(snap['flat'][g])
         s.m[g].copy_(snap['m'][g])
         s.v[g].copy_(snap['v'][g])
+        for t, saved in zip(s.slots.get(g, ()), snap['slots'].get(g, ())):
+          t.copy_(saved)
         s.grad[g].zero_()
       for k, v in snap['state'].items():
         s.state[k].copy_(v)
@@ -836,7 +884,7 @@ class Trainer:
         gen.close()
       ga = torch.cuda.CUDAGraph()
       with torch.cuda.graph(ga, pool=pool, capture_error_mode=mode):
-        self._adam(kind)
+        self._apply(kind)
       graphs[kind] = (segs, ga)
     self.adam_t = adam_t                          # the captured (not executed) applies
     self._graphs, self._outs = graphs, outs
