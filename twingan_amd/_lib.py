@@ -1,11 +1,11 @@
-"""ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h).
+"""ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h, include/twingan_hip_summary.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a kernel call returns
 an error, this module raises.  (``oracle/`` is test infrastructure and is never imported here.)
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint, c_uint32, c_void_p
 
 TG_F32, TG_BF16, TG_F16 = 0, 1, 2
 TG_ALGO_DIRECT, TG_ALGO_MFMA = 0, 1
@@ -208,6 +208,27 @@ OPTIM_SIGNATURES = {
     'tg_optim_step': (c_int, [c_int, _FP, _FP, _FP, _FP, _FP, c_int64, POINTER(TgOptimHyper), c_float, _P, _FP, _P]),
 }
 
+# include/twingan_hip_summary.h, one to one as above.
+SUMMARY_POS_LIMITS, SUMMARY_BUCKETS = 774, 1551      # TG_SUMMARY_POS_LIMITS, TG_SUMMARY_BUCKETS
+
+
+class TgSummaryStats(Structure):
+  """One tensor's result of tg_summary_multi (include/twingan_hip_summary.h TgSummaryStats)."""
+  _fields_ = [('sum', c_double), ('sum_squares', c_double), ('min', c_float), ('max', c_float), ('num', c_uint32),
+              ('zeros', c_uint32), ('nonfinite', c_uint32), ('reserved', c_uint32)]
+
+
+SUMMARY_SIGNATURES = {
+    'tg_summary_limits': (c_int, [POINTER(c_double), POINTER(c_float)]),
+    'tg_summary_table_bytes': (c_size_t, [c_int]),
+    'tg_summary_table_fill': (c_int, [_P, c_int, c_int64, c_int64, c_int64, c_int, c_int, _P, POINTER(c_int32)]),
+    'tg_summary_workspace_bytes': (c_size_t, [c_int]),
+    'tg_summary_multi': (c_int, [_P, c_int, c_int, c_int, c_float, _FP, _FP, _P, _P, _P, c_size_t, _P]),
+    'tg_image_grid_table_bytes': (c_size_t, [c_int]),
+    'tg_image_grid_table_fill': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
+    'tg_image_grid_u8': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+}
+
 _lib = None
 
 
@@ -220,7 +241,7 @@ def load():
     raise TgError('%s not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                   '(make -C twingan_amd/csrc). There is no CPU fallback.' % LIB_PATH)
   lib = ctypes.CDLL(LIB_PATH)
-  for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+  for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items()):
     fn = getattr(lib, name)       # AttributeError if a declared symbol is missing
     fn.restype = res
     fn.argtypes = args

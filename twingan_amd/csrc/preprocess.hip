@@ -23,6 +23,7 @@
 // two images of that level once, forms the five Gaussian-windowed moments separably in LDS, sums the ssim and cs maps per
 // workgroup and writes the 2x2-mean pair the next level reads; an ordered pass per (level, image) and one small kernel finish.
 #include "tg_common.h"
+#include "../../include/twingan_hip_summary.h"
 
 namespace {
 
@@ -983,4 +984,81 @@ extern "C" int tg_swd_distance(const float* desc_a, int64_t n_a, const float* de
   rc = tg_swd_sort_columns(pb, rd, npad, stream);
   if (rc != TG_OK) return rc;
   return tg_swd_mean_abs_diff(pa, pb, n_a, npad, repeats, dirs_per, out, rest, rest_bytes, stream);
+}
+
+// ---- sample grids (include/twingan_hip_summary.h tg_image_grid_u8) ---------------------------------------------------------
+// One thread per grid pixel: it finds the job of its column slot, reads the pixel's c values and stores three bytes; a pixel
+// of a cell no job fills stores zeros, so the launch writes every byte of the grid once and needs no clear.
+namespace {
+struct GridJob {
+  const void* src;
+  int dtype, n, c, col;
+};
+
+// clip(trunc(x * 255), 0, 255): !(f > 0) takes NaN, -inf and every product that truncates to <= 0
+__device__ __forceinline__ unsigned char grid_byte(float x) {
+  const float f = x * 255.0f;
+  if (!(f > 0.f)) return 0;
+  return f >= 255.f ? (unsigned char)255 : (unsigned char)(int)f;
+}
+
+template <typename T>
+__device__ __forceinline__ void grid_pixel(const GridJob& j, int64_t pix, unsigned char* dst) {
+  const T* p = (const T*)j.src + pix * j.c;
+  const unsigned char r = grid_byte(ld<T>(p));
+  dst[0] = r;
+  dst[1] = j.c == 3 ? grid_byte(ld<T>(p + 1)) : r;
+  dst[2] = j.c == 3 ? grid_byte(ld<T>(p + 2)) : r;
+}
+
+__global__ __launch_bounds__(256) void image_grid_kernel(const GridJob* __restrict__ jobs, int njobs, int rows, int cols, int h, int w,
+                                                         unsigned char* __restrict__ grid) {
+  const int total = rows * h * cols * w;      // < 2^31: checked by the entry point
+  // the stride is added in 64 bits: the last trip of a grid near 2^31 pixels must not wrap
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
+    const int pix = (int)p;
+    const int y = pix / (cols * w), x = pix - y * (cols * w);
+    const int r = y / h, iy = y - r * h, cs = x / w, ix = x - cs * w;
+    unsigned char* dst = grid + (int64_t)pix * 3;
+    int k = 0;
+    while (k < njobs && !(jobs[k].col == cs && r < jobs[k].n)) ++k;
+    if (k == njobs) {
+      dst[0] = dst[1] = dst[2] = 0;
+      continue;
+    }
+    const GridJob j = jobs[k];
+    const int64_t src_pix = ((int64_t)r * h + iy) * w + ix;
+    if (j.dtype == TG_F32) grid_pixel<float>(j, src_pix, dst);
+    else if (j.dtype == TG_BF16) grid_pixel<bf16>(j, src_pix, dst);
+    else grid_pixel<f16>(j, src_pix, dst);
+  }
+}
+}  // namespace
+
+extern "C" size_t tg_image_grid_table_bytes(int njobs) { return (size_t)(njobs > 0 ? njobs : 0) * sizeof(GridJob); }
+
+extern "C" int tg_image_grid_table_fill(const void* src, int dtype, int n, int c, int col, int job, void* table_host) {
+  TG_CHECK(src, TG_EINVAL, "tg_image_grid_table_fill: src is null");
+  TG_CHECK(table_host, TG_EINVAL, "tg_image_grid_table_fill: table_host is null");
+  TG_CHECK(dtype == TG_F32 || dtype == TG_BF16 || dtype == TG_F16, TG_EINVAL, "tg_image_grid_table_fill: unsupported dtype %d", dtype);
+  TG_CHECK(n >= 1, TG_EINVAL, "tg_image_grid_table_fill: n must be positive (got %d)", n);
+  TG_CHECK(c == 1 || c == 3, TG_EINVAL, "tg_image_grid_table_fill: c must be 1 or 3 (got %d)", c);
+  TG_CHECK(col >= 0, TG_EINVAL, "tg_image_grid_table_fill: col must not be negative (got %d)", col);
+  TG_CHECK(job >= 0, TG_EINVAL, "tg_image_grid_table_fill: job must not be negative (got %d)", job);
+  ((GridJob*)table_host)[job] = GridJob{src, dtype, n, c, col};
+  return TG_OK;
+}
+
+extern "C" int tg_image_grid_u8(const void* table_device, int njobs, int rows, int cols, int h, int w, uint8_t* grid, void* stream) {
+  TG_CHECK(table_device, TG_EINVAL, "tg_image_grid_u8: table_device is null");
+  TG_CHECK(grid, TG_EINVAL, "tg_image_grid_u8: grid is null");
+  TG_CHECK(njobs >= 1, TG_EINVAL, "tg_image_grid_u8: njobs must be positive (got %d)", njobs);
+  TG_CHECK(rows >= 1 && cols >= 1, TG_EINVAL, "tg_image_grid_u8: rows and cols must be positive (got %d, %d)", rows, cols);
+  TG_CHECK(h >= 1 && w >= 1, TG_EINVAL, "tg_image_grid_u8: h and w must be positive (got %d, %d)", h, w);
+  const int64_t total = (int64_t)rows * h * cols * w;
+  TG_CHECK(total < (1ll << 31), TG_EINVAL, "tg_image_grid_u8: rows * h * cols * w = %lld pixels, the limit is 2^31 - 1", (long long)total);
+  hipLaunchKernelGGL(image_grid_kernel, dim3(tg_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const GridJob*)table_device,
+                     njobs, rows, cols, h, w, grid);
+  TG_LAUNCH_CHECK("tg_image_grid_u8");
+  return TG_OK;
 }

@@ -2,6 +2,7 @@
 // dense layer, the fused Adam step and the other --optimizer rules' apply.
 #include "tg_common.h"
 #include "../../include/twingan_hip_optim.h"
+#include "../../include/twingan_hip_summary.h"
 
 namespace {
 
@@ -1129,6 +1130,180 @@ int launch_optim_rule(const OptimArgs& a, void* stream) {
   return TG_OK;
 }
 
+// ---- training summaries (include/twingan_hip_summary.h): statistics and TensorFlow histogram of a table of tensors -----------
+// One workgroup summarises SUM_EPB consecutive logical elements of one job (the job found as in ema_multi_kernel): every
+// thread keeps its counts, minimum, maximum and the two double sums in registers, the workgroup reduces them in a fixed
+// order (xor tree in the wave, wave 0..3 in turn) and stores ONE partial; summary_finish_kernel adds a job's partials in
+// block order.  The histogram is a per-workgroup LDS array of TG_SUMMARY_BUCKETS counters beside the 774 float limits;
+// its non-zero bins go to the result with one integer atomic each (integer adds commute: the result has no order).
+struct SummaryJob {
+  const void* base;
+  int64_t row_stride;
+  uint32_t rows, row_valid, numel;      // numel = rows * row_valid < 2^32
+  int dtype, out;
+  int block_begin, block_end;
+};
+struct SummaryPartial {
+  double sum, sumsq;
+  float mn, mx;
+  uint32_t num, zeros, nonfinite, pad;
+};
+static_assert(sizeof(SummaryPartial) == sizeof(TgSummaryStats), "a partial is a result over one workgroup's elements");
+constexpr int SUM_EPB = 16384, SUM_THREADS = 256, SUM_U = 4;
+constexpr int SUM_NL = TG_SUMMARY_POS_LIMITS;
+constexpr float SUM_FLT_MAX = 3.402823466e+38f;
+
+// Bucket of a finite v: c = #{k: L[k] <= |v|} counted on the rounded-up float limits (exact for L[k] <= a, and for L[k] < a
+// too because no L[k] is a float itself: tg_summary_limits checks), then 776 + c for v >= 0 (both zeros: 776) and 775 - c for
+// v < 0.  The logarithm only guesses; the two loops make c exact against the table whatever the guess was.
+__device__ __forceinline__ int summary_bucket(float v, const float* lim) {
+  const float a = fabsf(v);
+  // k ~ log(a / 1e-12) / log(1.1) = (log2 a + 39.8631) * 7.27254
+  const float g = (log2f(a) + 39.863137f) * 7.2725409f;
+  int c = g > 0.f ? (g < (float)SUM_NL ? (int)g : SUM_NL) : 0;      // NaN-free: a is finite; a = 0 gives -inf -> 0
+  while (c < SUM_NL && lim[c] <= a) ++c;
+  while (c > 0 && lim[c - 1] > a) --c;
+  return v < 0.f ? SUM_NL + 1 - c : SUM_NL + 2 + c;
+}
+
+struct SummaryAcc {
+  double sum = 0.0, sumsq = 0.0;
+  float mn = SUM_FLT_MAX, mx = -SUM_FLT_MAX;
+  uint32_t num = 0, zeros = 0, nonfinite = 0;
+};
+
+template <typename T>
+__device__ __forceinline__ void summary_elements(const SummaryJob& j, int64_t i0, float scale, const float* scale_dev, bool unit,
+                                                 const float* lim, unsigned* hist, SummaryAcc& acc) {
+  const T* p = (const T*)j.base;
+  const bool dense = j.rows == 1 || j.row_stride == (int64_t)j.row_valid;
+  const float dev = scale_dev ? scale_dev[0] : 1.f;
+  for (int e0 = threadIdx.x; e0 < SUM_EPB; e0 += SUM_THREADS * SUM_U) {
+    float x[SUM_U];
+    bool in[SUM_U];
+#pragma unroll
+    for (int u = 0; u < SUM_U; ++u) {      // SUM_U independent loads in flight
+      const int64_t i = i0 + e0 + u * SUM_THREADS;
+      in[u] = i < (int64_t)j.numel;
+      x[u] = 0.f;
+      if (in[u]) {
+        int64_t off = i;
+        if (!dense) {
+          const uint32_t r = (uint32_t)i / j.row_valid;
+          off = (int64_t)r * j.row_stride + ((uint32_t)i - r * j.row_valid);
+        }
+        x[u] = ld<T>(p + off);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < SUM_U; ++u) {
+      if (!in[u]) continue;
+      float v = x[u];
+      if (!unit) {
+        v *= scale;
+        if (scale_dev) v *= dev;
+      }
+      if (nonfinite_bits(v)) {
+        ++acc.nonfinite;
+        continue;
+      }
+      ++acc.num;
+      acc.zeros += v == 0.f;
+      acc.mn = fminf(acc.mn, v);
+      acc.mx = fmaxf(acc.mx, v);
+      const double d = (double)v;
+      acc.sum += d;
+      acc.sumsq += d * d;
+      atomicAdd(&hist[summary_bucket(v, lim)], 1u);
+    }
+  }
+}
+
+__device__ __forceinline__ int summary_find_job(const SummaryJob* jobs, int njobs, int b) {
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (b >= jobs[mid].block_end) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(SUM_THREADS) void summary_partial_kernel(const SummaryJob* __restrict__ jobs, int njobs, int nout, float scale,
+                                                                      const float* __restrict__ scale_dev,
+                                                                      const float* __restrict__ limits, uint32_t* __restrict__ buckets,
+                                                                      SummaryPartial* __restrict__ partials) {
+  __shared__ unsigned hist[TG_SUMMARY_BUCKETS];
+  __shared__ float lim[SUM_NL];
+  __shared__ SummaryPartial red[SUM_THREADS / TG_WAVE];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const SummaryJob j = jobs[summary_find_job(jobs, njobs, b)];
+  // a grid larger than the table's total, a job whose result row the caller did not provide: nothing to do (uniform)
+  if (b < j.block_begin || b >= j.block_end || j.out >= nout) return;
+  for (int i = tid; i < TG_SUMMARY_BUCKETS; i += SUM_THREADS) hist[i] = 0u;
+  for (int i = tid; i < SUM_NL; i += SUM_THREADS) lim[i] = limits[i];
+  __syncthreads();
+  SummaryAcc acc;
+  const int64_t i0 = (int64_t)(b - j.block_begin) * SUM_EPB;
+  const bool unit = scale == 1.f && !scale_dev;
+  if (j.dtype == TG_F32) summary_elements<float>(j, i0, scale, scale_dev, unit, lim, hist, acc);
+  else if (j.dtype == TG_BF16) summary_elements<bf16>(j, i0, scale, scale_dev, unit, lim, hist, acc);
+  else summary_elements<f16>(j, i0, scale, scale_dev, unit, lim, hist, acc);
+  // the workgroup's partial, in a fixed order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    acc.sum += __shfl_xor(acc.sum, o, 64);
+    acc.sumsq += __shfl_xor(acc.sumsq, o, 64);
+    acc.mn = fminf(acc.mn, __shfl_xor(acc.mn, o, 64));
+    acc.mx = fmaxf(acc.mx, __shfl_xor(acc.mx, o, 64));
+    acc.num += __shfl_xor(acc.num, o, 64);
+    acc.zeros += __shfl_xor(acc.zeros, o, 64);
+    acc.nonfinite += __shfl_xor(acc.nonfinite, o, 64);
+  }
+  if ((tid & 63) == 0) red[tid >> 6] = SummaryPartial{acc.sum, acc.sumsq, acc.mn, acc.mx, acc.num, acc.zeros, acc.nonfinite, 0u};
+  __syncthreads();      // also: every LDS histogram add of the workgroup is done
+  if (tid == 0) {
+    SummaryPartial r = red[0];
+    for (int w = 1; w < SUM_THREADS / TG_WAVE; ++w) {
+      r.sum += red[w].sum;
+      r.sumsq += red[w].sumsq;
+      r.mn = fminf(r.mn, red[w].mn);
+      r.mx = fmaxf(r.mx, red[w].mx);
+      r.num += red[w].num;
+      r.zeros += red[w].zeros;
+      r.nonfinite += red[w].nonfinite;
+    }
+    partials[b] = r;
+  }
+  uint32_t* dst = buckets + (size_t)j.out * TG_SUMMARY_BUCKETS;
+  for (int i = tid; i < TG_SUMMARY_BUCKETS; i += SUM_THREADS) {
+    const unsigned n = hist[i];
+    if (n) atomicAdd(&dst[i], n);
+  }
+}
+
+// one thread per job: its partials in block order
+__global__ __launch_bounds__(64) void summary_finish_kernel(const SummaryJob* __restrict__ jobs, int njobs, int nout,
+                                                            const SummaryPartial* __restrict__ partials,
+                                                            TgSummaryStats* __restrict__ stats) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= njobs) return;
+  const SummaryJob j = jobs[k];
+  if (j.out >= nout) return;
+  TgSummaryStats r{0.0, 0.0, SUM_FLT_MAX, -SUM_FLT_MAX, 0u, 0u, 0u, 0u};
+  for (int b = j.block_begin; b < j.block_end; ++b) {
+    const SummaryPartial p = partials[b];
+    r.sum += p.sum;
+    r.sum_squares += p.sumsq;
+    r.min = fminf(r.min, p.mn);
+    r.max = fmaxf(r.max, p.mx);
+    r.num += p.num;
+    r.zeros += p.zeros;
+    r.nonfinite += p.nonfinite;
+  }
+  stats[j.out] = r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1530,6 +1705,94 @@ int tg_optim_step(int rule, float* theta, const float* grad, float* slot0, float
     case TG_OPT_ADADELTA: return launch_optim_rule<TG_OPT_ADADELTA>(a, stream);
     default: return hyper->lr_power == -0.5f ? launch_optim_rule<TG_OPT_FTRL>(a, stream) : launch_optim_rule<TG_OPT_FTRL_POW>(a, stream);
   }
+}
+
+int tg_summary_limits(double* limits, float* pos_limits_f32) {
+  double pos[TG_SUMMARY_POS_LIMITS + 1];
+  int n = 0;
+  for (double v = 1e-12; v < 1e20; v *= 1.1) {
+    TG_CHECK(n < TG_SUMMARY_POS_LIMITS, TG_ENOSUP, "tg_summary_limits: more than %d positive limits on this host", TG_SUMMARY_POS_LIMITS);
+    pos[n++] = v;
+  }
+  TG_CHECK(n == TG_SUMMARY_POS_LIMITS, TG_ENOSUP, "tg_summary_limits: %d positive limits on this host, not %d", n, TG_SUMMARY_POS_LIMITS);
+  float prev = 0.f;
+  for (int k = 0; k < n; ++k) {
+    float f = (float)pos[k];
+    if ((double)f < pos[k]) f = nextafterf(f, INFINITY);
+    TG_CHECK((double)f > pos[k] && f > prev, TG_ENOSUP, "tg_summary_limits: limit %d is a float itself or rounds onto its predecessor", k);
+    prev = f;
+    if (pos_limits_f32) pos_limits_f32[k] = f;
+  }
+  if (limits) {
+    limits[0] = -1.7976931348623157e308;
+    for (int k = 0; k < n; ++k) {
+      limits[1 + k] = -pos[n - 1 - k];
+      limits[n + 2 + k] = pos[k];
+    }
+    limits[n + 1] = 0.0;
+    limits[2 * n + 2] = 1.7976931348623157e308;
+  }
+  return TG_OK;
+}
+
+size_t tg_summary_table_bytes(int njobs) { return (size_t)(njobs > 0 ? njobs : 0) * sizeof(SummaryJob); }
+
+int tg_summary_table_fill(const void* base, int dtype, int64_t rows, int64_t row_valid, int64_t row_stride, int out, int job,
+                          void* table_host, int32_t* total_blocks) {
+  TG_CHECK(base, TG_EINVAL, "tg_summary_table_fill: base is null");
+  TG_CHECK(table_host, TG_EINVAL, "tg_summary_table_fill: table_host is null");
+  TG_CHECK(total_blocks, TG_EINVAL, "tg_summary_table_fill: total_blocks is null");
+  TG_CHECK(dtype == TG_F32 || dtype == TG_BF16 || dtype == TG_F16, TG_EINVAL, "tg_summary_table_fill: unsupported dtype %d", dtype);
+  TG_CHECK(rows >= 1, TG_EINVAL, "tg_summary_table_fill: rows must be positive (got %lld)", (long long)rows);
+  TG_CHECK(row_valid >= 1, TG_EINVAL, "tg_summary_table_fill: row_valid must be positive (got %lld)", (long long)row_valid);
+  TG_CHECK(row_stride >= row_valid, TG_EINVAL, "tg_summary_table_fill: row_stride (%lld) is below row_valid (%lld)",
+           (long long)row_stride, (long long)row_valid);
+  TG_CHECK(out >= 0, TG_EINVAL, "tg_summary_table_fill: out must not be negative (got %d)", out);
+  TG_CHECK(job >= 0, TG_EINVAL, "tg_summary_table_fill: job must not be negative (got %d)", job);
+  TG_CHECK(rows < (1ll << 32) && row_valid < (1ll << 32) && rows * row_valid < (1ll << 32), TG_EINVAL,
+           "tg_summary_table_fill: rows * row_valid (%lld x %lld) must stay below 2^32 elements", (long long)rows, (long long)row_valid);
+  const int64_t numel = rows * row_valid, blocks = (numel + SUM_EPB - 1) / SUM_EPB;
+  TG_CHECK(*total_blocks >= 0 && *total_blocks + blocks <= 0x7fffffff, TG_EINVAL, "tg_summary_table_fill: total_blocks: grid too large");
+  SummaryJob j;
+  j.base = base;
+  j.row_stride = row_stride;
+  j.rows = (uint32_t)rows;
+  j.row_valid = (uint32_t)row_valid;
+  j.numel = (uint32_t)numel;
+  j.dtype = dtype;
+  j.out = out;
+  j.block_begin = *total_blocks;
+  j.block_end = j.block_begin + (int)blocks;
+  *total_blocks = j.block_end;
+  ((SummaryJob*)table_host)[job] = j;
+  return TG_OK;
+}
+
+size_t tg_summary_workspace_bytes(int total_blocks) { return (size_t)(total_blocks > 0 ? total_blocks : 0) * sizeof(SummaryPartial); }
+
+int tg_summary_multi(const void* table_device, int njobs, int total_blocks, int nout, float scale, const float* scale_dev,
+                     const float* limits_dev, TgSummaryStats* stats, uint32_t* buckets, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  TG_CHECK(table_device, TG_EINVAL, "tg_summary_multi: table_device is null");
+  TG_CHECK(limits_dev, TG_EINVAL, "tg_summary_multi: limits_dev is null");
+  TG_CHECK(stats, TG_EINVAL, "tg_summary_multi: stats is null");
+  TG_CHECK(buckets, TG_EINVAL, "tg_summary_multi: buckets is null");
+  TG_CHECK(workspace, TG_EINVAL, "tg_summary_multi: workspace is null");
+  TG_CHECK(njobs > 0 && total_blocks > 0 && nout > 0, TG_EINVAL,
+           "tg_summary_multi: njobs, total_blocks and nout must be positive (got %d, %d, %d)", njobs, total_blocks, nout);
+  TG_CHECK(workspace_bytes >= tg_summary_workspace_bytes(total_blocks), TG_EINVAL,
+           "tg_summary_multi: workspace_bytes %zu is below the %zu that %d blocks need", workspace_bytes,
+           tg_summary_workspace_bytes(total_blocks), total_blocks);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = tg_zero_async(buckets, (size_t)nout * TG_SUMMARY_BUCKETS * sizeof(uint32_t), nullptr, 0, s);
+  if (rc != TG_OK) return rc;
+  hipLaunchKernelGGL(summary_partial_kernel, dim3(total_blocks), dim3(SUM_THREADS), 0, s, (const SummaryJob*)table_device, njobs, nout, scale,
+                     scale_dev, limits_dev, buckets, (SummaryPartial*)workspace);
+  TG_LAUNCH_CHECK("tg_summary_multi");
+  hipLaunchKernelGGL(summary_finish_kernel, dim3((njobs + 63) / 64), dim3(64), 0, s, (const SummaryJob*)table_device, njobs, nout,
+                     (const SummaryPartial*)workspace, stats);
+  TG_LAUNCH_CHECK("tg_summary_multi");
+  return TG_OK;
 }
 
 }  // extern "C"

@@ -3140,3 +3140,161 @@ def swd_distance(desc_a, desc_b, dirs, return_sorted=False):
     return out[r:], out[:r]
   npad, keys = swd_npad(n), (r * d * swd_npad(n) + 3) // 4 * 4
   return out[r:], out[:r], ws[:r * d * npad].view(r * d, npad), ws[keys:keys + r * d * npad].view(r * d, npad)
+
+
+# ------------------------------------------------------------------------------------------------
+# training summaries (include/twingan_hip_summary.h): tensor statistics + TF histogram, sample grids
+# ------------------------------------------------------------------------------------------------
+SUMMARY_BUCKETS = _lib.SUMMARY_BUCKETS
+_SUMMARY_STATS_BYTES = ctypes.sizeof(_lib.TgSummaryStats)
+_summary_limits_host = None
+_summary_limits_dev = {}
+
+
+def summary_limits():
+  """-> (limits float64 [1551], positive limits rounded up to float32 [774]) as NumPy arrays: tg_summary_limits, the one
+  place that computes TensorFlow's default histogram buckets."""
+  global _summary_limits_host
+  if _summary_limits_host is None:
+    import numpy as np
+    lim = (ctypes.c_double * _lib.SUMMARY_BUCKETS)()
+    pos = (ctypes.c_float * _lib.SUMMARY_POS_LIMITS)()
+    call('tg_summary_limits', lim, pos)
+    _summary_limits_host = (np.array(lim, dtype=np.float64), np.array(pos, dtype=np.float32))
+  return _summary_limits_host
+
+
+def _summary_limits_on(device):
+  key = str(device)
+  if key not in _summary_limits_dev:
+    _summary_limits_dev[key] = torch.from_numpy(summary_limits()[1].copy()).to(device)
+  return _summary_limits_dev[key]
+
+
+def _table_to(host, device):
+  return torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(device)
+
+
+def summary_rows(shape, phys=None):
+  """(rows, row_valid, row_stride) of a logical ``shape`` stored inside the physical shape ``phys`` (ParamStore.add_conv: the
+  two differ in at most one dimension, the padded input channels)."""
+  shape = tuple(int(d) for d in shape) or (1,)
+  phys = tuple(int(d) for d in (phys or shape)) or (1,)
+  diff = [i for i, (a, b) in enumerate(zip(shape, phys)) if a != b]
+  if len(shape) != len(phys) or len(diff) > 1 or any(shape[i] > phys[i] for i in diff):
+    raise _lib.TgError('tensor_summaries: shape %s does not lie inside the physical shape %s along one dimension' % (shape, phys))
+  if not diff:
+    n = 1
+    for d in shape:
+      n *= d
+    return 1, n, n
+  d = diff[0]
+  rows = inner = 1
+  for v in shape[:d]:
+    rows *= v
+  for v in shape[d + 1:]:
+    inner *= v
+  return rows, shape[d] * inner, phys[d] * inner
+
+
+class SummaryTable:
+  """Device job table of tg_summary_multi, built once for tensors that keep their addresses: job k writes result row k."""
+
+  def __init__(self, jobs, device):
+    """``jobs``: [(address, dtype code, rows, row_valid, row_stride)]."""
+    lib = _lib.load()
+    host = ctypes.create_string_buffer(lib.tg_summary_table_bytes(len(jobs)))
+    blocks = ctypes.c_int32(0)
+    for k, (ptr, dt, rows, valid, stride) in enumerate(jobs):
+      call('tg_summary_table_fill', ptr, dt, rows, valid, stride, k, k, ctypes.addressof(host), ctypes.byref(blocks))
+    self.njobs, self.blocks = len(jobs), blocks.value
+    self.nbytes = sum(j[2] * j[3] * (4 if j[1] == TG_F32 else 2) for j in jobs)
+    self.dev = _table_to(host, device)
+    self.ws_bytes = lib.tg_summary_workspace_bytes(self.blocks)
+    self.ws = torch.empty(max(self.ws_bytes, 8) // 8, dtype=torch.float64, device=device)
+
+  @classmethod
+  def of_tensors(cls, tensors):
+    _chk(*tensors)
+    return cls([(_p(t), _dt(t), 1, t.numel(), t.numel()) for t in tensors], tensors[0].device)
+
+  @classmethod
+  def of_flat(cls, flat, entries):
+    """``entries``: [(offset in elements, logical shape, physical shape)] inside the contiguous buffer ``flat``."""
+    _chk(flat)
+    es = flat.element_size()
+    return cls([(flat.data_ptr() + int(off) * es, _dt(flat)) + summary_rows(shape, phys) for off, shape, phys in entries], flat.device)
+
+
+class SummaryBuffer:
+  """``n`` result rows in ONE device allocation (n TgSummaryStats, then n x 1551 uint32 buckets), so that a read-out is one
+  device-to-host copy."""
+
+  def __init__(self, n, device, extra=0):
+    """``extra``: fp32 scalars carried behind the rows (extra_view()): loss terms and the like ride in the same copy."""
+    self.n, self.extra = int(n), int(extra)
+    self._rows_bytes = self.n * (_SUMMARY_STATS_BYTES + 4 * SUMMARY_BUCKETS)
+    self.raw = torch.zeros(self._rows_bytes + 4 * self.extra, dtype=torch.uint8, device=device)
+
+  def extra_view(self):
+    return self.raw[self._rows_bytes:].view(torch.float32)
+
+  def stats_ptr(self, row=0):
+    return self.raw.data_ptr() + row * _SUMMARY_STATS_BYTES
+
+  def buckets_ptr(self, row=0):
+    return self.raw.data_ptr() + self.n * _SUMMARY_STATS_BYTES + row * 4 * SUMMARY_BUCKETS
+
+  def read(self, extra=False):
+    """The one synchronisation: -> (stats, buckets), a NumPy record array [n] with the fields of TgSummaryStats and uint32
+    [n, 1551]; with ``extra`` also the fp32 scalars."""
+    import numpy as np
+    host = self.raw.cpu().numpy()
+    dt = np.dtype([('sum', '<f8'), ('sum_squares', '<f8'), ('min', '<f4'), ('max', '<f4'), ('num', '<u4'), ('zeros', '<u4'),
+                   ('nonfinite', '<u4'), ('reserved', '<u4')])
+    k = self.n * _SUMMARY_STATS_BYTES
+    stats = host[:k].view(dt).copy()
+    buckets = host[k:self._rows_bytes].view(np.uint32).reshape(self.n, SUMMARY_BUCKETS).copy()
+    return (stats, buckets, host[self._rows_bytes:].view(np.float32).copy()) if extra else (stats, buckets)
+
+
+def tensor_summaries(tensors=None, flat=None, entries=None, scale=1.0, scale_dev=None, table=None, out=None, row=0):
+  """Statistics and TensorFlow histogram of every tensor of a table in one pass over the data (tg_summary_multi): of
+  ``tensors`` (contiguous fp32 / bf16 / fp16), or of ``entries`` = [(offset, shape, phys)] inside the buffer ``flat``, or of
+  a SummaryTable built earlier.  v = float(x) * scale (* scale_dev[0], a device scalar).  Job k writes row ``row`` + k of
+  ``out`` (a SummaryBuffer; a fresh one when None).  No synchronisation: -> the SummaryBuffer, whose read() is the copy."""
+  if table is None:
+    table = SummaryTable.of_tensors(list(tensors)) if tensors is not None else SummaryTable.of_flat(flat, entries)
+  dev = table.dev.device
+  if out is None:
+    out = SummaryBuffer(row + table.njobs, dev)
+  if row < 0 or row + table.njobs > out.n:
+    raise _lib.TgError('tensor_summaries: rows %d..%d do not fit a buffer of %d' % (row, row + table.njobs, out.n))
+  _chk(scale_dev)
+  call('tg_summary_multi', _p(table.dev), table.njobs, table.blocks, table.njobs, float(scale), _p(scale_dev),
+       _p(_summary_limits_on(dev)), out.stats_ptr(row), out.buckets_ptr(row), _p(table.ws), table.ws_bytes, _stream(),
+       work=('summary:%d' % table.njobs, 0, table.nbytes))
+  return out
+
+
+def image_grid(batches, rows, cols, out=None):
+  """uint8 grid [rows * h, cols * w, 3] on the device from ``batches`` = [(NHWC tensor [n, h, w, 1 | 3], column slot)]: image
+  i of a batch fills cell (i, slot), byte = clip(trunc(x * 255), 0, 255); cells nobody fills are 0.  One launch
+  (tg_image_grid_u8), no synchronisation."""
+  ts = [t for t, _ in batches]
+  _chk(*ts)
+  if not ts or any(t.dim() != 4 or t.shape[1:3] != ts[0].shape[1:3] for t in ts):
+    raise _lib.TgError('image_grid: batches are NHWC tensors of one height and width')
+  h, w = int(ts[0].shape[1]), int(ts[0].shape[2])
+  lib = _lib.load()
+  host = ctypes.create_string_buffer(lib.tg_image_grid_table_bytes(len(ts)))
+  for k, (t, col) in enumerate(batches):
+    call('tg_image_grid_table_fill', _p(t), _dt(t), int(t.shape[0]), int(t.shape[3]), int(col), k, ctypes.addressof(host))
+  tab = _table_to(host, ts[0].device)
+  if out is None:
+    out = torch.empty(rows * h, cols * w, 3, dtype=torch.uint8, device=ts[0].device)
+  elif out.dtype != torch.uint8 or tuple(out.shape) != (rows * h, cols * w, 3) or not out.is_contiguous():
+    raise _lib.TgError('image_grid: out must be a contiguous uint8 tensor [%d, %d, 3]' % (rows * h, cols * w))
+  call('tg_image_grid_u8', _p(tab), len(ts), int(rows), int(cols), h, w, _p(out), _stream(),
+       work=('image_grid', 0, sum(t.numel() * t.element_size() for t in ts) + out.numel()))
+  return out      # the table was allocated on this stream: its memory is not reused before the launch has read it

@@ -57,7 +57,7 @@ def warm_start(trainer, previous_state):
 
 def run_progressive(base_cfg, batch_fn, start_hw=4, max_hw=256, hw_to_batch_size=None, num_images_per_resolution=300000,
                     device='cuda', seed=0, max_steps_per_stage=None, use_graph=False, on_stage_end=None, train_dir=None,
-                    save_interval_secs=600, save_interval_steps=None, max_to_keep=5):
+                    save_interval_secs=600, save_interval_steps=None, max_to_keep=5, monitor=None):
   """Trains stage after stage.  ``batch_fn(hw, batch_size)`` -> (sources, targets) device tensors, or
   (sources, targets, gp_alpha_s, gp_alpha_t) to fix the gradient-penalty interpolation draws (tests); a trailing dict
   holds further dataset fields for Trainer.run (distill_embed_s / distill_embed_t of --do_encoder_distillation).
@@ -69,11 +69,17 @@ def run_progressive(base_cfg, batch_fn, start_hw=4, max_hw=256, hw_to_batch_size
   previous stage's directory with ignore_missing_vars = is_growing, and saves model.ckpt-<global_step> at its end and,
   like slim.learning.train's Saver (--save_interval_secs, model_inheritor.py:75,1126: 600 s), every
   ``save_interval_secs`` seconds (or every ``save_interval_steps`` steps) inside a stage, keeping ``max_to_keep`` files:
-  the final stage runs for 10 M steps, an interruption must not lose it."""
+  the final stage runs for 10 M steps, an interruption must not lose it.
+  ``monitor``: a monitor.Monitor (needs ``train_dir``).  Every stage gets its event file in <train_dir>/<name> and its sample
+  grids in <train_dir>/<name>/generated_samples; the monitor is called before the stage's first step and after every global
+  step, and decides itself what is due (--save_summaries_secs, --log_image_every_n_iter: model_inheritor.py:1094-1126,
+  twingan.py:606-678)."""
   import os
   import time
   from . import checkpoint as ckpt
   from .twingan import Trainer
+  if monitor is not None and not train_dir:
+    raise ValueError('run_progressive: a monitor writes into the stages\' directories: pass train_dir')
   state = None
   history = []
   last_dir = None
@@ -97,6 +103,9 @@ def run_progressive(base_cfg, batch_fn, start_hw=4, max_hw=256, hw_to_batch_size
     else:
       loaded = warm_start(tr, state) if state is not None else []
     last_save = time.time()
+    if monitor is not None:
+      monitor.begin(tr, cur_dir, bsz)
+      monitor.step(tr, first)
     for step in range(first, steps):
       if growing:
         tr.cfg.alpha_grow = alpha_grow(step, steps)
@@ -106,6 +115,8 @@ def run_progressive(base_cfg, batch_fn, start_hw=4, max_hw=256, hw_to_batch_size
           tr.run(*batch[:-1], **batch[-1])
         else:
           tr.run(*batch)
+      if monitor is not None:
+        monitor.step(tr, step + 1)
       if cur_dir and step + 1 < steps and (
           (save_interval_steps and (step + 1) % save_interval_steps == 0) or
           (save_interval_secs and time.time() - last_save >= save_interval_secs)):
@@ -120,5 +131,7 @@ def run_progressive(base_cfg, batch_fn, start_hw=4, max_hw=256, hw_to_batch_size
       history[-1]['loss_scale'] = tr.loss_scale_state()
     if on_stage_end is not None:
       on_stage_end(name, tr)
+    if monitor is not None:
+      monitor.end()
     tr.close()
   return state, history

@@ -498,6 +498,8 @@ class Trainer:
     self.split = bool(want and cfg.overlap_cut_hw and cfg.hw > cfg.overlap_cut_hw)
     self._ptr_phase = {self.P[k].data_ptr(): ph for k, ph in self.store.phase.items()}
     self._extras = None             # per-run dataset fields besides the images (run(..., distill_embed_s=, distill_embed_t=))
+    self.last_run = None            # (group, loss, terms) of the last run()
+    self.last_losses = {}           # group -> (loss, terms) of that group's last run (monitor.Monitor reads both)
     self.use_graph = use_graph
     self.graph_fallback_reason = None
     self.capture_note = None        # set when the segmented capture had to be replaced by one graph per step kind
@@ -990,6 +992,9 @@ class Trainer:
         out = self.g_step(sources, targets)
       else:
         out = self.d_step(sources, targets, gp_alpha_s, gp_alpha_t)
+    if out is not None:      # (group, loss, terms) of the last run: what monitor.Monitor reads
+      self.last_run = ('g' if is_g else 'd',) + tuple(out)
+      self.last_losses[self.last_run[0]] = tuple(out)
     self._advance_counters()
     return out
 
