@@ -1,4 +1,5 @@
-"""ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h, include/twingan_hip_summary.h).
+"""ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h, include/twingan_hip_summary.h,
+include/twingan_hip_knn.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a kernel call returns
 an error, this module raises.  (``oracle/`` is test infrastructure and is never imported here.)
@@ -229,6 +230,17 @@ SUMMARY_SIGNATURES = {
     'tg_image_grid_u8': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
+# include/twingan_hip_knn.h, one to one as above.
+KNN_MAX_K = 32      # TG_KNN_MAX_K
+KNN_METRICS = {'l2': 0, 'cosine': 1}      # TG_KNN_L2, TG_KNN_COSINE
+
+KNN_SIGNATURES = {
+    'tg_knn_sqnorm': (c_int, [_P, c_int64, c_int, c_int, _FP, _P]),
+    'tg_knn_plan': (c_int, [c_int64, c_int64, c_int, c_int, POINTER(c_int)]),
+    'tg_knn_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    'tg_knn_topk': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int64, _P, _FP, _P, _P, c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -241,7 +253,8 @@ def load():
     raise TgError('%s not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                   '(make -C twingan_amd/csrc). There is no CPU fallback.' % LIB_PATH)
   lib = ctypes.CDLL(LIB_PATH)
-  for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items()):
+  for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items()) + \
+      list(KNN_SIGNATURES.items()):
     fn = getattr(lib, name)       # AttributeError if a declared symbol is missing
     fn.restype = res
     fn.argtypes = args

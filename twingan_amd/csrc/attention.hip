@@ -12,6 +12,7 @@
 //   * tg_tanh_{fwd,bwd}, tg_mul3, tg_dot, tg_scale_dev   the pointwise pieces and the sa_gamma scale / reduction
 // Replaces tf.matmul x2, tf.nn.softmax, tf.nn.tanh and the gamma * o + layer arithmetic of libs/self_attention.py:57-69.
 #include "tg_common.h"
+#include "../../include/twingan_hip_knn.h"
 
 namespace {
 
@@ -275,6 +276,355 @@ __global__ __launch_bounds__(256) void dot_final_kernel(const float* __restrict_
   if (threadIdx.x == 0) out[0] = t;
 }
 
+// ---- nearest-neighbour search over embeddings (include/twingan_hip_knn.h) -------------------------------------------------
+// A workgroup owns a tile of queries and walks gallery tiles of 128 rows.  16-bit: the bgemm staging above with both operands
+// K-contiguous ([rows][32 k] at 80 B a row, ds_read_b128 fragments), wave w holds the 32 QB x 32 dot products of the tile's
+// columns 32 w ..; fp32: one thread per pair.  Either way a pair's reduction over d is one fixed chain.  Selection is shared:
+// per query a list of k (distance, chunk-local index), ascending, in LDS as [slot][query] (a thread walks its own query's
+// column: no bank conflict); the list's last slot is the filter every candidate meets first.  What passes is staged, 32
+// columns at a time, and the query's own thread inserts in column order -- the order does not matter to the result, since
+// (distance, index) is a total order, but a fixed one costs nothing.  Every split's list goes to the workspace, and
+// knn_merge_kernel folds the incoming table and the partials, split by split, into the in/out table.
+constexpr int KNN_K = TG_KNN_MAX_K;
+constexpr int KNN_GT = 128;      // gallery rows per tile
+constexpr int KNN_SW = 33;       // floats per staged row of 32 columns (+1: a thread per row scans without conflicts)
+constexpr int KNN_ROW = 80;      // bytes per staged operand row, as A_KC_STRIDE
+
+struct KnnGeom {
+  int q, n, d, k, metric, splits, tiles, vec;
+  int64_t index_offset;
+  const int64_t* query_ids;
+  const float* qn;
+  const float* gn;
+  float* part_d;
+  int* part_i;
+};
+
+template <typename I>
+__device__ __forceinline__ bool knn_less(float d1, I i1, float d2, I i2) { return d1 < d2 || (d1 == d2 && i1 < i2); }
+
+__device__ __forceinline__ float knn_distance(int metric, float qn, float gn, float dot) {
+  if (metric == TG_KNN_L2) {
+    const float t = (qn + gn) - 2.f * dot;
+    return t < 0.f ? 0.f : t;      // not fmaxf: a NaN stays a NaN
+  }
+  const float den = sqrtf(qn) * sqrtf(gn);
+  return den == 0.f ? 1.f : 1.f - dot / den;
+}
+
+// (d, gi) into the ascending list whose slot j is at [j * stride]; false when it does not beat the last slot (NaN never does)
+template <typename I>
+__device__ __forceinline__ bool knn_insert(float* ld_, I* li, int stride, int k, float d, I gi) {
+  if (!knn_less<I>(d, gi, ld_[(k - 1) * stride], li[(k - 1) * stride])) return false;
+  int j = k - 1;
+  while (j > 0 && knn_less<I>(d, gi, ld_[(j - 1) * stride], li[(j - 1) * stride])) {
+    ld_[j * stride] = ld_[(j - 1) * stride];
+    li[j * stride] = li[(j - 1) * stride];
+    --j;
+  }
+  ld_[j * stride] = d;
+  li[j * stride] = gi;
+  return true;
+}
+
+// the query's own thread: the 32 staged columns of its row, NaN = not a candidate, column c = chunk row `first` + c
+__device__ __forceinline__ void knn_scan(const float* stage_row, float* ld_, int* li, int stride, int k, int first, int skip) {
+#pragma unroll 1
+  for (int c = 0; c < 32; ++c) {
+    const float v = stage_row[c];
+    if (v == v && first + c != skip) knn_insert<int>(ld_, li, stride, k, v, first + c);
+  }
+}
+
+// gload8 for a dense [rows][d] matrix whose tail (d % 8 != 0, or a base that is not 16-byte aligned) is read without a branch
+// per element: the address is clamped into the row and the value selected afterwards
+__device__ __forceinline__ bf16x8 knn_load8(const bf16* base, int row, int col, int rows, int d, bool vec) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (bf16)0.f;
+  if (row >= rows || col >= d) return v;
+  const bf16* p = base + (size_t)row * d;
+  if (vec) return *reinterpret_cast<const bf16x8*>(p + col);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const bf16 x = p[col + j < d ? col + j : d - 1];
+    v[j] = col + j < d ? x : (bf16)0.f;
+  }
+  return v;
+}
+
+template <int BM>
+__device__ __forceinline__ void knn_write_partial(const KnnGeom& g, const float* listD, const int* listI, int q0, int split) {
+  for (int i = threadIdx.x; i < g.k * BM; i += 256) {
+    const int j = i / BM, row = i - j * BM;
+    if (q0 + row >= g.q) continue;
+    const size_t off = ((size_t)split * g.q + (q0 + row)) * g.k + j;
+    g.part_d[off] = listD[j * BM + row];
+    g.part_i[off] = listI[j * BM + row];
+  }
+}
+
+template <int QB, bool F16>
+__global__ __launch_bounds__(256, 2) void knn_mfma_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ G, const KnnGeom g) {
+  constexpr int BM = 32 * QB;
+  constexpr int A_BYTES = BM * KNN_ROW, B_BYTES = KNN_GT * KNN_ROW, STAGE_BYTES = BM * KNN_SW * 4;
+  constexpr int S_BYTES = A_BYTES + B_BYTES > STAGE_BYTES ? A_BYTES + B_BYTES : STAGE_BYTES;
+  constexpr int AV = (BM * 4 + 255) / 256;      // 16-byte vectors of the query tile per thread
+  __shared__ __attribute__((aligned(16))) unsigned char smem[S_BYTES];      // operand tiles; the staged distances after the k loop
+  __shared__ float listD[KNN_K * BM];
+  __shared__ int listI[KNN_K * BM];
+  __shared__ float sQn[BM];
+  // QB < 4 (few queries: the search is bound by reading the gallery once): the gallery norms come from this loop too -- the
+  // B fragment against itself, the diagonal of the wave's 32 x 32 block, the very chain of knn_sqnorm_mfma_kernel -- instead of
+  // from a pass of their own over the gallery; with 128 queries a fifth MFMA a step costs more than that pass
+  constexpr bool GN = QB < 4;
+  __shared__ float sGn[KNN_GT];
+  unsigned char* sA = smem;
+  unsigned char* sB = smem + A_BYTES;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, kg = lane >> 5;
+  const int q0 = blockIdx.x * BM, split = blockIdx.y;
+  // tiles < 2^24 and splits <= 256: the products fit 32 bits
+  const int t_lo = (int)((unsigned)split * (unsigned)g.tiles / (unsigned)g.splits);
+  const int t_hi = (int)((unsigned)(split + 1) * (unsigned)g.tiles / (unsigned)g.splits);
+  const bool vec = g.vec != 0;
+  int skip = -1;      // thread `row` of the tile: the chunk row that is the query itself (query_ids)
+
+  for (int i = tid; i < KNN_K * BM; i += 256) {
+    listD[i] = INFINITY;
+    listI[i] = -1;
+  }
+  if (tid < BM) {
+    const bool in = q0 + tid < g.q;
+    sQn[tid] = in ? g.qn[q0 + tid] : 0.f;
+    const int64_t self = in && g.query_ids ? g.query_ids[q0 + tid] - g.index_offset : -1;
+    skip = self >= 0 && self < g.n ? (int)self : -1;
+  }
+  __syncthreads();
+
+  const int a_frag = i32 * KNN_ROW + kg * 16, b_frag = (wid * 32 + i32) * KNN_ROW + kg * 16;
+  for (int t = t_lo; t < t_hi; ++t) {
+    const int g0 = t * KNN_GT;
+    f32x16 acc[QB];
+#pragma unroll
+    for (int i = 0; i < QB; ++i)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[i][j] = 0.f;
+
+    f32x16 accn;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) accn[j] = 0.f;
+
+    bf16x8 ra[AV], rb[2];
+    auto load_tiles = [&](int k0) __attribute__((always_inline)) {
+#pragma unroll
+      for (int s = 0; s < AV; ++s) {
+        const int v = tid + s * 256;
+        if (v < BM * 4) ra[s] = knn_load8(Q, q0 + (v >> 2), k0 + (v & 3) * 8, g.q, g.d, vec);
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int v = tid + s * 256;
+        rb[s] = knn_load8(G, g0 + (v >> 2), k0 + (v & 3) * 8, g.n, g.d, vec);
+      }
+    };
+    load_tiles(0);
+    for (int k0 = 0; k0 < g.d; k0 += 32) {
+      __syncthreads();      // the previous step's fragment reads (or the previous tile's staged distances) are done with
+#pragma unroll
+      for (int s = 0; s < AV; ++s) {
+        const int v = tid + s * 256;
+        if (v < BM * 4) *reinterpret_cast<bf16x8*>(sA + (v >> 2) * KNN_ROW + (v & 3) * 16) = ra[s];
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int v = tid + s * 256;
+        *reinterpret_cast<bf16x8*>(sB + (v >> 2) * KNN_ROW + (v & 3) * 16) = rb[s];
+      }
+      __syncthreads();
+      if (k0 + 32 < g.d) load_tiles(k0 + 32);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(sB + b_frag + ks * 32);
+        if constexpr (GN) accn = mfma_32x32x16<F16>(bfr, bfr, accn);
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) {
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(sA + a_frag + qb * 32 * KNN_ROW + ks * 32);
+          acc[qb] = mfma_32x32x16<F16>(af, bfr, acc[qb]);
+        }
+      }
+    }
+
+    // acc[qb][r]: query row 32 qb + (r & 3) + 8 (r >> 2) + 4 kg, gallery column g0 + 32 wid + i32.  The waves take turns to
+    // stage their 32 columns of distances (NaN: no such gallery row); each query's thread filters and inserts.  Eight
+    // barriers a tile, against two per 32 of d in the loop above.
+    const int gcol = g0 + wid * 32 + i32;
+    const bool gvalid = gcol < g.n;
+    float gnv = 0.f;
+    if constexpr (GN) {      // column i's norm is element (i, i): lane (i, kg = (i >> 2) & 1), register 4 (i >> 3) + (i & 3)
+      // registers 4 a + c of the lanes with kg == b hold rows 8 a + 4 b + c: two selects on the lane's own a and c
+      const int a = i32 >> 3, c = i32 & 3;
+      f32x4 quad;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) quad[j] = a == 0 ? accn[j] : a == 1 ? accn[4 + j] : a == 2 ? accn[8 + j] : accn[12 + j];
+      const float v = c == 0 ? quad[0] : c == 1 ? quad[1] : c == 2 ? quad[2] : quad[3];
+      if (kg == ((i32 >> 2) & 1)) sGn[wid * 32 + i32] = v;
+    } else if (gvalid) {
+      gnv = g.gn[gcol];
+    }
+    float* stage = reinterpret_cast<float*>(smem);
+    __syncthreads();      // every fragment read of smem is done; the tile's norms are in sGn
+    if constexpr (GN) gnv = sGn[wid * 32 + i32];
+#pragma unroll 1
+    for (int w = 0; w < 4; ++w) {
+      if (wid == w) {
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int row = qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
+            const float dv = knn_distance(g.metric, sQn[row], gnv, acc[qb][r]);
+            stage[row * KNN_SW + i32] = gvalid ? dv : NAN;
+          }
+      }
+      __syncthreads();
+      if (tid < BM && q0 + tid < g.q) knn_scan(stage + tid * KNN_SW, listD + tid, listI + tid, BM, g.k, g0 + w * 32, skip);
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  knn_write_partial<BM>(g, listD, listI, q0, split);
+}
+
+// any dtype: 8 queries x 32 gallery rows per step, one thread per pair, one fmaf chain over d (the fp32 exact-parity path)
+template <typename T>
+__global__ __launch_bounds__(256) void knn_valu_kernel(const T* __restrict__ Q, const T* __restrict__ G, const KnnGeom g) {
+  constexpr int BM = 8;
+  __shared__ float stage[BM * KNN_SW];
+  __shared__ float listD[KNN_K * BM];
+  __shared__ int listI[KNN_K * BM];
+  const int tid = threadIdx.x, qr = tid >> 5, c = tid & 31;
+  const int q0 = blockIdx.x * BM, split = blockIdx.y;
+  // tiles < 2^24 and splits <= 256: the products fit 32 bits
+  const int t_lo = (int)((unsigned)split * (unsigned)g.tiles / (unsigned)g.splits);
+  const int t_hi = (int)((unsigned)(split + 1) * (unsigned)g.tiles / (unsigned)g.splits);
+  for (int i = tid; i < KNN_K * BM; i += 256) {
+    listD[i] = INFINITY;
+    listI[i] = -1;
+  }
+  const bool qin = q0 + qr < g.q;
+  const T* qp = Q + (size_t)(qin ? q0 + qr : 0) * g.d;
+  const float qnv = qin ? g.qn[q0 + qr] : 0.f;
+  const int64_t self = qin && g.query_ids ? g.query_ids[q0 + qr] - g.index_offset : -1;
+  const int skip = self >= 0 && self < g.n ? (int)self : -1;
+  __syncthreads();
+  for (int t = t_lo; t < t_hi; ++t)
+    for (int sub = 0; sub < KNN_GT / 32; ++sub) {
+      const int first = t * KNN_GT + sub * 32;
+      if (first >= g.n) break;
+      const int gcol = first + c;
+      float dv = NAN;
+      if (qin && gcol < g.n && gcol != skip) {
+        const T* gp = G + (size_t)gcol * g.d;
+        float dot = 0.f;
+        for (int i = 0; i < g.d; ++i) dot = fmaf(ld(qp + i), ld(gp + i), dot);
+        dv = knn_distance(g.metric, qnv, g.gn[gcol], dot);
+      }
+      stage[qr * KNN_SW + c] = dv;
+      __syncthreads();
+      if (tid < BM) knn_scan(stage + tid * KNN_SW, listD + tid, listI + tid, BM, g.k, first, -1);
+      __syncthreads();
+    }
+  knn_write_partial<BM>(g, listD, listI, q0, split);
+}
+
+// one thread per query: the incoming table, then every split's partial list in split order, through the same insertion
+__global__ __launch_bounds__(64) void knn_merge_kernel(const KnnGeom g, float* __restrict__ dist, int64_t* __restrict__ idx) {
+  __shared__ float mD[KNN_K * 64];
+  __shared__ int64_t mI[KNN_K * 64];
+  const int t = threadIdx.x;
+  const int64_t qrow = (int64_t)blockIdx.x * 64 + t;
+  if (qrow >= g.q) return;
+  for (int j = 0; j < g.k; ++j) {
+    mD[j * 64 + t] = INFINITY;
+    mI[j * 64 + t] = -1;
+  }
+  for (int j = 0; j < g.k; ++j) knn_insert<int64_t>(mD + t, mI + t, 64, g.k, dist[qrow * g.k + j], idx[qrow * g.k + j]);
+  for (int s = 0; s < g.splits; ++s)
+    for (int j = 0; j < g.k; ++j) {
+      const size_t off = ((size_t)s * g.q + qrow) * g.k + j;
+      const int li = g.part_i[off];
+      // a partial list ascends: after its first filler, or its first entry that does not get in, nothing of it does
+      if (li < 0 || !knn_insert<int64_t>(mD + t, mI + t, 64, g.k, g.part_d[off], g.index_offset + li)) break;
+    }
+  for (int j = 0; j < g.k; ++j) {
+    dist[qrow * g.k + j] = mD[j * 64 + t];
+    idx[qrow * g.k + j] = mI[j * 64 + t];
+  }
+}
+
+// Squared norms by the SAME reduction as the search's dot product of the row with itself, so that the squared L2 distance
+// of a row to a bitwise copy of it is exactly 0.  fp32: the one fmaf chain.
+__global__ __launch_bounds__(256) void knn_sqnorm_f32_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t rows, int d) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= rows) return;
+  const float* p = x + (size_t)row * d;
+  float acc = 0.f;
+  for (int i = 0; i < d; ++i) acc = fmaf(p[i], p[i], acc);
+  out[row] = acc;
+}
+
+// 16-bit: a wave takes 32 rows and runs the search's MFMA chain on them against themselves, both operands one register (lane
+// l: row l % 32, k 8 (l / 32) .. of the step's 16); row i's norm is the diagonal element (i, i) of the 32 x 32 result, which
+// lives in lane (i, kg = (i >> 2) & 1) at register 4 (i >> 3) + (i & 3).  32 MACs per element read: the price of the exact 0.
+template <bool F16>
+__global__ __launch_bounds__(256) void knn_sqnorm_mfma_kernel(const bf16* __restrict__ x, float* __restrict__ out, int rows, int d, int vec) {
+  const int lane = threadIdx.x & 63, i32 = lane & 31, kg = lane >> 5;
+  const int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
+  if (r0 >= rows) return;      // a whole wave
+  f32x16 acc;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+  const int dpad = (d + 31) & ~31;      // as many steps as the search runs
+  for (int k0 = 0; k0 < dpad; k0 += 16) {
+    const bf16x8 a = knn_load8(x, r0 + i32, k0 + kg * 8, rows, d, vec != 0);
+    acc = mfma_32x32x16<F16>(a, a, acc);
+  }
+  const int rsel = 4 * (i32 >> 3) + (i32 & 3);
+  float v = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (r == rsel) v = acc[r];
+  if (kg == ((i32 >> 2) & 1) && r0 + i32 < rows) out[r0 + i32] = v;
+}
+
+constexpr int64_t KNN_MAX_ROWS = (1ll << 31) - 1024;
+
+int knn_plan(int64_t q, int64_t n, int d, int k, int* splits, int* tiles) {
+  TG_CHECK(q >= 1 && q <= KNN_MAX_ROWS, TG_EINVAL, "tg_knn: q = %lld outside 1 .. 2^31 - 1024", (long long)q);
+  TG_CHECK(n >= 1 && n <= KNN_MAX_ROWS, TG_EINVAL, "tg_knn: n = %lld outside 1 .. 2^31 - 1024", (long long)n);
+  TG_CHECK(d >= 1 && d <= (1 << 30), TG_EINVAL, "tg_knn: d = %d outside 1 .. 2^30", d);
+  TG_CHECK(k >= 1 && k <= TG_KNN_MAX_K, TG_EINVAL, "tg_knn: k = %d outside 1 .. %d", k, TG_KNN_MAX_K);
+  const int64_t t = (n + KNN_GT - 1) / KNN_GT, q32 = (q + 31) / 32, want = (1024 + q32 - 1) / q32;
+  int64_t s = want < 256 ? want : 256;
+  if (s > t) s = t;
+  *tiles = (int)t;
+  *splits = (int)s;
+  return TG_OK;
+}
+
+void knn_sqnorm_launch(const void* x, int64_t rows, int d, int dtype, float* out, hipStream_t s) {
+  if (dtype == TG_F32) {
+    hipLaunchKernelGGL(knn_sqnorm_f32_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (const float*)x, out, rows, d);
+    return;
+  }
+  const int vec = d % 8 == 0 && tg_aligned16(x) ? 1 : 0;
+  const dim3 grid((unsigned)((rows + 127) / 128));
+  if (dtype == TG_F16)
+    hipLaunchKernelGGL(knn_sqnorm_mfma_kernel<true>, grid, dim3(256), 0, s, (const bf16*)x, out, (int)rows, d, vec);
+  else
+    hipLaunchKernelGGL(knn_sqnorm_mfma_kernel<false>, grid, dim3(256), 0, s, (const bf16*)x, out, (int)rows, d, vec);
+}
+
 }  // namespace
 
 extern "C" {
@@ -400,6 +750,80 @@ int tg_dot(const void* a, const void* b, float* out, float* ws, int64_t numel, i
   });
   hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, nparts, out);
   TG_LAUNCH_CHECK("tg_dot");
+  return TG_OK;
+}
+
+// ---- include/twingan_hip_knn.h ---------------------------------------------------------------------------------------------
+int tg_knn_sqnorm(const void* x, int64_t rows, int d, int dtype, float* out_f32, void* stream) {
+  TG_CHECK(x && out_f32, TG_EINVAL, "tg_knn_sqnorm: NULL pointer");
+  TG_CHECK(rows >= 1 && rows <= KNN_MAX_ROWS && d >= 1 && d <= (1 << 30), TG_EINVAL, "tg_knn_sqnorm: rows = %lld, d = %d",
+           (long long)rows, d);
+  TG_CHECK(dtype == TG_F32 || dtype == TG_BF16 || dtype == TG_F16, TG_EINVAL, "tg_knn_sqnorm: dtype %d", dtype);
+  knn_sqnorm_launch(x, rows, d, dtype, out_f32, (hipStream_t)stream);
+  TG_LAUNCH_CHECK("tg_knn_sqnorm");
+  return TG_OK;
+}
+
+int tg_knn_plan(int64_t q, int64_t n, int d, int k, int* splits) {
+  TG_CHECK(splits, TG_EINVAL, "tg_knn_plan: splits is NULL");
+  int tiles = 0;
+  return knn_plan(q, n, d, k, splits, &tiles);
+}
+
+size_t tg_knn_workspace_bytes(int64_t q, int64_t n, int d, int k) {
+  int splits = 0, tiles = 0;
+  if (knn_plan(q, n, d, k, &splits, &tiles) != TG_OK) return 0;
+  return 4 * (2 * (size_t)splits * (size_t)q * (size_t)k + (size_t)q + (size_t)n);
+}
+
+int tg_knn_topk(const void* queries, int64_t q, const void* gallery, int64_t n, int d, int dtype, int metric, int k,
+                int64_t index_offset, const int64_t* query_ids, float* dist, int64_t* idx, void* ws, size_t ws_bytes,
+                void* stream) {
+  TG_CHECK(queries && gallery && dist && idx && ws, TG_EINVAL, "tg_knn_topk: NULL pointer");
+  TG_CHECK(dtype == TG_F32 || dtype == TG_BF16 || dtype == TG_F16, TG_EINVAL, "tg_knn_topk: dtype %d", dtype);
+  TG_CHECK(metric == TG_KNN_L2 || metric == TG_KNN_COSINE, TG_EINVAL, "tg_knn_topk: metric %d", metric);
+  TG_CHECK(index_offset >= 0, TG_EINVAL, "tg_knn_topk: index_offset %lld < 0", (long long)index_offset);
+  KnnGeom g;
+  const int rc = knn_plan(q, n, d, k, &g.splits, &g.tiles);
+  if (rc != TG_OK) return rc;
+  const size_t parts = (size_t)g.splits * (size_t)q * (size_t)k;
+  TG_CHECK((reinterpret_cast<uintptr_t>(ws) & 3u) == 0, TG_EINVAL, "tg_knn_topk: workspace not 4-byte aligned");
+  TG_CHECK(ws_bytes >= 4 * (2 * parts + (size_t)q + (size_t)n), TG_EINVAL, "tg_knn_topk: workspace of %zu bytes, %zu needed", ws_bytes,
+           4 * (2 * parts + (size_t)q + (size_t)n));
+  g.q = (int)q; g.n = (int)n; g.d = d; g.k = k; g.metric = metric;
+  g.index_offset = index_offset;
+  g.query_ids = query_ids;
+  g.part_i = reinterpret_cast<int*>(ws);
+  g.part_d = reinterpret_cast<float*>(ws) + parts;
+  float* qn = g.part_d + parts;
+  float* gn = qn + q;
+  g.qn = qn;
+  g.gn = gn;
+  g.vec = (d % 8 == 0 && tg_aligned16(queries) && tg_aligned16(gallery)) ? 1 : 0;
+  hipStream_t s = (hipStream_t)stream;
+  knn_sqnorm_launch(queries, q, d, dtype, qn, s);
+  const int qb = q <= 32 ? 1 : q <= 64 ? 2 : 4;      // query tile of 32, 64 or 128: no MFMA rows for queries that are not there
+  if (dtype == TG_F32 || qb == 4) knn_sqnorm_launch(gallery, n, d, dtype, gn, s);      // else the tile kernel takes them itself
+  if (dtype == TG_F32) {
+    hipLaunchKernelGGL(knn_valu_kernel<float>, dim3((unsigned)((q + 7) / 8), g.splits), dim3(256), 0, s, (const float*)queries,
+                       (const float*)gallery, g);
+  } else {
+    const dim3 grid((unsigned)((q + 32 * qb - 1) / (32 * qb)), g.splits);
+    tg_note_kernel("knn_mfma_kernel<%d>", qb);
+#define TG_KNN_LAUNCH(QB_)                                                                                                  \
+  do {                                                                                                                    \
+    if (dtype == TG_F16)                                                                                                  \
+      hipLaunchKernelGGL((knn_mfma_kernel<QB_, true>), grid, dim3(256), 0, s, (const bf16*)queries, (const bf16*)gallery, g);  \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((knn_mfma_kernel<QB_, false>), grid, dim3(256), 0, s, (const bf16*)queries, (const bf16*)gallery, g); \
+  } while (0)
+    if (qb == 1) TG_KNN_LAUNCH(1);
+    else if (qb == 2) TG_KNN_LAUNCH(2);
+    else TG_KNN_LAUNCH(4);
+#undef TG_KNN_LAUNCH
+  }
+  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((q + 63) / 64)), dim3(64), 0, s, g, dist, idx);
+  TG_LAUNCH_CHECK("tg_knn_topk");
   return TG_OK;
 }
 

@@ -3298,3 +3298,71 @@ def image_grid(batches, rows, cols, out=None):
   call('tg_image_grid_u8', _p(tab), len(ts), int(rows), int(cols), h, w, _p(out), _stream(),
        work=('image_grid', 0, sum(t.numel() * t.element_size() for t in ts) + out.numel()))
   return out      # the table was allocated on this stream: its memory is not reused before the launch has read it
+
+
+# ------------------------------------------------------------------------------------------------
+# nearest-neighbour search over embeddings (include/twingan_hip_knn.h)
+# ------------------------------------------------------------------------------------------------
+KNN_MAX_K = _lib.KNN_MAX_K
+
+
+def _knn_rows(t, name):
+  _chk(t)
+  if t.dim() != 2:
+    raise _lib.TgError('%s: a [rows, d] matrix is needed, got %s' % (name, tuple(t.shape)))
+  return int(t.shape[0]), int(t.shape[1])
+
+
+def row_sqnorm(x):
+  """fp32 [rows]: the squared L2 norm of every row of the [rows, d] matrix ``x`` (fp32 / bf16 / fp16), summed in fp32 in a
+  fixed order (tg_knn_sqnorm).  No synchronisation."""
+  rows, d = _knn_rows(x, 'row_sqnorm')
+  out = torch.empty(rows, dtype=torch.float32, device=x.device)
+  call('tg_knn_sqnorm', _p(x), rows, d, _dt(x), _p(out), _stream(), work=('knn_sqnorm', 2 * rows * d, x.numel() * x.element_size()))
+  return out
+
+
+def knn_plan(q, n, d, k):
+  """-> (gallery splits, workspace bytes) of a knn_topk launch of q queries against a chunk of n rows (tg_knn_plan,
+  tg_knn_workspace_bytes: the one place the split rule lives)."""
+  splits = ctypes.c_int(0)
+  call('tg_knn_plan', int(q), int(n), int(d), int(k), ctypes.byref(splits))
+  return splits.value, int(_lib.load().tg_knn_workspace_bytes(int(q), int(n), int(d), int(k)))
+
+
+def knn_table(q, k, device):
+  """A fresh result table: (dist fp32 [q, k] = +inf, idx int64 [q, k] = -1)."""
+  return (torch.full((q, k), float('inf'), dtype=torch.float32, device=device),
+          torch.full((q, k), -1, dtype=torch.int64, device=device))
+
+
+def knn_topk(queries, gallery, k, metric='l2', out=None, index_offset=0, query_ids=None):
+  """The k nearest rows of ``gallery`` [n, d] for every row of ``queries`` [q, d] (one dtype: fp32 / bf16 / fp16), exactly:
+  -> (dist fp32 [q, k], idx int64 [q, k]), ascending by (distance, index).  ``metric``: 'l2' (squared) or 'cosine' (distance).
+  ``out`` = (dist, idx) of an earlier call continues a running table: gallery rows are numbered from ``index_offset``, and
+  the table then holds the k best of everything fed so far, bit-identical however the gallery was cut.  ``query_ids`` int64
+  [q]: the gallery row with that index is skipped for that query.  Unfilled slots are +inf / -1.  tg_knn_topk; no
+  synchronisation."""
+  q, d = _knn_rows(queries, 'knn_topk')
+  n, dg = _knn_rows(gallery, 'knn_topk')
+  if dg != d or gallery.dtype != queries.dtype:
+    raise _lib.TgError('knn_topk: queries are %s [., %d], the gallery %s [., %d]' % (queries.dtype, d, gallery.dtype, dg))
+  if metric not in _lib.KNN_METRICS:
+    raise _lib.TgError('knn_topk: metric %r is not one of %s' % (metric, sorted(_lib.KNN_METRICS)))
+  if query_ids is not None:
+    _chk(query_ids)
+    if query_ids.dtype != torch.int64 or tuple(query_ids.shape) != (q,):
+      raise _lib.TgError('knn_topk: query_ids must be int64 [%d]' % q)
+  _, ws_bytes = knn_plan(q, n, d, k)      # refuses k, d, q, n out of range
+  if out is None:
+    dist, idx = knn_table(q, k, queries.device)
+  else:
+    dist, idx = out
+    _chk(dist, idx)
+    if dist.dtype != torch.float32 or idx.dtype != torch.int64 or tuple(dist.shape) != (q, k) or tuple(idx.shape) != (q, k):
+      raise _lib.TgError('knn_topk: out must be (fp32 [%d, %d], int64 [%d, %d])' % (q, k, q, k))
+  ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=queries.device)
+  call('tg_knn_topk', _p(queries), q, _p(gallery), n, d, _dt(queries), _lib.KNN_METRICS[metric], int(k), int(index_offset),
+       _p(query_ids), _p(dist), _p(idx), _p(ws), ws_bytes, _stream(),
+       work=('knn_topk:%dx%dx%d' % (q, n, d), 2 * q * n * d, (q + n) * d * queries.element_size()))
+  return dist, idx      # the workspace was allocated on this stream: its memory is not reused before the launches have run
