@@ -1,5 +1,5 @@
-/* The reference's --optimizer choices besides Adam as fused apply kernels (twingan_amd/csrc/reduce.hip), same library and
- * conventions as twingan_hip.h: int-returning entry points, TG_OK or a TG_E* code with the text in tg_last_error(), every
+/* The reference's --optimizer choices besides Adam as further rules of Adam's fused apply kernel (apply_kernel<RULE, VEC, EMA>,
+ * twingan_amd/csrc/reduce.hip; Adam's entry points tg_adam_* are in twingan_hip.h), same library and conventions as twingan_hip.h: int-returning entry points, TG_OK or a TG_E* code with the text in tg_last_error(), every
  * launch enqueued on `stream` without host synchronisation. */
 #ifndef TWINGAN_HIP_OPTIM_H_
 #define TWINGAN_HIP_OPTIM_H_

@@ -399,7 +399,7 @@ def gp_penalty_bounds(ss, L, lam):
 
 # ------------------------------------------------------------------------------------------------ Adam
 def adam_step_bounds(th, g, m, v, lr_t, b1, b2, eps, gscale):
-  """One step of apply_kernel (csrc/reduce.hip) in float64 from the fp32 state it READS (the previous step's stored theta, m,
+  """One step of apply_kernel's Adam rule (adam_element, csrc/reduce.hip) in float64 from the fp32 state it READS (the previous step's stored theta, m,
   v: inputs of this launch, not its output), with the fp32 scalars it is given, and the error of every fp32 operation on
   the way.  Each operation counts 2^-24 of its result (the compiler may contract a multiply into the following add, which
   only removes a rounding); sqrtf and the division are not required to be correctly rounded: one unit in the last place

@@ -1,4 +1,4 @@
-"""float64 one-step references of the --optimizer rules (include/twingan_hip_optim.h, csrc/reduce.hip optim_kernel) and the
+"""float64 one-step references of the --optimizer rules (include/twingan_hip_optim.h, csrc/reduce.hip apply_kernel) and the
 error bounds of one fp32 launch.  TEST INFRASTRUCTURE.
 
 The rules restate TF 1.8's dense kernels (core/kernels/training_ops.cc).  sgd, momentum and adadelta coincide with

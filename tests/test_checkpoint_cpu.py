@@ -133,8 +133,8 @@ def test_save_and_warm_start_follow_the_reference_rules(tmp_path):
   small = Trainer(Config(hw=4, max_ch=8, precision='fp32'), device='cpu', seed=1)
   small.global_step, small.adam_t = 11, 22
   with torch.no_grad():
-    small.store.m['g'].fill_(0.5)
-    small.store.v['d'].fill_(0.25)
+    small.store.slots['g'][0].fill_(0.5)
+    small.store.slots['d'][1].fill_(0.25)
   d4 = str(tmp_path / '4')
   path = C.save(small, d4)
   assert path.endswith('model.ckpt-11') and C.latest_checkpoint(d4) == path
@@ -161,7 +161,7 @@ def test_save_and_warm_start_follow_the_reference_rules(tmp_path):
       assert torch.equal(after[k], sd[k])
     else:
       assert torch.equal(after[k], fresh[k])
-  assert float(grown.store.m['g'].abs().max()) == 0                    # optimiser slots are not model variables
+  assert float(grown.store.slots['g'][0].abs().max()) == 0                   # optimiser slots are not model variables
   # excluded scopes keep their fresh values
   again = Trainer(Config(hw=8, max_ch=8, precision='fp32', is_growing=True), device='cpu', seed=2)
   got = C.init_from_checkpoint(again, path, checkpoint_exclude_scopes='discriminator_s, generator', ignore_missing_vars=True)
@@ -172,6 +172,70 @@ def test_save_and_warm_start_follow_the_reference_rules(tmp_path):
   assert C.init_from_checkpoint(third, d4, ignore_missing_vars=True, train_dir=str(tmp_path / '4to8')) == []
   for tr in (small, grown, again, third):
     tr.close()
+
+
+def test_adam_moments_are_slots_like_any_other_rules(tmp_path):
+  """ParamStore.slots[g] = [m, v] under Adam: slot_dict() is exactly {<var>/Adam, <var>/Adam_1} per variable in logical (TF)
+  shape -- the physically padded discriminator tail conv included --, load_slot_dict inverts it bit for bit, and restoring a
+  file of model variables only into an Adam trainer leaves both moments zero and raises nothing."""
+  from twingan_amd import Config
+  from twingan_amd.twingan import Trainer
+  a = Trainer(Config(hw=4, max_ch=8, precision='fp32'), device='cpu', seed=1)
+  st = a.store
+  assert all(len(st.slots[g]) == 2 and all(t.shape == st.flat[g].shape for t in st.slots[g]) for g in st.GROUPS)
+  with torch.no_grad():
+    for g in st.GROUPS:
+      n = st.flat[g].numel()
+      st.slots[g][0].copy_(torch.arange(n, dtype=torch.float32) + 0.5)         # distinct everywhere, and m != v
+      st.slots[g][1].copy_(-(torch.arange(n, dtype=torch.float32) + 0.25))
+  sd = st.slot_dict()
+  assert set(sd) == {k + s for k in st.specs for s in ('/Adam', '/Adam_1')}
+  padded = [k for k, s in st.specs.items() if s['phys'] != s['shape']]
+  assert padded and all(k.startswith('discriminator_') for k in padded)
+  for k, s in st.specs.items():
+    off, n = st.offsets[k], int(np.prod(s['phys']))
+    for i, slot in enumerate(('/Adam', '/Adam_1')):
+      assert tuple(sd[k + slot].shape) == s['shape'], k
+      phys = st.slots[s['group']][i][off:off + n].view(s['phys'])
+      assert torch.equal(sd[k + slot], phys[tuple(slice(0, d) for d in s['shape'])]), k
+  b = Trainer(Config(hw=4, max_ch=8, precision='fp32'), device='cpu', seed=2)
+  b.store.load_slot_dict(sd)
+  back = b.store.slot_dict()
+  assert set(back) == set(sd) and all(torch.equal(back[k], v) for k, v in sd.items())
+  for k in padded:      # what lies outside the logical shape is not the file's to set: it stays zero
+    s = st.specs[k]
+    off, n = st.offsets[k], int(np.prod(s['phys']))
+    for i in range(2):
+      rest = b.store.slots[s['group']][i][off:off + n].view(s['phys']).clone()
+      rest[tuple(slice(0, d) for d in s['shape'])] = 0
+      assert float(rest.abs().max()) == 0, k
+  # a file of model variables only (a TF stage's weights, no optimiser state)
+  arrays = {k: v.numpy() for k, v in st.state_dict(include_state=True).items()}
+  C.write_checkpoint(str(tmp_path / 'vars.ckpt-0'), arrays)
+  c = Trainer(Config(hw=4, max_ch=8, precision='fp32'), device='cpu', seed=3)
+  C.restore(c, str(tmp_path / 'vars.ckpt-0'))
+  assert all(float(t.abs().max()) == 0 for g in c.store.GROUPS for t in c.store.slots[g])
+  assert all(torch.equal(v, st.state_dict()[k]) for k, v in c.store.state_dict().items())
+  for t in (a, b, c):
+    t.close()
+
+
+@pytest.mark.parametrize('optimizer', ['adadelta', 'adagrad', 'adam', 'ftrl', 'momentum', 'rmsprop', 'sgd'])
+def test_save_writes_the_keys_its_docstring_lists(tmp_path, optimizer):
+  """The key set of a saved checkpoint, per optimiser, spelt out here from checkpoint.save's docstring (not from
+  params.OPTIM_SLOTS): the variables and state, the rule's slots of every variable, global_step and the two counters; the beta
+  powers under Adam alone."""
+  from twingan_amd import Config
+  from twingan_amd.twingan import Trainer
+  listed = {'adam': ('Adam', 'Adam_1'), 'momentum': ('Momentum',), 'adagrad': ('Adagrad',), 'rmsprop': ('RMSProp', 'RMSProp_1'),
+            'adadelta': ('Adadelta', 'Adadelta_1'), 'ftrl': ('Ftrl', 'Ftrl_1'), 'sgd': ()}
+  tr = Trainer(Config(hw=4, max_ch=8, precision='fp32', optimizer=optimizer), device='cpu', seed=1)
+  got = {n for n, _, _ in C.list_variables(C.save(tr, str(tmp_path / optimizer)))}
+  want = set(tr.store.state_dict(include_state=True)) | {k + '/' + s for k in tr.store.specs for s in listed[optimizer]}
+  want |= {'global_step', 'n_critic_counter'} | ({C.RNG_DRAWS_KEY} if getattr(tr, '_rng_state', None) is not None else set())
+  want |= {'beta1_power', 'beta2_power'} if optimizer == 'adam' else set()
+  assert got == want, (sorted(got - want), sorted(want - got))
+  tr.close()
 
 
 def test_run_progressive_directory_protocol(tmp_path):

@@ -707,7 +707,7 @@ def test_multi_pack_refresh_stays_inside_its_tensors(dname):
 @pytest.mark.parametrize('skip', [0, 1], ids=['applied', 'skipped'])
 @pytest.mark.parametrize('numel', [1, 3, 5, 4099])
 def test_guarded_applies_and_the_loss_scale_state_stay_inside_their_tensors(numel, skip):
-  """tg_nonfinite_check, tg_loss_scale_tick, tg_adam_step_guarded and tg_adam_ema_step_guarded as Trainer._adam issues
+  """tg_nonfinite_check, tg_loss_scale_tick, tg_adam_step_guarded and tg_adam_ema_step_guarded as Trainer._apply issues
   them (the trainer calls the library on its own flat buffers: there is no wrapper that allocates).  The 32-byte state, the
   step counter and the rate sit between NaN bands like every other operand."""
   import ctypes

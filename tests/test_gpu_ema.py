@@ -339,7 +339,7 @@ def test_averaging_does_not_disturb_training():
   b = Trainer(_cfg(generator_norm_type='batch_norm'), device=DEV, seed=4)
   assert b.cfg.moving_average_decay is None and not b.store.averaged and b.store.avg == {} and b.store.state_avg == {}
   assert not hasattr(b, '_ema_w_dev')
-  assert set(a.store.avg) == {'g', 'd'} and all(a.store.avg[g].shape == a.store.m[g].shape for g in 'gd')
+  assert set(a.store.avg) == {'g', 'd'} and all(a.store.avg[g].shape == a.store.slots[g][0].shape for g in 'gd')
   for _ in range(5):
     a.run(s, t)
     b.run(s, t)

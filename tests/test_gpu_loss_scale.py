@@ -379,7 +379,7 @@ def _batch():
 def _tensors(tr):
   """Bit copies of everything the optimiser owns, per group, and both loss-scale states."""
   s = tr.store
-  out = {'%s/%s' % (k, g): getattr(s, k)[g].clone() for g in s.GROUPS for k in ('flat', 'm', 'v')}
+  out = {'%s/%s' % (k, g): t.clone() for g in s.GROUPS for k, t in zip(('flat', 'm', 'v'), [s.flat[g]] + s.slots[g])}
   out.update({'ls/' + g: t.clone() for g, t in tr._ls.items()})
   out['step'], out['lr'] = tr._adam_step_dev.clone(), tr._lr_t_dev.clone()
   return out
@@ -513,7 +513,7 @@ def _quiet(graph):
         tr.run(s, t)
       assert not graph or tr.graph_fallback_reason is None, tr.graph_fallback_reason
       sd = {k: v.clone() for k, v in tr.store.state_dict(include_state=True).items()}
-      sd.update({'%s/%s' % (k, g): getattr(tr.store, k)[g].clone() for g in 'gd' for k in ('m', 'v')})
+      sd.update({'%s/%s' % (k, g): t.clone() for g in 'gd' for k, t in zip(('m', 'v'), tr.store.slots[g])})
       out.append((sd, tr.loss_scale_state() if kw else None))
       tr.close()
   (dyn, state), (stat, _) = out

@@ -364,7 +364,7 @@ def test_graph_replay_matches_eager_steps(norm):
   den = sum(float((sa[k].double() ** 2).sum()) for k in sa)
   assert (num / den) ** 0.5 < 5e-3, (num / den) ** 0.5      # Adam's sign-like first steps amplify atomics-order noise
   for grp in ('g', 'd'):           # Adam moments: the warm-up steps must not have entered them
-    ma, mb = a.store.m[grp], b.store.m[grp]
+    ma, mb = a.store.slots[grp][0], b.store.slots[grp][0]
     assert float((ma - mb).norm() / (ma.norm() + 1e-30)) < 5e-2
   if norm == 'batch_norm':
     k = 'generator/block_4x4x16/Conv/BatchNorm/moving_mean_s'
@@ -1534,12 +1534,12 @@ def test_fp32_path_is_bit_reproducible(norm):
     for s, t, a_s, a_t in data:
       tr.run(s.cuda(), t.cuda(), a_s.cuda(), a_t.cuda())
     torch.cuda.synchronize()
-    ends.append((tr.store.state_dict(include_state=True), {k: (m, v) for k, (m, v) in tr.store.adam_dict().items()}))
+    ends.append((tr.store.state_dict(include_state=True), tr.store.slot_dict()))
     tr.close()
   (pa, sa), (pb, sb) = ends
   bad = [k for k in pa if not torch.equal(pa[k], pb[k])]
   assert not bad, (len(bad), bad[:5])
-  bad = [k for k in sa if not (torch.equal(sa[k][0], sb[k][0]) and torch.equal(sa[k][1], sb[k][1]))]
+  bad = [k for k in sa if not torch.equal(sa[k], sb[k])]      # <var>/Adam and <var>/Adam_1 of every variable
   assert not bad, (len(bad), bad[:5])
 
 

@@ -405,8 +405,8 @@ def _train(cfg, use_graph, monitor_dir):
     torch.cuda.synchronize()
     st = tr.store
     out = {'flat/' + g: st.flat[g].clone() for g in st.GROUPS}
-    out.update({'m/' + g: st.m[g].clone() for g in st.GROUPS})
-    out.update({'v/' + g: st.v[g].clone() for g in st.GROUPS})
+    out.update({'m/' + g: st.slots[g][0].clone() for g in st.GROUPS})
+    out.update({'v/' + g: st.slots[g][1].clone() for g in st.GROUPS})
     out.update({'grad/' + g: st.grad[g].clone() for g in st.GROUPS})
     out.update({'state/' + k: v.clone() for k, v in st.state.items()})
     out['draws'] = tr._rng_state.clone()

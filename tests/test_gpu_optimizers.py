@@ -312,7 +312,7 @@ def _owned(tr, group):
 def _everything(tr):
   s = tr.store
   out = {'flat/' + g: s.flat[g].detach().clone() for g in s.GROUPS}
-  out.update({'slot%d/%s' % (i, g): t.clone() for g in s.GROUPS for i, t in enumerate(s.slots.get(g, ()))})
+  out.update({'slot%d/%s' % (i, g): t.clone() for g in s.GROUPS for i, t in enumerate(s.slots[g])})
   out.update({'avg/' + g: t.clone() for g, t in s.avg.items()})
   return out
 
@@ -336,7 +336,7 @@ def test_trainer_applies_match_float64(rule):
   from twingan_amd.twingan import Trainer
   tr = Trainer(_cfg(optimizer=rule), device=DEV, seed=3)
   st = tr.store
-  assert all(t.numel() == 0 for t in list(st.m.values()) + list(st.v.values()))
+  assert not hasattr(st, 'm') and not hasattr(st, 'v')      # no Adam moments beside the rule's own slots
   for g in st.GROUPS:
     assert len(st.slots[g]) == len(R.SLOT_NAMES[rule])
     for t, want in zip(st.slots[g], R.slot_init(rule, 1)):
@@ -357,6 +357,31 @@ def test_trainer_applies_match_float64(rule):
     assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(rest, _owned(tr, other))), 'run %d touched the other group' % i
   assert (tr.adam_t, tr.n_critic_counter, tr.global_step) == (4, 4, 2) and int(tr._adam_step_dev.item()) == 4
   print('trainer %s: worst error / bound %.3f' % (rule, worst))
+  tr.close()
+
+
+def test_trainer_adam_moments_are_slots_and_snapshot_restores_them():
+  """optimizer='adam': after two runs slots[g] is [m, v], two buffers of flat[g]'s shape with v >= 0 everywhere and both groups'
+  moments moved; _snapshot -> one more run -> _restore leaves every buffer as it was before that run, bit for bit."""
+  from twingan_amd.twingan import Trainer
+  tr = Trainer(_cfg(optimizer='adam', moving_average_decay=0.999), device=DEV, seed=3)
+  st = tr.store
+  s, t = _batch()
+  tr.run(s, t)
+  tr.run(s, t)
+  for g in st.GROUPS:
+    assert len(st.slots[g]) == 2 and all(x.shape == st.flat[g].shape and x.dtype == torch.float32 for x in st.slots[g])
+    assert bool((st.slots[g][1] >= 0).all()) and float(st.slots[g][1].max()) > 0 and float(st.slots[g][0].abs().max()) > 0
+  before = _everything(tr)
+  counters = (tr.adam_t, tr.n_critic_counter, tr.global_step, int(tr._adam_step_dev.item()))
+  snap = tr._snapshot()
+  tr.run(s, t)
+  moved = _differing(before, _everything(tr))
+  assert {'flat/g', 'slot0/g', 'slot1/g', 'avg/g'} <= set(moved), moved
+  tr._restore(snap)
+  bad = _differing(before, _everything(tr))
+  assert not bad, bad
+  assert (tr.adam_t, tr.n_critic_counter, tr.global_step, int(tr._adam_step_dev.item())) == counters == (2, 2, 1, 2)
   tr.close()
 
 

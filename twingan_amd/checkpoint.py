@@ -470,8 +470,8 @@ def variables_to_restore(names, moving_average):
 
 def save(trainer, train_dir, global_step=None, max_to_keep=5):
   """What the reference's Saver leaves for a stage: every model variable (TF names, TF layouts), the non-trainable
-  state (moving / renorm statistics, spectral-norm u), ``global_step``, and the shared Adam optimiser's slots
-  (``<var>/Adam``, ``<var>/Adam_1``, ``beta1_power``, ``beta2_power``) -> <train_dir>/model.ckpt-<step> + checkpoint
+  state (moving / renorm statistics, spectral-norm u), ``global_step``, and the shared Adam optimiser's slots and beta powers
+  (``<var>/Adam``, ``<var>/Adam_1``; ``beta1_power``, ``beta2_power``) -> <train_dir>/model.ckpt-<step> + checkpoint
   (the ``max_to_keep`` most recent ones are retained).  Under --moving_average_decay (Config.moving_average_decay) also the
   shadow ``<var>/ExponentialMovingAverage`` of every model variable; without it the key set is unchanged.  Under
   Config.dynamic_loss_scale also each group's loss-scale state and the applies made (LOSS_SCALE_PREFIX, ADAM_APPLIES_KEY;
@@ -481,13 +481,8 @@ def save(trainer, train_dir, global_step=None, max_to_keep=5):
   store = trainer.store
   step = int(trainer.global_step if global_step is None else global_step)
   tensors = {k: v.detach().float().cpu().numpy() for k, v in store.state_dict(include_state=True).items()}
-  adam = store.optimizer == 'adam'
-  if adam:
-    for k, (m, v) in store.adam_dict().items():
-      tensors[k + '/Adam'] = m.detach().float().cpu().numpy()
-      tensors[k + '/Adam_1'] = v.detach().float().cpu().numpy()
-  else:      # --optimizer: the rule's own slot names (params.OPTIM_SLOTS), no beta powers
-    tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.slot_dict().items()})
+  # --optimizer: the rule's own slot names (params.OPTIM_SLOTS)
+  tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.slot_dict().items()})
   if store.averaged:
     tensors.update({k: v.detach().float().cpu().numpy() for k, v in store.averages_dict().items()})
   t = int(trainer.adam_t)
@@ -499,7 +494,7 @@ def save(trainer, train_dir, global_step=None, max_to_keep=5):
       tensors[LOSS_SCALE_PREFIX + g + '/scale'] = np.float32(st['scale'])
       tensors[LOSS_SCALE_PREFIX + g + '/good_steps'] = np.int32(st['good_steps'])
       tensors[LOSS_SCALE_PREFIX + g + '/skipped'] = np.int64(st['skipped'])
-  if adam:
+  if store.optimizer == 'adam':      # non-slot variables of tf.train.AdamOptimizer alone
     tensors['beta1_power'] = np.float32(trainer.cfg.adam_beta1 ** (t + 1))       # TF keeps beta^(t+1) after t applies
     tensors['beta2_power'] = np.float32(trainer.cfg.adam_beta2 ** (t + 1))
   tensors['global_step'] = np.int64(step)
@@ -601,12 +596,11 @@ def restore(trainer, prefix):
   if store.averaged:
     store.load_averages_dict({k: torch.from_numpy(arrays[k].astype(np.float32)) for k in shadows})
   _check_optimizer(prefix, arrays, store)
-  if store.optimizer == 'adam':
-    slots = {k: (arrays[k + '/Adam'], arrays[k + '/Adam_1']) for k in store.specs if k + '/Adam' in arrays}
-    store.load_adam_dict(slots)
-  else:
-    from .params import OPTIM_SLOTS
-    store.load_slot_dict({k + '/' + slot: arrays[k + '/' + slot] for k in store.specs for slot, _ in OPTIM_SLOTS[store.optimizer]})
+  from .params import OPTIM_SLOTS
+  keys = [k + '/' + slot for k in store.specs for slot, _ in OPTIM_SLOTS[store.optimizer]]
+  if store.optimizer == 'adam':      # the slots the file has: one of model variables only leaves the moments zero
+    keys = [k for k in keys if k in arrays]
+  store.load_slot_dict({k: arrays[k] for k in keys})      # KeyError where another rule's file lacks a slot
   if 'global_step' in arrays:
     trainer.global_step = int(arrays['global_step'])
     trainer.n_critic_counter = trainer.global_step * trainer.cfg.n_critic

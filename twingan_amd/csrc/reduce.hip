@@ -747,10 +747,8 @@ __global__ void small_gemm_wave_kernel(const float* __restrict__ a, const float*
 // TF-1.x Adam (model/model_inheritor.py:537-542): epsilon OUTSIDE the bias-corrected sqrt.  One element, shared by
 // both loops of apply_kernel so that every instantiation writes the same bits: the two multiply-adds are spelled as the fused
 // operations the compiler's contraction made of `b1 * m + (1 - b1) * g` and `b2 * v + (1 - b2) * g * g`, so their
-// rounding does not depend on the loop they are inlined into.
-__device__ __forceinline__ float adam_element(float th, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
-                                              float gscale) {
-  const float gi = g * gscale;
+// rounding does not depend on the loop they are inlined into.  gi = g * gscale, formed by the caller.
+__device__ __forceinline__ float adam_element(float th, float gi, float& m, float& v, float lr_t, float b1, float b2, float eps) {
   const float mi = fmaf(b1, m, (1.f - b1) * gi);
   const float vi = fmaf(b2, v, (1.f - b2) * gi * gi);
   m = mi;
@@ -791,76 +789,9 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ avg, const
   ema_span<VEC>(avg, var, numel, w_dev[0], (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-// What the four optimiser entry points (tg_adam_step, tg_adam_ema_step and their _guarded forms) hand to apply_kernel: what all
-// of them have, then what only some have.
-struct ApplyArgs {
-  float* th;
-  const float* g;
-  float *m, *v;
-  int64_t numel;
-  float b1, b2, eps;
-  const float* lr_t_dev = nullptr;           // the rate; null: lr_t
-  float lr_t = 0.f;
-  float gscale = 0.f;                        // multiplies g first, without ls
-  const TgLossScaleState* ls = nullptr;      // the guard: the gradient scale is its inv_scale, its skip decides
-  float* avg = nullptr;                      // the fused forms (EMA instantiations)
-  const float* w_dev = nullptr;
-  bf16* shadow = nullptr;                    // tg_adam_step's rounded copy of theta (the instantiation without EMA)
-};
-
-// The Adam apply of one group's flat buffers, 28 bytes per element (read theta, g, m, v; write theta, m, v).  EMA: the moving
-// average of the parameters it just wrote in the same pass, 36 bytes per element against 28 + 12 for the apply followed by
-// ema_kernel.  VEC as for ema_span, over all five pointers.  ls (dynamic loss scaling, below): the gradient scale is the
-// state's inv_scale, and a skipped apply stores nothing -- but for the average, which is then ema_span over the unchanged
-// theta (12 bytes per element): every run updates every average.
-template <bool VEC, bool EMA>
-__global__ __launch_bounds__(256) void apply_kernel(const ApplyArgs a) {
-  static_assert(EMA || !VEC, "the 16-byte loop is the fused one: it has the average and no bf16 shadow");
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  if (a.ls && a.ls->skip) {
-    if constexpr (EMA) ema_span<VEC>(a.avg, a.th, a.numel, a.w_dev[0], tid, nthr);
-    return;
-  }
-  const float lr_t = a.lr_t_dev ? a.lr_t_dev[0] : a.lr_t, gscale = a.ls ? a.ls->inv_scale : a.gscale;
-  float w = 0.f;
-  if constexpr (EMA) w = a.w_dev[0];
-  int64_t done = 0;
-  if constexpr (VEC) {
-    const int64_t nvec = a.numel >> 2;
-    for (int64_t i = tid; i < nvec; i += nthr) {
-      Vec16<float> t4 = ldv(a.th + 4 * i), m4 = ldv(a.m + 4 * i), v4 = ldv(a.v + 4 * i), a4 = ldv(a.avg + 4 * i);
-      const Vec16<float> g4 = ldv(a.g + 4 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float mi = m4.v[e], vi = v4.v[e];
-        const float t = adam_element(t4.v[e], g4.v[e], mi, vi, lr_t, a.b1, a.b2, a.eps, gscale);
-        m4.v[e] = mi;
-        v4.v[e] = vi;
-        t4.v[e] = t;
-        a4.v[e] = ema_element(a4.v[e], t, w);
-      }
-      stv(a.m + 4 * i, m4);
-      stv(a.v + 4 * i, v4);
-      stv(a.th + 4 * i, t4);
-      stv(a.avg + 4 * i, a4);
-    }
-    done = nvec << 2;
-  }
-  for (int64_t i = done + tid; i < a.numel; i += nthr) {
-    float mi = a.m[i], vi = a.v[i], ai = 0.f;
-    if constexpr (EMA) ai = a.avg[i];      // with the other loads: behind a store it would wait for the whole update
-    const float t = adam_element(a.th[i], a.g[i], mi, vi, lr_t, a.b1, a.b2, a.eps, gscale);
-    a.m[i] = mi;
-    a.v[i] = vi;
-    a.th[i] = t;
-    if constexpr (EMA) a.avg[i] = ema_element(ai, t, w);
-    else if (a.shadow) a.shadow[i] = (bf16)t;
-  }
-}
-
 // ---- the reference's other --optimizer rules (include/twingan_hip_optim.h; TF 1.8 core/kernels/training_ops.cc, the dense
 // functors).  One element each, in adam_element's style: g arrives unscaled-by-the-loss (g * gscale), every multiply that
-// feeds an add is an explicit fmaf, so the 16-byte loop and the tail loop of optim_kernel write the same bits, and so do the
+// feeds an add is an explicit fmaf, so the 16-byte loop and the tail loop of apply_kernel write the same bits, and so do the
 // fused and the unfused form; contraction is off inside them, so that the caller's g * gscale is not pulled into one of
 // their plain adds in one instantiation and left alone in another.  a, b: the rule's slots in slot0, slot1 order; a rule
 // touches only those it has.
@@ -916,37 +847,47 @@ __device__ __forceinline__ float ftrl_element(float th, float g, float& accum, f
 }
 
 constexpr int TG_OPT_FTRL_POW = TG_OPT_FTRL + 1;      // kernel-side only: ftrl with lr_power != -0.5
+constexpr int TG_OPT_ADAM = TG_OPT_FTRL + 2;          // kernel-side only: Adam has its own entry points (tg_adam_*)
 constexpr int optim_slots(int rule) {
   return rule == TG_OPT_SGD ? 0 : (rule == TG_OPT_MOMENTUM || rule == TG_OPT_ADAGRAD) ? 1 : 2;
 }
 
+// a, b: the rule's slots.  Adam: h.lr is the bias-corrected rate, its betas ride in h.momentum and h.decay_or_rho.
 template <int RULE>
-__device__ __forceinline__ float optim_element(float th, float g, float& a, float& b, const TgOptimHyper& h) {
+__device__ __forceinline__ float apply_element(float th, float g, float& a, float& b, const TgOptimHyper& h) {
   if constexpr (RULE == TG_OPT_SGD) return sgd_element(th, g, h);
   else if constexpr (RULE == TG_OPT_MOMENTUM) return momentum_element(th, g, a, h);
   else if constexpr (RULE == TG_OPT_ADAGRAD) return adagrad_element(th, g, a, h);
   else if constexpr (RULE == TG_OPT_RMSPROP) return rmsprop_element(th, g, a, b, h);
   else if constexpr (RULE == TG_OPT_ADADELTA) return adadelta_element(th, g, a, b, h);
+  else if constexpr (RULE == TG_OPT_ADAM) return adam_element(th, g, a, b, h.lr, h.momentum, h.decay_or_rho, h.eps);
   else return ftrl_element<RULE == TG_OPT_FTRL>(th, g, a, b, h);
 }
 
-// What tg_optim_step hands to optim_kernel.
-struct OptimArgs {
+// What every optimiser entry point (tg_adam_step, tg_adam_ema_step, their _guarded forms, tg_optim_step) hands to
+// apply_kernel: what all of them have, then what only some have.
+struct ApplyArgs {
   float* th;
   const float* g;
-  float *s0, *s1;                 // null where the rule has no such slot: never dereferenced then
+  float *s0, *s1;                            // null where the rule has no such slot: never dereferenced then.  Adam: m, v
   int64_t numel;
-  TgOptimHyper h;
-  float gscale;                   // multiplies g first, without ls
-  const TgLossScaleState* ls;     // the guard: the gradient scale is its inv_scale, its skip decides
-  float* avg;                     // the fused moving average (EMA instantiations)
-  const float* w_dev;
+  TgOptimHyper h;                            // Adam: {lr_t, beta1, beta2, eps}, see apply_element
+  float gscale = 0.f;                        // multiplies g first, without ls
+  const TgLossScaleState* ls = nullptr;      // the guard: the gradient scale is its inv_scale, its skip decides
+  float* avg = nullptr;                      // the fused moving average (EMA instantiations)
+  const float* w_dev = nullptr;
+  const float* lr_t_dev = nullptr;           // Adam alone: the rate on the device; null: h.lr
+  bf16* shadow = nullptr;                    // Adam alone: tg_adam_step's rounded copy of theta (the instantiation without EMA)
 };
 
-// apply_kernel's sibling for the other rules: 12 (sgd), 20 (momentum, adagrad) or 28 bytes per element, 8 more with the moving
-// average.  VEC, EMA and ls as there, but every form has its 16-byte loop (there is no bf16 shadow here).
+// The apply of one group's flat buffers under RULE: 12 (sgd), 20 (momentum, adagrad) or 28 bytes per element (read theta, g
+// and the slots; write theta and the slots).  EMA: the moving average of the parameters it just wrote in the same pass, 8
+// bytes per element more against 12 for the apply followed by ema_kernel.  VEC as for ema_span, over every pointer in use.
+// ls (dynamic loss scaling, below): the gradient scale is the state's inv_scale, and a skipped apply stores nothing -- but
+// for the average, which is then ema_span over the unchanged theta (12 bytes per element): every run updates every average.
 template <int RULE, bool VEC, bool EMA>
-__global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
+__global__ __launch_bounds__(256) void apply_kernel(const ApplyArgs a) {
+  static_assert(RULE != TG_OPT_ADAM || EMA || !VEC, "plain Adam stores its bf16 shadow in the element loop: it has no 16-byte one");
   constexpr int NS = optim_slots(RULE);
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   if (a.ls && a.ls->skip) {
@@ -954,7 +895,10 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
     return;
   }
   const float gscale = a.ls ? a.ls->inv_scale : a.gscale;
-  const TgOptimHyper h = a.h;
+  TgOptimHyper h = a.h;
+  if constexpr (RULE == TG_OPT_ADAM) {
+    if (a.lr_t_dev) h.lr = a.lr_t_dev[0];
+  }
   float w = 0.f;
   if constexpr (EMA) w = a.w_dev[0];
   int64_t done = 0;
@@ -969,7 +913,7 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pi = p4.v[e], qi = q4.v[e];
-        const float t = optim_element<RULE>(t4.v[e], g4.v[e] * gscale, pi, qi, h);
+        const float t = apply_element<RULE>(t4.v[e], g4.v[e] * gscale, pi, qi, h);
         p4.v[e] = pi;
         q4.v[e] = qi;
         t4.v[e] = t;
@@ -986,12 +930,15 @@ __global__ __launch_bounds__(256) void optim_kernel(const OptimArgs a) {
     float pi = 0.f, qi = 0.f, ai = 0.f;
     if constexpr (NS >= 1) pi = a.s0[i];
     if constexpr (NS >= 2) qi = a.s1[i];
-    if constexpr (EMA) ai = a.avg[i];      // with the other loads, as in apply_kernel
-    const float t = optim_element<RULE>(a.th[i], a.g[i] * gscale, pi, qi, h);
+    if constexpr (EMA) ai = a.avg[i];      // with the other loads: behind a store it would wait for the whole update
+    const float t = apply_element<RULE>(a.th[i], a.g[i] * gscale, pi, qi, h);
     if constexpr (NS >= 1) a.s0[i] = pi;
     if constexpr (NS >= 2) a.s1[i] = qi;
     a.th[i] = t;
     if constexpr (EMA) a.avg[i] = ema_element(ai, t, w);
+    else if constexpr (RULE == TG_OPT_ADAM) {
+      if (a.shadow) a.shadow[i] = (bf16)t;
+    }
   }
 }
 
@@ -1102,31 +1049,21 @@ __global__ void loss_scale_tick_kernel(TgLossScaleState* ls, int64_t* step, floa
   ls->seed = (float)((double)next / (double)world);
 }
 
-// The one launch of apply_kernel.  Only the fused forms (those with an average) have a 16-byte path: it is taken when all
-// five pointers are 16-byte aligned, else the apply goes element by element.  avg and shadow exclude each other: the EMA
-// instantiations store no shadow, and no entry point has both.
+// The one launch of apply_kernel, `name` the entry point's.  The 16-byte loop is taken when every pointer in use (theta, grad,
+// the rule's slots, the average when there is one) is 16-byte aligned, else the apply goes element by element.  avg and
+// shadow exclude each other: the EMA instantiations store no shadow, and no entry point has both.
+template <int RULE>
 int launch_apply(const ApplyArgs& a, void* stream, const char* name) {
+  constexpr int NS = optim_slots(RULE);
+  // plain Adam (no average) has no 16-byte instantiation: its bf16 shadow is stored in the element loop
+  constexpr bool PLAIN_VEC = RULE != TG_OPT_ADAM;
   const bool ema = a.avg != nullptr;
-  const bool vec =
-      ema && tg_aligned16(a.th) && tg_aligned16(a.g) && tg_aligned16(a.m) && tg_aligned16(a.v) && tg_aligned16(a.avg);
-  auto kernel = vec ? apply_kernel<true, true> : ema ? apply_kernel<false, true> : apply_kernel<false, false>;
+  const bool vec = (ema || PLAIN_VEC) && tg_aligned16(a.th) && tg_aligned16(a.g) && (NS < 1 || tg_aligned16(a.s0)) &&
+                   (NS < 2 || tg_aligned16(a.s1)) && (!ema || tg_aligned16(a.avg));
+  auto kernel = ema ? (vec ? apply_kernel<RULE, true, true> : apply_kernel<RULE, false, true>)
+                    : (vec ? apply_kernel<RULE, PLAIN_VEC, false> : apply_kernel<RULE, false, false>);
   hipLaunchKernelGGL(kernel, dim3(tg_grid_for(vec ? (a.numel + 3) / 4 : a.numel, 256)), dim3(256), 0, (hipStream_t)stream, a);
   TG_LAUNCH_CHECK(name);
-  return TG_OK;
-}
-
-// The one launch of optim_kernel, under launch_apply's workgroup cap.  The 16-byte loop is taken when every pointer in use
-// (theta, grad, the rule's slots, the average when there is one) is 16-byte aligned.
-template <int RULE>
-int launch_optim_rule(const OptimArgs& a, void* stream) {
-  constexpr int NS = optim_slots(RULE);
-  const bool ema = a.avg != nullptr;
-  const bool vec = tg_aligned16(a.th) && tg_aligned16(a.g) && (NS < 1 || tg_aligned16(a.s0)) && (NS < 2 || tg_aligned16(a.s1)) &&
-                   (!ema || tg_aligned16(a.avg));
-  auto kernel = vec ? (ema ? optim_kernel<RULE, true, true> : optim_kernel<RULE, true, false>)
-                    : (ema ? optim_kernel<RULE, false, true> : optim_kernel<RULE, false, false>);
-  hipLaunchKernelGGL(kernel, dim3(tg_grid_for(vec ? (a.numel + 3) / 4 : a.numel, 256)), dim3(256), 0, (hipStream_t)stream, a);
-  TG_LAUNCH_CHECK("tg_optim_step");
   return TG_OK;
 }
 
@@ -1574,17 +1511,18 @@ int tg_fc_bwd(const void* x, const float* w, const float* g, void* gx, float* gw
 int tg_adam_step(float* theta, const float* grad, float* m, float* v, void* theta_bf16, int64_t numel, float lr_t,
                  const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, void* stream) {
   TG_CHECK(theta && grad && m && v && numel > 0, TG_EINVAL, "tg_adam_step: bad arguments");
-  ApplyArgs a{theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, lr_t, grad_scale};
+  ApplyArgs a{theta, grad, m, v, numel, {lr_t, beta1, beta2, eps}, grad_scale};
+  a.lr_t_dev = lr_t_dev;
   a.shadow = (bf16*)theta_bf16;
-  return launch_apply(a, stream, "tg_adam_step");
+  return launch_apply<TG_OPT_ADAM>(a, stream, "tg_adam_step");
 }
 
 int tg_adam_ema_step(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel, const float* lr_t_dev,
                      float beta1, float beta2, float eps, float grad_scale, const float* w_dev, void* stream) {
   TG_CHECK(theta && grad && m && v && avg && lr_t_dev && w_dev, TG_EINVAL, "tg_adam_ema_step: null pointer");
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step: numel must be positive (got %lld)", (long long)numel);
-  return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, grad_scale, nullptr, avg, w_dev}, stream,
-                      "tg_adam_ema_step");
+  return launch_apply<TG_OPT_ADAM>({theta, grad, m, v, numel, {0.f, beta1, beta2, eps}, grad_scale, nullptr, avg, w_dev, lr_t_dev},
+                                   stream, "tg_adam_ema_step");
 }
 
 int tg_ema_update(float* avg, const float* var, int64_t numel, const float* w_dev, void* stream) {
@@ -1667,7 +1605,8 @@ int tg_adam_step_guarded(float* theta, const float* grad, float* m, float* v, in
                          float beta1, float beta2, float eps, const TgLossScaleState* state, void* stream) {
   TG_CHECK(theta && grad && m && v && lr_t_dev && state, TG_EINVAL, "tg_adam_step_guarded: null pointer");
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_step_guarded: numel must be positive (got %lld)", (long long)numel);
-  return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, 0.f, state}, stream, "tg_adam_step_guarded");
+  return launch_apply<TG_OPT_ADAM>({theta, grad, m, v, numel, {0.f, beta1, beta2, eps}, 0.f, state, nullptr, nullptr, lr_t_dev}, stream,
+                                   "tg_adam_step_guarded");
 }
 
 int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v, float* avg, int64_t numel,
@@ -1675,8 +1614,8 @@ int tg_adam_ema_step_guarded(float* theta, const float* grad, float* m, float* v
                              const float* w_dev, void* stream) {
   TG_CHECK(theta && grad && m && v && avg && lr_t_dev && state && w_dev, TG_EINVAL, "tg_adam_ema_step_guarded: null pointer");
   TG_CHECK(numel > 0, TG_EINVAL, "tg_adam_ema_step_guarded: numel must be positive (got %lld)", (long long)numel);
-  return launch_apply({theta, grad, m, v, numel, beta1, beta2, eps, lr_t_dev, 0.f, 0.f, state, avg, w_dev}, stream,
-                      "tg_adam_ema_step_guarded");
+  return launch_apply<TG_OPT_ADAM>({theta, grad, m, v, numel, {0.f, beta1, beta2, eps}, 0.f, state, avg, w_dev, lr_t_dev}, stream,
+                                   "tg_adam_ema_step_guarded");
 }
 
 int tg_optim_slot_count(int rule) { return rule >= TG_OPT_SGD && rule <= TG_OPT_FTRL ? optim_slots(rule) : -1; }
@@ -1696,14 +1635,15 @@ int tg_optim_step(int rule, float* theta, const float* grad, float* slot0, float
   if (rule == TG_OPT_FTRL)
     TG_CHECK(hyper->lr_power <= 0.f, TG_EINVAL, "tg_optim_step: hyper->lr_power must not be positive (got %g)",
              (double)hyper->lr_power);
-  const OptimArgs a{theta, grad, ns >= 1 ? slot0 : nullptr, ns >= 2 ? slot1 : nullptr, numel, *hyper, grad_scale, guard, avg, w_dev};
+  const ApplyArgs a{theta, grad, ns >= 1 ? slot0 : nullptr, ns >= 2 ? slot1 : nullptr, numel, *hyper, grad_scale, guard, avg, w_dev};
+  const char* name = "tg_optim_step";
   switch (rule) {
-    case TG_OPT_SGD: return launch_optim_rule<TG_OPT_SGD>(a, stream);
-    case TG_OPT_MOMENTUM: return launch_optim_rule<TG_OPT_MOMENTUM>(a, stream);
-    case TG_OPT_ADAGRAD: return launch_optim_rule<TG_OPT_ADAGRAD>(a, stream);
-    case TG_OPT_RMSPROP: return launch_optim_rule<TG_OPT_RMSPROP>(a, stream);
-    case TG_OPT_ADADELTA: return launch_optim_rule<TG_OPT_ADADELTA>(a, stream);
-    default: return hyper->lr_power == -0.5f ? launch_optim_rule<TG_OPT_FTRL>(a, stream) : launch_optim_rule<TG_OPT_FTRL_POW>(a, stream);
+    case TG_OPT_SGD: return launch_apply<TG_OPT_SGD>(a, stream, name);
+    case TG_OPT_MOMENTUM: return launch_apply<TG_OPT_MOMENTUM>(a, stream, name);
+    case TG_OPT_ADAGRAD: return launch_apply<TG_OPT_ADAGRAD>(a, stream, name);
+    case TG_OPT_RMSPROP: return launch_apply<TG_OPT_RMSPROP>(a, stream, name);
+    case TG_OPT_ADADELTA: return launch_apply<TG_OPT_ADADELTA>(a, stream, name);
+    default: return hyper->lr_power == -0.5f ? launch_apply<TG_OPT_FTRL>(a, stream, name) : launch_apply<TG_OPT_FTRL_POW>(a, stream, name);
   }
 }
 

@@ -1,14 +1,14 @@
 """Parameter store: every variable of one optimiser group lives in ONE flat fp32 HBM buffer (plus
-flat grad / Adam m / Adam v buffers), so a step needs one fused Adam launch and one RCCL all-reduce
+a flat grad buffer and the optimiser's flat slot buffers), so a step needs one fused apply launch and one RCCL all-reduce
 per group instead of one per variable (the reference applies Adam and tf.add_n per variable:
 model/model_inheritor.py:537-542, deployment/model_deploy.py:473-503).
 
 Variables are addressed by the reference's TF names and keep TF layouts
 (conv HWIO, fc [in, out]) so reference checkpoints map 1:1.  A variable may have a *physical*
 shape larger than its logical one (the D tail conv sees the minibatch-stddev tensor padded to a
-multiple of 8 channels); the padding rows are zero and stay zero under Adam -- and under every other rule of
-Config.optimizer (their gradient is 0: sgd, momentum, adagrad, rmsprop and adadelta then keep theta bit for bit, ftrl
-writes 0), whose slots live in ``slots[group]`` instead of ``m`` / ``v``.
+multiple of 8 channels); the padding rows are zero and stay zero under every rule of Config.optimizer (their gradient
+is 0: adam, sgd, momentum, adagrad, rmsprop and adadelta then keep theta bit for bit, ftrl writes 0).  The rule's slots
+live in ``slots[group]``: Adam's moments are ``[m, v]`` there, like any other rule's pair.
 """
 import math
 from collections import OrderedDict
@@ -51,8 +51,6 @@ class ParamStore:
     self.P = _ParamDict()           # name -> physical leaf tensor (requires_grad)
     self.flat = {}
     self.grad = {}
-    self.m = {}
-    self.v = {}
     self.offsets = {}
     self.state_specs = OrderedDict()   # name -> (numel, init value): non-trainable variables
     self.state = {}
@@ -64,14 +62,14 @@ class ParamStore:
     self.phase = {}                    # name -> phase
     self.pairs = {}                    # 'discriminator_*/<rest>' -> [2, *phys] view over the two domains' adjacent variables
     # --moving_average_decay (Config.moving_average_decay): set before build() by the trainer; build() then allocates the
-    # moving averages of the model variables -- avg[g] flat buffers laid out like flat[g] / m[g], state_avg[name] per state variable
+    # moving averages of the model variables -- avg[g] flat buffers laid out like flat[g], state_avg[name] per state variable
     self.averaged = False
     self.avg = {}
     self.state_avg = {}
-    # --optimizer (Config.optimizer): set before build() by the trainer (set_optimizer).  'adam' keeps m / v; any other rule has
-    # slots[g] = its flat slot buffers in slot0, slot1 order (OPTIM_SLOTS), laid out like flat[g], and empty m / v
+    # --optimizer (Config.optimizer): set before build() by the trainer (set_optimizer).  slots[g] = the rule's flat slot
+    # buffers in slot0, slot1 order (OPTIM_SLOTS), laid out like flat[g]: [m, v] for Adam, [] for sgd
     self.optimizer = 'adam'
-    self.slot_init = ()
+    self.slot_init = tuple(v for _, v in OPTIM_SLOTS['adam'])
     self.slots = {}
 
   def set_optimizer(self, cfg):
@@ -155,10 +153,7 @@ class ParamStore:
       n = max(sizes[g], ALIGN)
       self.flat[g] = torch.zeros(n, dtype=torch.float32, device=self.device)
       self.grad[g] = torch.zeros(n, dtype=torch.float32, device=self.device)
-      self.m[g] = torch.zeros(n if self.optimizer == 'adam' else 0, dtype=torch.float32, device=self.device)
-      self.v[g] = torch.zeros(n if self.optimizer == 'adam' else 0, dtype=torch.float32, device=self.device)
-      if self.optimizer != 'adam':
-        self.slots[g] = [torch.full((n,), v, dtype=torch.float32, device=self.device) for v in self.slot_init]
+      self.slots[g] = [torch.full((n,), v, dtype=torch.float32, device=self.device) for v in self.slot_init]
     gen = torch.Generator().manual_seed(seed)
     for name, s in self.specs.items():
       g, off, n = s['group'], self.offsets[name], int(math.prod(s['phys']))
@@ -246,30 +241,9 @@ class ParamStore:
     """Logical (TF checkpoint) shape of a non-trainable variable."""
     return () if k in self.scalar_state else tuple(self.state[k].shape)
 
-  def adam_dict(self):
-    """{variable name: (m, v)} -- logical views of the shared Adam optimiser's slot variables (TF: <var>/Adam,
-    <var>/Adam_1)."""
-    assert self.optimizer == 'adam', 'this store keeps the slots of %s: slot_dict()' % self.optimizer
-    out = {}
-    for k, s in self.specs.items():
-      g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
-      out[k] = (self._logical(self.m[g][off:off + n].view(s['phys']), s).clone(),
-                self._logical(self.v[g][off:off + n].view(s['phys']), s).clone())
-    return out
-
-  def load_adam_dict(self, slots):
-    """Inverse of adam_dict for the names given ({name: (m, v)} of logical shape)."""
-    with torch.no_grad():
-      for k, (m, v) in slots.items():
-        s = self.specs[k]
-        g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
-        for dst, src in ((self.m[g], m), (self.v[g], v)):
-          self._logical(dst[off:off + n].view(s['phys']), s).copy_(torch.as_tensor(src, dtype=torch.float32).reshape(s['shape']))
-
   def slot_dict(self):
-    """{'<var>/<slot>': logical (TF-shaped) copy} of the slots of a store whose optimiser is not Adam, under the names TF's
-    Saver writes (OPTIM_SLOTS: '<var>/RMSProp', '<var>/RMSProp_1', ...); {} for sgd."""
-    assert self.optimizer != 'adam', 'the Adam slots: adam_dict()'
+    """{'<var>/<slot>': logical (TF-shaped) copy} of the optimiser's slots, under the names TF's Saver writes (OPTIM_SLOTS:
+    '<var>/Adam', '<var>/Adam_1', '<var>/RMSProp', ...); {} for sgd."""
     out = {}
     for k, s in self.specs.items():
       g, off, n = s['group'], self.offsets[k], int(math.prod(s['phys']))
@@ -279,7 +253,6 @@ class ParamStore:
 
   def load_slot_dict(self, slots):
     """Inverse of slot_dict for the keys given."""
-    assert self.optimizer != 'adam', 'the Adam slots: load_adam_dict()'
     index = {slot: i for i, (slot, _) in enumerate(OPTIM_SLOTS[self.optimizer])}
     with torch.no_grad():
       for key, src in slots.items():

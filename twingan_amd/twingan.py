@@ -574,13 +574,13 @@ class Trainer:
     new numbers on every replay)."""
     return ops.uniform(n, self._rng_seed, self._rng_state)
 
-  def _adam(self, group):
-    """tf.train.AdamOptimizer apply (model/model_inheritor.py:537-542) on the group's flat buffers: tick, apply, the moving
-    averages, then refresh the bf16 weight packs of the convs that just moved.  All on the main stream, so a captured apply
-    graph holds (and replays) every decision made on the device.
+  def _apply(self, group):
+    """The apply of --optimizer (model/model_inheritor.py:516-565; Adam: tf.train.AdamOptimizer, :537-542) on the group's flat
+    buffers: tick, apply, the moving averages, then refresh the bf16 weight packs of the convs that just moved.  All on the
+    main stream, so a captured apply graph holds (and replays) every decision made on the device.
 
     Config.dynamic_loss_scale: check -> loss-scale tick -> guarded apply.  The check reads the group's WHOLE flat gradient
-    buffer after the clones' sum (reducer.finish() precedes _adam; inf + finite, inf - inf and NaN all stay non-finite
+    buffer after the clones' sum (reducer.finish() precedes _apply; inf + finite, inf - inf and NaN all stay non-finite
     through a sum), so every clone decides the same.  The host neither learns nor asks whether the apply was made:
     n_critic_counter, global_step and adam_t advance as ever.
 
@@ -592,14 +592,22 @@ class Trainer:
     moving statistics / spectral-norm u / gdrop updates (all joined before the apply).  Data-parallel runs need no
     communication: every clone applies the same all-reduced gradients to the same parameters, so the averages agree
     wherever the parameters do.  A skipped guarded apply still moves the group's averages, towards its unchanged
-    parameters."""
+    parameters.
+
+    --optimizer sgd | momentum | adagrad | rmsprop | adadelta | ftrl: one tg_optim_step in the place of Adam's entry point,
+    with the moving average and the guard exactly as Adam has them.  Every hyper-parameter goes by value, the guard and the
+    average's weight are device pointers: a captured apply graph replays unchanged.  The tick is Adam's (tg_adam_tick, or
+    tg_loss_scale_tick under the guard): it keeps the device count of applies made; the bias-corrected rate it also writes
+    is not read.  The learning rate is Config.learning_rate (the reference asserts learning_rate_decay_type == 'fixed');
+    use_ttur changes nothing here either."""
+    from ._lib import OPTIM_RULES, TgOptimHyper
     c, s = self.cfg, self.store
     st = torch.cuda.current_stream().cuda_stream
     self.adam_t += 1
     step, lr_t = self._adam_step_dev.data_ptr(), self._lr_t_dev.data_ptr()
-    th, g, m, v = (t[group].data_ptr() for t in (s.flat, s.grad, s.m, s.v))
+    th, g = s.flat[group].data_ptr(), s.grad[group].data_ptr()
+    slots = [t.data_ptr() for t in s.slots[group]] + [None, None]
     n = s.flat[group].numel()
-    hyper = (c.adam_beta1, c.adam_beta2, c.opt_epsilon)
     ls = self._ls[group].data_ptr() if self._ls is not None else None
     avg = s.avg[group].data_ptr() if s.averaged else None
     w = self._ema_w_dev.data_ptr() if s.averaged else None
@@ -609,17 +617,29 @@ class Trainer:
            int(c.loss_scale_growth_interval), self._ls_max, self.world, st)
     else:
       call('tg_adam_tick', step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2, st)
-    if s.averaged and ls is not None:
-      call('tg_adam_ema_step_guarded', th, g, m, v, avg, n, lr_t, *hyper, ls, w, st,
-           work=('adam_ema_guarded:numel%d' % n, 0, 36 * n))
-    elif s.averaged:
-      call('tg_adam_ema_step', th, g, m, v, avg, n, lr_t, *hyper, 1.0 / c.loss_scale, w, st,
-           work=('adam_ema:numel%d' % n, 0, 36 * n))
-    elif ls is not None:
-      call('tg_adam_step_guarded', th, g, m, v, n, lr_t, *hyper, ls, st, work=('adam_guarded:numel%d' % n, 0, 28 * n))
+    rule = c.optimizer
+    nbytes = (12 + 8 * len(s.slots[group]) + (8 if s.averaged else 0)) * n      # theta, grad; a slot or the average: 8 each
+    if rule == 'adam':      # its four entry points: one per form
+      m, v = slots[:2]
+      hyper = (c.adam_beta1, c.adam_beta2, c.opt_epsilon)
+      if s.averaged and ls is not None:
+        call('tg_adam_ema_step_guarded', th, g, m, v, avg, n, lr_t, *hyper, ls, w, st,
+             work=('adam_ema_guarded:numel%d' % n, 0, nbytes))
+      elif s.averaged:
+        call('tg_adam_ema_step', th, g, m, v, avg, n, lr_t, *hyper, 1.0 / c.loss_scale, w, st,
+             work=('adam_ema:numel%d' % n, 0, nbytes))
+      elif ls is not None:
+        call('tg_adam_step_guarded', th, g, m, v, n, lr_t, *hyper, ls, st, work=('adam_guarded:numel%d' % n, 0, nbytes))
+      else:
+        call('tg_adam_step', th, g, m, v, None, n, 0.0, lr_t, *hyper, 1.0 / c.loss_scale, st,
+             work=('adam:numel%d' % n, 0, nbytes))
     else:
-      call('tg_adam_step', th, g, m, v, None, n, 0.0, lr_t, *hyper, 1.0 / c.loss_scale, st,
-           work=('adam:numel%d' % n, 0, 28 * n))
+      hyper = TgOptimHyper(lr=c.learning_rate, momentum=c.rmsprop_momentum if rule == 'rmsprop' else c.momentum,
+                           decay_or_rho=c.adadelta_rho if rule == 'adadelta' else c.rmsprop_decay, eps=c.opt_epsilon,
+                           lr_power=c.ftrl_learning_rate_power, l1=c.ftrl_l1, l2=c.ftrl_l2)
+      tag = 'optim_%s%s%s:numel%d' % (rule, '_ema' if s.averaged else '', '_guarded' if ls is not None else '', n)
+      call('tg_optim_step', OPTIM_RULES[rule], th, g, slots[0], slots[1], avg, n, ctypes.byref(hyper), 1.0 / c.loss_scale, ls, w,
+           st, work=(tag, 0, nbytes))
     self._after_apply(group, w, st)
 
   def _after_apply(self, group, w, st):
@@ -635,44 +655,6 @@ class Trainer:
         tab = self._ema_table
         call('tg_ema_update_multi', tab[0].data_ptr(), tab[1], tab[2], w, st, work=('ema_multi:%d' % tab[1], 0, tab[3]))
     PackCache.refresh(self._group_weights[group])      # also after a skipped apply: it repacks the same bits
-
-  def _apply(self, group):
-    """The apply of --optimizer: Adam's own path, or tg_optim_step for the other rules."""
-    return self._adam(group) if self.cfg.optimizer == 'adam' else self._optim(group)
-
-  def _optim(self, group):
-    """_adam's sibling for --optimizer sgd | momentum | adagrad | rmsprop | adadelta | ftrl (model/model_inheritor.py:516-565):
-    one tg_optim_step on the group's flat buffers, with the moving average and the dynamic-loss-scale guard exactly as _adam
-    has them.  Every hyper-parameter goes by value, the guard and the average's weight are device pointers: a captured apply
-    graph replays unchanged.  The tick is Adam's (tg_adam_tick, or tg_loss_scale_tick under the guard): it keeps the device
-    count of applies made; the bias-corrected rate it also writes is not read.  The learning rate is Config.learning_rate
-    (the reference asserts learning_rate_decay_type == 'fixed'); use_ttur changes nothing here either."""
-    from ._lib import OPTIM_RULES, TgOptimHyper
-    c, s = self.cfg, self.store
-    st = torch.cuda.current_stream().cuda_stream
-    self.adam_t += 1
-    step, lr_t = self._adam_step_dev.data_ptr(), self._lr_t_dev.data_ptr()
-    n = s.flat[group].numel()
-    th, g = s.flat[group].data_ptr(), s.grad[group].data_ptr()
-    slots = [t.data_ptr() for t in s.slots[group]] + [None, None]
-    ls = self._ls[group].data_ptr() if self._ls is not None else None
-    avg = s.avg[group].data_ptr() if s.averaged else None
-    w = self._ema_w_dev.data_ptr() if s.averaged else None
-    rule = c.optimizer
-    hyper = TgOptimHyper(lr=c.learning_rate, momentum=c.rmsprop_momentum if rule == 'rmsprop' else c.momentum,
-                         decay_or_rho=c.adadelta_rho if rule == 'adadelta' else c.rmsprop_decay, eps=c.opt_epsilon,
-                         lr_power=c.ftrl_learning_rate_power, l1=c.ftrl_l1, l2=c.ftrl_l2)
-    if ls is not None:
-      call('tg_nonfinite_check', g, n, ls, st, work=('nonfinite:numel%d' % n, 0, 4 * n))
-      call('tg_loss_scale_tick', ls, step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2,
-           int(c.loss_scale_growth_interval), self._ls_max, self.world, st)
-    else:
-      call('tg_adam_tick', step, lr_t, c.learning_rate, c.adam_beta1, c.adam_beta2, st)
-    nbytes = (12 + 8 * len(s.slots[group]) + (8 if s.averaged else 0)) * n
-    tag = 'optim_%s%s%s:numel%d' % (rule, '_ema' if s.averaged else '', '_guarded' if ls is not None else '', n)
-    call('tg_optim_step', OPTIM_RULES[rule], th, g, slots[0], slots[1], avg, n, ctypes.byref(hyper), 1.0 / c.loss_scale, ls, w, st,
-         work=(tag, 0, nbytes))
-    self._after_apply(group, w, st)
 
   # ---- moving averages (--moving_average_decay) ---------------------------------------------------------------
   def _build_ema_table(self):
@@ -795,11 +777,10 @@ class Trainer:
 
   # ---- hipGraph capture ---------------------------------------------------------------------------
   def _snapshot(self):
-    """Everything a training run mutates: parameters, Adam moments (or the slots of Config.optimizer's rule) and step,
+    """Everything a training run mutates: parameters, the slots of Config.optimizer's rule (Adam's moments) and step,
     non-trainable state (BatchNorm moving / renorm statistics, spectral-norm u), the host counters and the device RNG."""
     s = self.store
-    return dict(flat={g: s.flat[g].clone() for g in s.GROUPS}, m={g: s.m[g].clone() for g in s.GROUPS},
-                v={g: s.v[g].clone() for g in s.GROUPS}, slots={g: [t.clone() for t in ts] for g, ts in s.slots.items()},
+    return dict(flat={g: s.flat[g].clone() for g in s.GROUPS}, slots={g: [t.clone() for t in ts] for g, ts in s.slots.items()},
                 state={k: v.clone() for k, v in s.state.items()},
                 step=self._adam_step_dev.clone(), lr=self._lr_t_dev.clone(), draws=self._rng_state.clone(),
                 host=(self.n_critic_counter, self.global_step, self.adam_t), rng=torch.cuda.get_rng_state(self.device),
@@ -814,9 +795,7 @@ class Trainer:
     with torch.no_grad():
       for g in s.GROUPS:
         s.flat[g].copy_(snap['flat'][g])
-        s.m[g].copy_(snap['m'][g])
-        s.v[g].copy_(snap['v'][g])
-        for t, saved in zip(s.slots.get(g, ()), snap['slots'].get(g, ())):
+        for t, saved in zip(s.slots[g], snap['slots'][g]):
           t.copy_(saved)
         s.grad[g].zero_()
       for k, v in snap['state'].items():
