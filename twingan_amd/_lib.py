@@ -1,5 +1,5 @@
 """ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h, include/twingan_hip_summary.h,
-include/twingan_hip_knn.h).
+include/twingan_hip_knn.h, include/twingan_hip_syncnorm.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a kernel call returns
 an error, this module raises.  (``oracle/`` is test infrastructure and is never imported here.)
@@ -241,6 +241,14 @@ KNN_SIGNATURES = {
     'tg_knn_topk': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int64, _P, _FP, _P, _P, c_size_t, _P]),
 }
 
+# include/twingan_hip_syncnorm.h, one to one as above.
+SYNCNORM_SIGNATURES = {
+    'tg_norm_moments': (c_int, [_P, _FP, _FP, c_int, c_int, c_int, c_int, c_int, _P]),
+    'tg_norm_moments_merge': (c_int, [_FP, c_int, c_int64, _FP, _FP, c_int, c_int, c_float, _P]),
+    'tg_norm_act_bwd_sums': (c_int, [_P, _P, _P] + [_FP] * 7 + [c_int, c_int] + [_FP] * 6 + [c_int] * 5 + [c_float, c_int, c_int, _P]),
+    'tg_norm_act_bwd_apply': (c_int, [_P, _P, _P] + [_FP] * 7 + [c_int, c_int, _P, _FP] + [c_int] * 6 + [c_float, c_int, _P]),
+}
+
 _lib = None
 
 
@@ -254,7 +262,7 @@ def load():
                   '(make -C twingan_amd/csrc). There is no CPU fallback.' % LIB_PATH)
   lib = ctypes.CDLL(LIB_PATH)
   for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items()) + \
-      list(KNN_SIGNATURES.items()):
+      list(KNN_SIGNATURES.items()) + list(SYNCNORM_SIGNATURES.items()):
     fn = getattr(lib, name)       # AttributeError if a declared symbol is missing
     fn.restype = res
     fn.argtypes = args

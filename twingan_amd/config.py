@@ -70,6 +70,11 @@ class Config:
   # [1, 2**24] (every unscale is exact).  Only 'fp16' grows the scale; the other precisions keep theirs and gain the guard.
   dynamic_loss_scale: bool = False
   loss_scale_growth_interval: int = 2000
+  # Cross-replica batch statistics (this project's own rule, the reference's clones keep their own: DESIGN.md section 7).
+  # With more than one clone, every statistic group of batch_norm / batch_renorm / batch_renorm_native (and their
+  # conditional forms) in training mode covers that pass's pixels on ALL clones, forward and backward; the moving and renorm
+  # state is then bit-identical on every clone.  Needs the same per-clone batch size everywhere; runs the eager step.
+  cross_replica_norm: bool = False
   # --optimizer (model/model_inheritor.py:122-165, 516-565): adadelta | adagrad | adam | ftrl | momentum | rmsprop | sgd, each
   # with the reference's defaults; learning_rate and opt_epsilon are shared.  DESIGN.md section 4
   optimizer: str = 'adam'
@@ -86,6 +91,9 @@ class Config:
   OPTIMIZERS = ('adadelta', 'adagrad', 'adam', 'ftrl', 'momentum', 'rmsprop', 'sgd')
 
   def __post_init__(self):
+    if self.cross_replica_norm and self.generator_norm_type not in ('batch_norm', 'batch_renorm', 'batch_renorm_native'):
+      raise ValueError('cross_replica_norm needs a batch normaliser (batch_norm | batch_renorm | batch_renorm_native): '
+                       'generator_norm_type %r keeps no batch statistics' % (self.generator_norm_type,))
     if self.optimizer not in self.OPTIMIZERS:
       raise ValueError('optimizer must be one of %s (got %r)' % (' | '.join(self.OPTIMIZERS), self.optimizer))
     if not float(self.ftrl_learning_rate_power) <= 0.0:

@@ -9,6 +9,7 @@
 // threads of a pixel are adjacent lanes of one wave, so the per-pixel channel reduction of pixel
 // norm is a butterfly shuffle inside the wave.
 #include "tg_common.h"
+#include "../../include/twingan_hip_syncnorm.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -578,7 +579,11 @@ __global__ void norm_act_bwd1_kernel(const T* __restrict__ gz, const T* __restri
 
 // backward pass 2: gy = gamma*rstd * (gu - S1/hw - yhat * S2/hw).  grid = (chunks2, n); the prologue sums the
 // image's partial S1 / S2; with `sink` block (0, n) adds them into the parameter gradients.
-template <typename T, int V, int FL = -1>
+// SYNC (tg_norm_act_bwd_apply, cross-replica statistics): `part` is gathered[chunks = replicas][n][2][c], the replicas'
+// sums of each group; the prologue adds the rows in rank order, the divisor is gcount (the group's pixels on all
+// replicas) instead of hw, and the parameter gradients are not this kernel's (they stay local sums).  SYNC = false is
+// the kernel as it was: gcount is not read.
+template <typename T, int V, int FL = -1, bool SYNC = false>
 __global__ void norm_act_bwd2_part_kernel(const T* __restrict__ gz, const T* __restrict__ gzp, int wdim,
                                           const T* __restrict__ y, const float* __restrict__ pn_scale,
                                           const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -587,7 +592,7 @@ __global__ void norm_act_bwd2_part_kernel(const T* __restrict__ gz, const T* __r
                                           int pstride, T* __restrict__ gy, const float* __restrict__ part, int chunks,
                                           float* __restrict__ ggamma, float* __restrict__ gbeta,
                                           float* __restrict__ ggamma2, float* __restrict__ gbeta2, int sink, int hw, int c,
-                                          int flags_rt, float alpha, int px_per_block) {
+                                          int flags_rt, float alpha, int px_per_block, int gcount) {
   extern __shared__ float sh[];   // [2][c]
   const int flags = FL < 0 ? flags_rt : ((flags_rt & ~3) | FL);
   const int cv = c / V;
@@ -604,8 +609,18 @@ __global__ void norm_act_bwd2_part_kernel(const T* __restrict__ gz, const T* __r
     ga[j] = pstride ? gamma[(int64_t)n * pstride + ch] : (n < split ? gamma : gamma2)[ch];
     be[j] = pstride ? beta[(int64_t)n * pstride + ch] : (n < split ? beta : beta2)[ch];
   }
-  reduce_partials<exact_path<T>()>(part, n, chunks, c, sh);
-  if (pstride && blockIdx.x == 0) {      // one parameter row per image: its gradient row is this image's sums
+  if constexpr (SYNC) {
+    for (int i = threadIdx.x; i < 2 * c; i += blockDim.x) {
+      float t = 0.f;
+      for (int r = 0; r < chunks; ++r) t += part[((int64_t)r * gridDim.y + n) * 2 * c + i];
+      sh[i] = t;
+    }
+    __syncthreads();
+  } else {
+    reduce_partials<exact_path<T>()>(part, n, chunks, c, sh);
+  }
+  if (SYNC) {
+  } else if (pstride && blockIdx.x == 0) {      // one parameter row per image: its gradient row is this image's sums
     for (int i = threadIdx.x; i < c; i += blockDim.x) {
       if (gbeta) gbeta[(int64_t)n * pstride + i] = sh[i];
       if (ggamma) ggamma[(int64_t)n * pstride + i] = sh[c + i];
@@ -642,7 +657,7 @@ __global__ void norm_act_bwd2_part_kernel(const T* __restrict__ gz, const T* __r
       }
     }
   }
-  const float inv = 1.f / (float)hw;
+  const float inv = 1.f / (float)(SYNC ? gcount : hw);
   float s1[V], s2[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -826,6 +841,133 @@ __global__ void lrelu_bwd_bias_kernel(const T* __restrict__ gz, const T* __restr
   wave_channel_accumulate<V>(a, sh, 0, cv, v, pl < lanes);
   __syncthreads();
   for (int i = threadIdx.x; i < c; i += blockDim.x) atomicAdd(gbias + i, sh[i]);
+}
+
+// ------------------------------------------------------------------------------------------------
+// cross-replica statistics (include/twingan_hip_syncnorm.h): the small kernels between the streaming passes and the
+// all-gathers.  One thread per value; every sum in a fixed order.
+// ------------------------------------------------------------------------------------------------
+// tot[col] = sum over q = 0 .. chunks-1 of p[q * cols + col] for col < cols (p: one group's [chunks][cols] partial sums), in
+// double and in a FIXED order: the block's threads form S = blockDim / min(cols, blockDim) slices, slice s adds chunks
+// s, s + S, ... (four loads in flight, four chains combined in order), and the slices' sums are added in slice order.  A
+// thread per value walking all the chunks alone was 100+ us of dependent round trips in front of the 512-chunk layers.
+// Block-collective (barriers); tot: LDS [cols]; blockDim <= 1024.
+__device__ __forceinline__ void ordered_chunk_sums(const float* __restrict__ p, int chunks, int cols, double* tot) {
+  __shared__ double scratch[1024];
+  const int wdt = cols < (int)blockDim.x ? cols : (int)blockDim.x;
+  const int slices = blockDim.x / wdt;
+  const int lane = threadIdx.x % wdt, sl = threadIdx.x / wdt;
+  for (int cb = 0; cb < cols; cb += wdt) {
+    const int col = cb + lane;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    if (sl < slices && col < cols) {
+      int q = sl;
+      for (; q + 3 * slices < chunks; q += 4 * slices) {
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = p[(int64_t)(q + u * slices) * cols + col];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a[u] += (double)v[u];
+      }
+      for (; q < chunks; q += slices) a[0] += (double)p[(int64_t)q * cols + col];
+    }
+    scratch[threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    if (sl == 0 && col < cols) {
+      double t = 0.0;
+      for (int k = 0; k < slices; ++k) t += scratch[k * wdt + lane];
+      tot[col] = t;
+    }
+    __syncthreads();
+  }
+}
+
+// moments[g][0..1][ch] = K + S1 / hw as an fp32 pair (value, what its rounding dropped), moments[g][2][ch] = S2 - S1 * S1 / hw,
+// from part[g][chunk][2][c] (shifted by K = y[g,0,0,ch]).  The pair: a mean rounded to fp32 would put
+// 2 count sum_r (mean_r - mean) e_r, |e_r| <= ulp(mean) / 2, into the merged variance -- 1e-3 of rstd at mean 300, sigma 0.05
+// and 16 pixels per replica (measured); with the dropped part alongside, the merge adds nothing to the chunk sums' own rounding.
+// grid = n groups, one workgroup each.  The chunks meet in double: what the results carry is the fp32 rounding of the chunk
+// sums themselves and one rounding of each value written (S2 - S1^2 / hw cancels when K sits sigmas off the mean).
+template <typename T>
+__global__ void norm_moments_final(const T* __restrict__ y, const float* __restrict__ part, int chunks,
+                                   float* __restrict__ moments, int hw, int c) {
+  extern __shared__ double tot[];      // [2][c]
+  const int g = blockIdx.x;
+  ordered_chunk_sums(part + (int64_t)g * chunks * 2 * c, chunks, 2 * c, tot);
+  for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
+    const float k = ld(y + (int64_t)g * hw * c + ch);
+    const double s1 = tot[ch], s2 = tot[c + ch];
+    const double m1 = s1 / (double)hw;
+    double m2 = s2 - s1 * m1;
+    m2 = m2 < 0.0 ? 0.0 : m2;
+    const double mu = (double)k + m1;
+    const float hi = (float)mu;
+    moments[((int64_t)g * 3) * c + ch] = hi;
+    moments[((int64_t)g * 3 + 1) * c + ch] = (float)(mu - (double)hi);
+    moments[((int64_t)g * 3 + 2) * c + ch] = (float)m2;
+  }
+}
+
+// Chan's rule over the replicas' (mean, M2) rows of equal count, in rank order
+__global__ void norm_moments_merge_kernel(const float* __restrict__ gathered, int replicas, double count,
+                                          float* __restrict__ mean, float* __restrict__ rstd, int n, int c, float eps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * c) return;
+  const int g = i / c, ch = i - g * c;
+  const int64_t row = (int64_t)n * 3 * c;
+  const float* p = gathered + ((int64_t)g * 3) * c + ch;
+  // in double, rows in rank order: the merge adds no rounding of its own but the two it writes (identical inputs in an
+  // identical order: identical bits on every clone)
+  double m = 0.0;
+  for (int r = 0; r < replicas; ++r) m += (double)p[r * row] + (double)p[r * row + c];
+  m /= (double)replicas;
+  double m2 = 0.0, q = 0.0;
+  for (int r = 0; r < replicas; ++r) {
+    m2 += (double)p[r * row + 2 * c];
+    const double dm = ((double)p[r * row] + (double)p[r * row + c]) - m;
+    q += dm * dm;
+  }
+  m2 += count * q;
+  const float var = (float)(m2 / ((double)replicas * count));
+  mean[i] = (float)m;
+  rstd[i] = rsqrtf(var + eps);
+}
+
+// local[g][0..2c) = sum over the chunks of part[g][chunk][0..2c) (ordered_chunk_sums, rounded to fp32 once); with rows
+// (per-image parameters) the group's sums are also its gradient rows: gbeta[g][c] = S1, ggamma[g][c] = S2.  grid = n groups.
+__global__ void norm_bwd_sums_final(const float* __restrict__ part, int chunks, float* __restrict__ local,
+                                    float* __restrict__ ggamma_rows, float* __restrict__ gbeta_rows, int c) {
+  extern __shared__ double tot[];      // [2][c]
+  const int g = blockIdx.x;
+  ordered_chunk_sums(part + (int64_t)g * chunks * 2 * c, chunks, 2 * c, tot);
+  for (int j = threadIdx.x; j < 2 * c; j += blockDim.x) {
+    const float t = (float)tot[j];
+    local[(int64_t)g * 2 * c + j] = t;
+    if (j < c) {
+      if (gbeta_rows) gbeta_rows[(int64_t)g * c + j] = t;
+    } else {
+      if (ggamma_rows) ggamma_rows[(int64_t)g * c + (j - c)] = t;
+    }
+  }
+}
+
+// groups [i0, i1) of local[n][2][c] -> (ggamma, gbeta), added in group order; blockIdx.y selects the domain half.  With
+// `accumulate` one add per parameter (launches that feed a gradient buffer are stream-ordered: no race, a fixed result)
+__global__ void norm_param_grads_local(const float* __restrict__ local, float* __restrict__ ggamma, float* __restrict__ gbeta,
+                                       float* __restrict__ ggamma2, float* __restrict__ gbeta2, int split, int n, int c,
+                                       int accumulate) {
+  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ch >= c) return;
+  const int i0 = blockIdx.y ? split : 0, i1 = blockIdx.y ? n : split;
+  float* gg = blockIdx.y ? ggamma2 : ggamma;
+  float* gb = blockIdx.y ? gbeta2 : gbeta;
+  float sb = 0.f, sg = 0.f;
+  for (int g = i0; g < i1; ++g) {
+    sb += local[((int64_t)g * 2) * c + ch];
+    sg += local[((int64_t)g * 2 + 1) * c + ch];
+  }
+  if (gg) gg[ch] = accumulate ? gg[ch] + sg : sg;
+  if (gb) gb[ch] = accumulate ? gb[ch] + sb : sb;
 }
 
 // largest power of two <= 64 check for the pixel-norm group reduction
@@ -1038,7 +1180,7 @@ int tg_norm_act_fwd(const void* y, const float* mean, const float* rstd, const f
                        pstride, sums, hw, c, flags, alpha, ppb);                                                           \
     hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, VN, exact_path<T>() ? -1 : FL_>), dim3(chunks2, n), dim3(256), lds, s, (const T*)gz, \
                        (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split,       \
-                       pstride, (T*)gy, sums, chunks, ggamma, gbeta, ggamma2, gbeta2, sink, hw, c, flags, alpha, ppb2);    \
+                       pstride, (T*)gy, sums, chunks, ggamma, gbeta, ggamma2, gbeta2, sink, hw, c, flags, alpha, ppb2, 0); \
   } while (0)
 
 int tg_norm_act_bwd(const void* gz, const void* gz_pooled, const void* y, const float* pn_scale, const float* mean,
@@ -1085,13 +1227,150 @@ int tg_norm_act_bwd(const void* gz, const void* gz_pooled, const void* y, const 
                          (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride, sums, hw, c, flags, alpha, ppb);
       hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, 1>), dim3(chunks2, n), dim3(256), lds, s, (const T*)gz,
                          (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split,
-                         pstride, (T*)gy, sums, chunks, ggamma, gbeta, ggamma2, gbeta2, sink, hw, c, flags, alpha, ppb2);
+                         pstride, (T*)gy, sums, chunks, ggamma, gbeta, ggamma2, gbeta2, sink, hw, c, flags, alpha, ppb2, 0);
     }
   });
   if (want_params && !sink && !pstride)
     hipLaunchKernelGGL(norm_param_grads, dim3((c + 255) / 256, split < n ? 2 : 1), dim3(256), 0, s, sums, chunks, ggamma,
                        gbeta, ggamma2, gbeta2, split, n, c, 0);
   TG_LAUNCH_CHECK("tg_norm_act_bwd");
+  return TG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// cross-replica statistics: include/twingan_hip_syncnorm.h
+// ------------------------------------------------------------------------------------------------
+int tg_norm_moments(const void* y, float* moments, float* ws, int n, int h, int w, int c, int dtype, void* stream) {
+  TG_CHECK(y && moments && ws && n > 0 && h > 0 && w > 0 && c > 0, TG_EINVAL, "tg_norm_moments: bad arguments");
+  TG_CHECK((int64_t)h * w < (1ll << 31) / c, TG_EINVAL, "tg_norm_moments: a group of %d x %d x %d elements does not fit 32-bit offsets",
+           h, w, c);
+  int rc = tg_instance_norm_partials(y, ws, n, h, w, c, dtype, stream);
+  if (rc) return rc;
+  TG_DISPATCH_DTYPE(dtype, "tg_norm_moments", {
+    hipLaunchKernelGGL(norm_moments_final<T>, dim3(n), dim3(1024), 2 * (size_t)c * sizeof(double), (hipStream_t)stream,
+                       (const T*)y, ws, tg_norm_chunks(n, h, w), moments, h * w, c);
+  });
+  TG_LAUNCH_CHECK("tg_norm_moments");
+  return TG_OK;
+}
+
+int tg_norm_moments_merge(const float* gathered, int replicas, int64_t count, float* mean, float* rstd, int n, int c,
+                          float eps, void* stream) {
+  TG_CHECK(gathered && mean && rstd && n > 0 && c > 0, TG_EINVAL, "tg_norm_moments_merge: bad arguments");
+  TG_CHECK(replicas >= 1 && count >= 1 && count * replicas < (1ll << 31), TG_EINVAL,
+           "tg_norm_moments_merge: replicas %d x count %lld outside [1, 2^31)", replicas, (long long)count);
+  hipLaunchKernelGGL(norm_moments_merge_kernel, dim3((n * c + 255) / 256), dim3(256), 0, (hipStream_t)stream, gathered, replicas,
+                     (double)count, mean, rstd, n, c, eps);
+  TG_LAUNCH_CHECK("tg_norm_moments_merge");
+  return TG_OK;
+}
+
+// pass 1 of the vector path with the LeakyReLU / pixel-norm bits FL_ fixed at compile time (locals of tg_norm_act_bwd_sums)
+#define TG_NB1_LAUNCH(FL_)                                                                                                 \
+  hipLaunchKernelGGL((norm_act_bwd1_kernel<T, VN, exact_path<T>() ? -1 : FL_>), dim3(chunks, n), dim3(256), lds, s, (const T*)gz, \
+                     (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride,  \
+                     ws, hw, c, flags, alpha, ppb)
+
+int tg_norm_act_bwd_sums(const void* gz, const void* gz_pooled, const void* y, const float* pn_scale, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, const float* gamma2, const float* beta2,
+                         int split, int per_image_params, float* ggamma, float* gbeta, float* ggamma2, float* gbeta2,
+                         float* ws, float* local, int n, int h, int w, int c, int flags, float alpha, int accumulate,
+                         int dtype, void* stream) {
+  const int pstride = per_image_params ? c : 0;
+  TG_CHECK((gz || gz_pooled) && y && mean && rstd && gamma && beta && ws && local && n > 0 && h > 0 && w > 0 && c > 0,
+           TG_EINVAL, "tg_norm_act_bwd_sums: bad arguments");
+  TG_CHECK(!gz_pooled || (h % 2 == 0 && w % 2 == 0), TG_EINVAL, "tg_norm_act_bwd_sums: pooled gradient needs even h, w");
+  TG_CHECK(!(flags & NF_NOSTATS), TG_EINVAL, "tg_norm_act_bwd_sums: constant statistics (NF_NOSTATS) have no sums to share");
+  TG_CHECK((int64_t)h * w < (1ll << 31) / c, TG_EINVAL, "tg_norm_act_bwd_sums: a group of %d x %d x %d elements does not fit 32-bit offsets",
+           h, w, c);
+  TG_CHECK(!pstride || !accumulate, TG_EINVAL, "tg_norm_act_bwd_sums: per-image parameter gradients are written, not added");
+  if (!gamma2 || !beta2) split = n;
+  TG_CHECK(split >= 0 && split <= n, TG_EINVAL, "tg_norm_act_bwd_sums: split %d outside [0, %d]", split, n);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  int chunks, ppb;
+  norm_chunks(n, hw, &chunks, &ppb);
+  const size_t lds = 2 * (size_t)c * sizeof(float);
+  TG_DISPATCH_DTYPE(dtype, "tg_norm_act_bwd_sums", {
+    constexpr int VN = Vec16<T>::N;
+    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
+    if (flags & NF_PIXNORM) {
+      TG_CHECK(vec && pn_scale, TG_ENOSUP, "tg_norm_act_bwd_sums: pixel norm needs c (%d) = %d * 2^k and pn_scale", c, VN);
+    }
+    if (vec) {
+      switch (flags & 3) {
+        case 0: TG_NB1_LAUNCH(0); break;
+        case 1: TG_NB1_LAUNCH(1); break;
+        case 2: TG_NB1_LAUNCH(2); break;
+        default: TG_NB1_LAUNCH(3); break;
+      }
+    } else {
+      TG_CHECK(c <= 256, TG_ENOSUP, "tg_norm_act_bwd_sums: scalar path needs c <= 256 (got %d)", c);
+      hipLaunchKernelGGL((norm_act_bwd1_kernel<T, 1>), dim3(chunks, n), dim3(256), lds, s, (const T*)gz, (const T*)gz_pooled, w,
+                         (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride, ws, hw, c, flags, alpha,
+                         ppb);
+    }
+  });
+  hipLaunchKernelGGL(norm_bwd_sums_final, dim3(n), dim3(1024), 2 * (size_t)c * sizeof(double), s, ws, chunks, local,
+                     pstride ? ggamma : nullptr, pstride ? gbeta : nullptr, c);
+  if (!pstride && (ggamma || gbeta || ggamma2 || gbeta2))
+    hipLaunchKernelGGL(norm_param_grads_local, dim3((c + 255) / 256, split < n ? 2 : 1), dim3(256), 0, s, local, ggamma, gbeta,
+                       ggamma2, gbeta2, split, n, c, accumulate ? 1 : 0);
+  TG_LAUNCH_CHECK("tg_norm_act_bwd_sums");
+  return TG_OK;
+}
+
+// pass 2 of the vector path in its SYNC form (locals of tg_norm_act_bwd_apply)
+#define TG_NB2S_LAUNCH(FL_)                                                                                                \
+  hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, VN, exact_path<T>() ? -1 : FL_, true>), dim3(chunks2, n), dim3(256), lds, s, \
+                     (const T*)gz, (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2,    \
+                     split, pstride, (T*)gy, gathered, replicas, nullptr, nullptr, nullptr, nullptr, 0, hw, c, flags, alpha, \
+                     ppb2, gcount)
+
+int tg_norm_act_bwd_apply(const void* gz, const void* gz_pooled, const void* y, const float* pn_scale, const float* mean,
+                          const float* rstd, const float* gamma, const float* beta, const float* gamma2, const float* beta2,
+                          int split, int per_image_params, void* gy, const float* gathered, int replicas, int n, int h,
+                          int w, int c, int flags, float alpha, int dtype, void* stream) {
+  const int pstride = per_image_params ? c : 0;
+  TG_CHECK((gz || gz_pooled) && y && mean && rstd && gamma && beta && gy && gathered && n > 0 && h > 0 && w > 0 && c > 0,
+           TG_EINVAL, "tg_norm_act_bwd_apply: bad arguments");
+  TG_CHECK(!gz_pooled || (h % 2 == 0 && w % 2 == 0), TG_EINVAL, "tg_norm_act_bwd_apply: pooled gradient needs even h, w");
+  TG_CHECK(!(flags & NF_NOSTATS), TG_EINVAL, "tg_norm_act_bwd_apply: constant statistics (NF_NOSTATS) have no sums to share");
+  TG_CHECK((int64_t)h * w < (1ll << 31) / c, TG_EINVAL, "tg_norm_act_bwd_apply: a group of %d x %d x %d elements does not fit 32-bit offsets",
+           h, w, c);
+  TG_CHECK(replicas >= 1 && (int64_t)replicas * h * w < (1ll << 31), TG_EINVAL,
+           "tg_norm_act_bwd_apply: replicas %d x %d pixels outside [1, 2^31)", replicas, h * w);
+  if (!gamma2 || !beta2) split = n;
+  TG_CHECK(split >= 0 && split <= n, TG_EINVAL, "tg_norm_act_bwd_apply: split %d outside [0, %d]", split, n);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  const int gcount = replicas * hw;
+  int chunks2 = (2048 + n - 1) / n;
+  int ppb2 = (hw + chunks2 - 1) / chunks2;
+  if (ppb2 < min_ppb(hw)) ppb2 = min_ppb(hw);
+  chunks2 = (hw + ppb2 - 1) / ppb2;
+  const size_t lds = 2 * (size_t)c * sizeof(float);
+  TG_DISPATCH_DTYPE(dtype, "tg_norm_act_bwd_apply", {
+    constexpr int VN = Vec16<T>::N;
+    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
+    if (flags & NF_PIXNORM) {
+      TG_CHECK(vec && pn_scale, TG_ENOSUP, "tg_norm_act_bwd_apply: pixel norm needs c (%d) = %d * 2^k and pn_scale", c, VN);
+    }
+    if (vec) {
+      switch (flags & 3) {
+        case 0: TG_NB2S_LAUNCH(0); break;
+        case 1: TG_NB2S_LAUNCH(1); break;
+        case 2: TG_NB2S_LAUNCH(2); break;
+        default: TG_NB2S_LAUNCH(3); break;
+      }
+    } else {
+      TG_CHECK(c <= 256, TG_ENOSUP, "tg_norm_act_bwd_apply: scalar path needs c <= 256 (got %d)", c);
+      hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, 1, -1, true>), dim3(chunks2, n), dim3(256), lds, s, (const T*)gz,
+                         (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride,
+                         (T*)gy, gathered, replicas, nullptr, nullptr, nullptr, nullptr, 0, hw, c, flags, alpha, ppb2, gcount);
+    }
+  });
+  TG_LAUNCH_CHECK("tg_norm_act_bwd_apply");
   return TG_OK;
 }
 

@@ -119,3 +119,50 @@ class GradReducer:
     self.start(flat_grad)
     self.finish()
     return flat_grad
+
+
+class ReplicaGather:
+  """All-gather of one small fp32 tensor across clones, in program order: what the cross-replica normaliser statistics
+  (Config.cross_replica_norm; ops.norm_act(..., replicas=)) exchange -- per statistic group and channel the clone's
+  (mean, M2) on the way forward and its (S1, S2) on the way back.  ``gather(t)`` returns [size, *t.shape] with row r the
+  tensor of rank r, the same rows in the same order on every clone (so whatever is computed from them in a fixed order
+  is bit-identical on all of them).  The collective is synchronous with respect to the calling stream: on "nccl" it is
+  enqueued behind the kernels that wrote ``t`` and the stream's later kernels wait for it on the device; on "gloo" (the
+  tests) the host waits.  Every clone must call gather() the same number of times in the same order with the same shapes
+  -- the forward / autograd order of one model on equal batch sizes is that.  ``stats()`` counts like
+  GradReducer.stats()."""
+
+  def __init__(self, world_size=1, process_group=None):
+    self.size = int(world_size)
+    self.pg = process_group
+    if self.size > 1:
+      if not dist.is_initialized():
+        raise RuntimeError('world_size %d but torch.distributed is not initialised' % self.size)
+      got = dist.get_world_size(process_group)
+      if got != self.size:
+        raise RuntimeError('world_size %d but the process group has %d ranks' % (self.size, got))
+    self.rank = dist.get_rank(process_group) if self.size > 1 else 0
+    self.reset_stats()
+
+  def reset_stats(self):
+    self._bytes = 0
+    self._collectives = 0
+
+  def gather(self, t):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+      raise ValueError('ReplicaGather.gather takes a contiguous float32 tensor (got %s)' % (t.dtype,))
+    out = torch.empty((self.size,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+    if self.size == 1:
+      out[0].copy_(t)
+      return out
+    if dist.get_backend(self.pg) == 'nccl':
+      dist.all_gather_into_tensor(out, t, group=self.pg)
+    else:      # the list form: every backend has it (gloo gathers device tensors through it)
+      dist.all_gather([out[r] for r in range(self.size)], t, group=self.pg)
+    self._bytes += out.numel() * out.element_size()
+    self._collectives += 1
+    return out
+
+  def stats(self):
+    """dict(gather_bytes = bytes received, collectives) since the last reset_stats()."""
+    return dict(gather_bytes=int(self._bytes), collectives=int(self._collectives))

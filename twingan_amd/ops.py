@@ -1391,9 +1391,29 @@ def _ema_update(mean, rstd, n, c, split, eps, ema):
       mv.sub_((mv - v[gi]) * (1.0 - decay))
 
 
-def instance_stats(y, eps):
-  """(mean, rstd), fp32 [n*c], of y[n,h,w,c] over (h,w): biased variance, rstd = rsqrt(var + eps).  No autograd."""
+def _sync_stats(y, eps, replicas):
+  """instance_stats over the pixels of ALL clones (include/twingan_hip_syncnorm.h): this clone's (mean, M2) per
+  (group, channel), one all-gather, Chan's rule in rank order -- the same bits on every clone."""
+  n, h, w, c = y.shape
+  dev = y.device
+  ws = torch.empty(n * _lib.load().tg_norm_chunks(n, h, w) * 2 * c, dtype=torch.float32, device=dev)
+  moments = torch.empty((n, 3, c), dtype=torch.float32, device=dev)      # mean as an fp32 pair, M2
+  call('tg_norm_moments', _p(y), _p(moments), _p(ws), n, h, w, c, _dt(y), _stream(),
+       work=('sync_moments' + _shape_tag(y), 0, y.numel() * _esize(y)))
+  gathered = replicas.gather(moments)
+  mean = torch.empty(n * c, dtype=torch.float32, device=dev)
+  rstd = torch.empty(n * c, dtype=torch.float32, device=dev)
+  call('tg_norm_moments_merge', _p(gathered), replicas.size, h * w, _p(mean), _p(rstd), n, c, eps, _stream(),
+       work=('sync_merge' + _shape_tag(y), 0, gathered.numel() * 4))
+  return mean, rstd
+
+
+def instance_stats(y, eps, replicas=None):
+  """(mean, rstd), fp32 [n*c], of y[n,h,w,c] over (h,w): biased variance, rstd = rsqrt(var + eps).  No autograd.
+  ``replicas`` (dp.ReplicaGather): over (h,w) of every clone's y -- all clones hold the same number of pixels."""
   _chk(y)
+  if replicas is not None:
+    return _sync_stats(y, eps, replicas)
   n, h, w, c = y.shape
   mean = torch.empty(n * c, dtype=torch.float32, device=y.device)
   rstd = torch.empty(n * c, dtype=torch.float32, device=y.device)
@@ -1511,6 +1531,82 @@ class NormActPoolFn(torch.autograd.Function):
     return _norm_act_backward(ctx, gz, gzp) + (None, None)
 
 
+class SyncNormActFn(torch.autograd.Function):
+  """NormActFn / NormActPoolFn with the statistics of every group taken over the pixels of ALL clones
+  (Config.cross_replica_norm; include/twingan_hip_syncnorm.h): what one clone would compute on the clones' batches
+  concatenated along the group's pixels.  Forward: moments -> all-gather -> merge -> tg_norm_act_fwd (+ tg_pool2x2_fwd for
+  ``pool``: (z, z_pooled)); with ``stats`` (batch renorm: the caller's instance_stats(y, eps, replicas), already merged)
+  the forward has nothing to gather.  Backward: this clone's S1 / S2 -> all-gather -> apply with the sums and the pixel
+  count of all clones.  The parameter gradients (1-D, gradient sink, or [n, c] rows) are this clone's sums: the trainer's
+  gradient all-reduce adds the clones'.  Two collectives per layer and step, issued in forward / autograd order."""
+
+  @staticmethod
+  def forward(ctx, y, gamma, beta, gamma2, beta2, split, flags, in_eps, pn_eps, alpha, ema, stats, replicas, pool):
+    _chk(y, gamma, beta, gamma2, beta2)
+    n, h, w, c = y.shape
+    split = n if gamma2 is None else int(split)
+    per_image = gamma.dim() == 2
+    if per_image:
+      assert stats is not None and tuple(gamma.shape) == (n, c) and tuple(beta.shape) == (n, c) and gamma2 is None
+      mean, rstd = stats
+    else:
+      mean, rstd = _sync_stats(y, in_eps, replicas)
+    z = torch.empty_like(y)
+    s = torch.empty(n * h * w, dtype=torch.float32, device=y.device) if (flags & NF_PIXNORM) else None
+    call('tg_norm_act_fwd', _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2), _p(beta2), split,
+         1 if per_image else 0, _p(z), _p(s), n, h, w, c, flags, alpha, pn_eps, _dt(y), _stream(),
+         work=('norm_act_fwd' + _shape_tag(y), 0, 2 * y.numel() * _esize(y)))
+    if ema is not None and not per_image:
+      _ema_update(mean, rstd, n, c, split, in_eps, ema)
+    ctx.flags, ctx.alpha, ctx.split, ctx.per_image, ctx.replicas = flags, alpha, split, per_image, replicas
+    ctx.save_for_backward(y, mean, rstd, gamma, beta, gamma2, beta2, s)
+    if not pool:
+      return z
+    zp = torch.empty((n, h // 2, w // 2, c), dtype=y.dtype, device=y.device)
+    call('tg_pool2x2_fwd', _p(z), _p(zp), n, h, w, c, 0.25, _dt(z), _stream(),
+         work=('pool_fwd' + _shape_tag(z), 0, int(1.25 * z.numel()) * _esize(z)))
+    ctx.set_materialize_grads(False)
+    return z, zp
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, gz, gzp=None):
+    if gz is None and gzp is None:
+      return (None,) * 14
+    y, mean, rstd, gamma, beta, gamma2, beta2, s = ctx.saved_tensors
+    gz = gz.contiguous() if gz is not None else None
+    gzp = gzp.contiguous() if gzp is not None else None
+    n, h, w, c = y.shape
+    dev = y.device
+    params = [gamma, beta] + ([gamma2, beta2] if gamma2 is not None else [])
+    per_image = ctx.per_image
+    sinks = [None if per_image else GradSink.get(q) for q in params]
+    sunk = all(t is not None for t in sinks)
+    if _State.skip_param_grads:
+      outs = [None] * 4
+    elif per_image:
+      outs = [torch.empty((n, c), dtype=torch.float32, device=dev) for _ in params] + [None, None]
+    elif sunk:
+      outs = sinks + [None] * (4 - len(sinks))
+    else:
+      outs = [torch.empty(c, dtype=torch.float32, device=dev) for _ in params] + [None] * (4 - len(params))
+    ws = torch.empty(n * _lib.load().tg_norm_chunks(n, h, w) * 2 * c, dtype=torch.float32, device=dev)
+    local = torch.empty((n, 2, c), dtype=torch.float32, device=dev)
+    reads = 2 + (0.25 if gzp is not None else 0) - (0 if gz is not None else 1)
+    call('tg_norm_act_bwd_sums', _p(gz), _p(gzp), _p(y), _p(s), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2), _p(beta2),
+         ctx.split, 1 if per_image else 0, _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(ws), _p(local), n, h, w, c,
+         ctx.flags, ctx.alpha, 1 if (sunk and not _State.skip_param_grads) else 0, _dt(y), _stream(),
+         work=('sync_bwd_sums' + _shape_tag(y), 0, int(reads * y.numel()) * _esize(y)))
+    gathered = ctx.replicas.gather(local)
+    gy = torch.empty_like(y)
+    call('tg_norm_act_bwd_apply', _p(gz), _p(gzp), _p(y), _p(s), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2),
+         _p(beta2), ctx.split, 1 if per_image else 0, _p(gy), _p(gathered), ctx.replicas.size, n, h, w, c, ctx.flags,
+         ctx.alpha, _dt(y), _stream(), work=('sync_bwd_apply' + _shape_tag(y), 0, int((reads + 1) * y.numel()) * _esize(y)))
+    if sunk or _State.skip_param_grads:
+      outs = [None] * 4
+    return (gy, outs[0], outs[1], outs[2], outs[3]) + (None,) * 9
+
+
 _CONST = {}
 
 
@@ -1611,13 +1707,19 @@ def layer_norm_act(y, gamma, beta, lrelu=True, pixel_norm=True, ln_eps=1e-12, pn
 
 
 def norm_act(y, gamma, beta, lrelu=True, pixel_norm=True, in_eps=1e-6, pn_eps=1e-6, alpha=LRELU_ALPHA, gamma2=None,
-             beta2=None, split=None, pool=False, ema=None, stats=None, conv_stats=None):
+             beta2=None, split=None, pool=False, ema=None, stats=None, conv_stats=None, replicas=None):
   """Statistics are per leading index of ``y`` (instance norm: one image; batch norm: the caller passes the view
   [passes, B*H, W, C] so that each batched pass is one statistic group).  ``pool``: also return the 2x2
   average-pooled output -> (z, z_pooled).  ``ema``: (decay, [(moving_mean, moving_var) per domain]) to update.
   Batch renorm: ``gamma`` / ``beta`` are [n, c] (one effective r*gamma, d*gamma+beta row per statistic group,
-  ordinary differentiable tensors) and ``stats`` = instance_stats(y, eps) computed by the caller."""
+  ordinary differentiable tensors) and ``stats`` = instance_stats(y, eps) computed by the caller.
+  ``replicas`` (dp.ReplicaGather; the batch normalisers under Config.cross_replica_norm): every group's statistics, and
+  the backward through them, cover the group's pixels on all clones (SyncNormActFn); ``stats`` then come from
+  instance_stats(y, eps, replicas)."""
   flags = (NF_LRELU if lrelu else 0) | (NF_PIXNORM if pixel_norm else 0)
+  if replicas is not None:
+    return SyncNormActFn.apply(y, gamma, beta, gamma2, beta2, split, flags, in_eps, pn_eps, alpha, ema, stats, replicas,
+                               bool(pool))
   fn = NormActPoolFn if pool else NormActFn
   if conv_stats is not None and (gamma.dim() != 1 or stats is not None):
     conv_stats = None      # per-image parameter rows take their statistics from the caller

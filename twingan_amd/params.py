@@ -37,9 +37,10 @@ def mbstd_cpad(c):
 
 class _ParamDict(dict):
   """name -> parameter tensor; ``state`` holds the non-trainable variables (BatchNorm moving statistics); ``pairs`` the
-  stacked [2, ...] views of the two discriminators' twin variables (ParamStore.build)."""
+  stacked [2, ...] views of the two discriminators' twin variables (ParamStore.build); ``replicas`` is set by the trainer."""
   state = None
   pairs = None
+  replicas = None      # dp.ReplicaGather when the batch normalisers take their statistics over all clones (Config.cross_replica_norm)
 
 
 class ParamStore:

@@ -272,6 +272,12 @@ def maybe_resblock(P, blk, input_layer, out_channels, conv2d_out, cfg, is_discri
   return ops.add(sc, conv2d_out)
 
 
+def _replicas(P):
+  """The clones' gather (dp.ReplicaGather) when the trainer runs cross-replica batch statistics
+  (Config.cross_replica_norm with more than one clone), else None: the batch normalisers' statistics are the clone's own."""
+  return getattr(P, 'replicas', None)
+
+
 def _cond_rows(P, scope, ns, cond, segments):
   """Per-image normaliser parameters from a style embedding (libs/instance_norm.py:93-120; libs/batch_norm.py:34-38):
   gamma = 1 + FC(cond; '<scope>/<norm>/gamma_<d>'), beta = FC(cond; '.../beta_<d>') with the FC of each image's domain.
@@ -390,7 +396,7 @@ def _ge_conv(P, scope, x, domain, cfg, k=3, padding='SAME', activation=True, pix
              for d in ((d0, d1) if d1 else (d0,))]
     ema = (0.999, pairs)
   out = ops.norm_act(yv, g0, b0, lrelu=activation, pixel_norm=pn, in_eps=1e-3, gamma2=g1, beta2=b1,
-                     split=None if split is None else split * passes // n, pool=pool, ema=ema)
+                     split=None if split is None else split * passes // n, pool=pool, ema=ema, replicas=_replicas(P))
   if pool:
     return out[0].view(n, h, w, c), out[1].view(n, h // 2, w // 2, c)
   return out.view(n, h, w, c)
@@ -419,7 +425,7 @@ def _cond_batch_norm(P, scope, y, cond, segs, passes, activation, pn, pool, cfg)
   split_v = None if len(segs) == 1 else segs[0][2] * passes // n
   yhat = ops.norm_act(y.view(passes, (n // passes) * h, w, c), one, zero, lrelu=False, pixel_norm=False, in_eps=BN_EPS,
                       gamma2=one if split_v is not None else None, beta2=zero if split_v is not None else None,
-                      split=split_v, ema=ema).view(n, h, w, c)
+                      split=split_v, ema=ema, replicas=_replicas(P)).view(n, h, w, c)
   # the per-image affine, LeakyReLU, pixel norm (and pool) after it: the fused kernel with constant statistics
   return ops.affine_act(yhat, g_rows, b_rows, lrelu=activation, pixel_norm=pn, pool=pool)
 
@@ -465,7 +471,8 @@ def _batch_renorm(P, scope, yv, domain, activation, pn, pool, cond_rows=None, im
   import torch
   d0, d1, split, passes = domain
   st = P.state
-  mean, rstd = ops.instance_stats(yv, BN_EPS)
+  rep = _replicas(P)
+  mean, rstd = ops.instance_stats(yv, BN_EPS, replicas=rep)
   c = yv.shape[3]
   mean_p, rstd_p = mean.view(passes, c), rstd.view(passes, c)
   rmax, rmin, dmax = st['renorm/rmax'], st['renorm/rmin'], st['renorm/dmax']
@@ -498,11 +505,12 @@ def _batch_renorm(P, scope, yv, domain, activation, pn, pool, cond_rows=None, im
     b_rows.append(dd * gamma + beta)
   if cond_rows is not None:
     one = torch.ones(passes, c, dtype=torch.float32, device=yv.device)
-    yhat = ops.norm_act(yv, one, torch.zeros_like(one), lrelu=False, pixel_norm=False, in_eps=BN_EPS, stats=(mean, rstd))
+    yhat = ops.norm_act(yv, one, torch.zeros_like(one), lrelu=False, pixel_norm=False, in_eps=BN_EPS, stats=(mean, rstd),
+                        replicas=rep)
     return ops.affine_act(yhat.view(image_shape), torch.cat(g_rows), torch.cat(b_rows), lrelu=activation, pixel_norm=pn,
                           pool=pool)
   return ops.norm_act(yv, torch.stack(g_rows), torch.stack(b_rows), lrelu=activation, pixel_norm=pn, in_eps=BN_EPS,
-                      pool=pool, stats=(mean, rstd))
+                      pool=pool, stats=(mean, rstd), replicas=rep)
 
 
 def maybe_gdrop(P, x, cfg, in_ch=None):

@@ -20,7 +20,7 @@ import torch
 
 from . import ops, pggan
 from ._lib import call
-from .dp import GradReducer, loss_scale_for_clones
+from .dp import GradReducer, ReplicaGather, loss_scale_for_clones
 from .ops import PackCache
 from .params import ParamStore, declare_twingan
 
@@ -453,6 +453,9 @@ class Trainer:
     """``overlap``: cut the backward into segments and start the clone all-reduce of each segment's finished
     gradients while the next one runs (None: whenever there is more than one clone; True forces the segmented
     schedule for a single clone too -- same results, used by the tests)."""
+    if cfg.cross_replica_norm and world_size > 1 and use_graph:
+      raise ValueError('cross_replica_norm with %d clones runs the eager step: the collectives inside every normaliser '
+                       'are not captured into the step hipGraphs (use_graph=False)' % world_size)
     if cfg.spectral_norm and cfg.domain_streams:
       # Spectral norm keeps the discriminators on one stream.  The per-run normalised kernels are computed (and their
       # packs rebuilt) on the main stream by pggan.prepare_run before anything forks, so two streams are SAFE
@@ -480,6 +483,11 @@ class Trainer:
     store.set_optimizer(cfg)                                   # --optimizer: the slots build() allocates
     self.store = store.build(seed)
     self.P = self.store.P
+    # Config.cross_replica_norm: the batch normalisers of this clone take their statistics (and the backward through them)
+    # over the batches of all clones -- two small all-gathers per normalised layer, issued in forward / autograd order on
+    # the reducer's process group.  A single clone takes the usual route.
+    self.replicas = ReplicaGather(world_size, process_group) if (cfg.cross_replica_norm and world_size > 1) else None
+    self.P.replicas = self.replicas
     self.n_critic_counter = 0       # image_generation.py:622-623
     self.global_step = 0            # advanced once per n_critic cycle, see _advance_counters
     self.adam_t = 0                 # one shared optimizer: beta powers advance on every apply (:554-561)
