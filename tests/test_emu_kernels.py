@@ -3,8 +3,8 @@ MFMA / DPP / permlane swaps / transposing LDS reads emulated), run through the p
 oracles as on the GPU.  What this checks without a GPU is the kernels' LOGIC -- index arithmetic, LDS staging, lane exchanges,
 operand layouts, epilogues, the host-side dispatch -- not timing and not the hardware's rounding inside an MFMA.
 
-The subset in tests/hipemu/fast_subset.txt is every case of tests/test_gpu_ops.py that runs in under a second over the
-emulated kernels (all operator families; the large shapes are left to `TG_EMU=1 python -m pytest tests/test_gpu_ops.py -m gpu`,
+The subset in tests/hipemu/fast_subset.txt is every case of tests/test_gpu_ops.py (and of tests/test_gpu_wgrad_split.py) that
+runs in under a second over the emulated kernels (all operator families; the large shapes are left to `TG_EMU=1 python -m pytest tests/test_gpu_ops.py -m gpu`,
 which passes all but four of its cases -- those compare device libm bit patterns, the CUDA-tensor check and RCCL).  It
 runs in a child process: the harness redirects torch's CUDA entry points process-wide.
 """
@@ -59,6 +59,18 @@ def test_thin_output_kernels_over_the_emulated_kernels():
             '(thin_output_kernel_matches and 16-16-dtype0) or spectral_norm_of_many'], timeout=2400)
   assert r.returncode == 0, r.stdout[-3000:]
   assert ' passed' in r.stdout[-3000:]
+
+
+def test_filter_gradient_split_cells_over_the_emulated_kernels():
+  """tests/test_gpu_wgrad_split.py on the host: the rows of its tables that the emulation walks in a minute or two each (the
+  sub-second ones are in fast_subset.txt) -- ragged last ranges, the segment boundary inside a range, odd batches on the
+  pair-of-images kernel, the XCD decode, the concat input, the scalar slab stores.  Rows 19-21, 23, 24 and the
+  first-generation kernel's 512-channel rows are left to the GPU."""
+  r = _run(['tests/test_gpu_wgrad_split.py', '-n', '8', '-k',
+            'not (r19_ or r20_ or r21_ or r23_ or r24_ or first_generation)'], timeout=2400)
+  tail = r.stdout[-3000:]
+  assert r.returncode == 0, tail
+  assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail.split('passed')[-1], tail
 
 
 def test_wrapper_bounds_cases_over_the_emulated_kernels():
