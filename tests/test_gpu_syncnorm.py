@@ -134,6 +134,44 @@ def test_merge_is_rank_ordered_and_refuses_bad_counts():
       O.call('tg_norm_moments_merge', O._p(g), R, count, O._p(a[0]), O._p(a[1]), 2, 5, BN_EPS, O._stream())
 
 
+def test_only_the_split_route_refuses_constant_statistics():
+  """The backward entry points share their argument checks, not this one: constant statistics (NF_NOSTATS: ops.pixel_norm,
+  ops.affine_act) have no sums to share, so tg_norm_act_bwd_sums / tg_norm_act_bwd_apply refuse them, while the fused
+  tg_norm_act_bwd runs them.  A pooled gradient over an odd height is refused by both routes."""
+  import twingan_amd.ops as O
+  from twingan_amd import _lib
+  lib = _lib.load()
+
+  def routes(h, w, pooled, flags):
+    n, c = 1, 8
+    rng = np.random.RandomState(17)
+    t = lambda *shape: torch.from_numpy(rng.randn(*shape).astype(np.float32)).to(dev())
+    y, gz, gy = t(n, h, w, c), t(n, h, w, c), torch.full((n, h, w, c), float('nan'), device=dev())
+    gzp = t(n, h // 2, w // 2, c) if pooled else None
+    one, zero = torch.ones(n * c, device=dev()), torch.zeros(n * c, device=dev())
+    ws, local = _f32(n * lib.tg_norm_chunks(n, h, w) * 2 * c), _f32((n, 2, c))
+    common = (O._p(gz), O._p(gzp), O._p(y), None, O._p(zero), O._p(one), O._p(one), O._p(zero), None, None, n)
+    fused = lambda: O.call('tg_norm_act_bwd', *common, O._p(gy), 0, None, None, None, None, O._p(ws), n, h, w, c, flags, 0.2, 0,
+                           O._dt(y), O._stream())
+    sums = lambda: O.call('tg_norm_act_bwd_sums', *common, 0, None, None, None, None, O._p(ws), O._p(local), n, h, w, c, flags,
+                          0.2, 0, O._dt(y), O._stream())
+    apply_ = lambda: O.call('tg_norm_act_bwd_apply', *common, 0, O._p(gy), O._p(local.view(1, n, 2, c)), 1, n, h, w, c, flags,
+                            0.2, O._dt(y), O._stream())
+    return fused, sums, apply_, gy
+
+  fused, sums, apply_, gy = routes(2, 2, False, _lib.NF_NOSTATS)
+  for entry in (sums, apply_):
+    with pytest.raises(_lib.TgError, match='NF_NOSTATS'):
+      entry()
+  assert fused() == 0
+  torch.cuda.synchronize()
+  assert torch.isfinite(gy).all()
+  fused, sums, apply_, _ = routes(3, 2, True, 0)
+  for entry in (fused, sums, apply_):
+    with pytest.raises(_lib.TgError, match='even h, w'):
+      entry()
+
+
 # ------------------------------------------------------------------------------------------------ 2. the split backward
 def _near_zero(r64, r32):
   """tests/test_gpu_ops.py _near_zero: where the float64 pre-activation is inside its own bound 2^-24 |u| + 16 E32(u)."""

@@ -10,6 +10,7 @@
 // norm is a butterfly shuffle inside the wave.
 #include "tg_common.h"
 #include "../../include/twingan_hip_syncnorm.h"
+#include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -994,6 +995,113 @@ static void norm_chunks(int n, int hw, int* chunks, int* ppb) {
   *chunks = (hw + pp - 1) / pp;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The launch plan of the fused normaliser: geometry, path, flag dispatch and the two backward passes, shared by the forward
+// launchers and by both routes of the backward (fused: tg_norm_act_bwd; cross-replica: tg_norm_act_bwd_sums -> all-gather ->
+// tg_norm_act_bwd_apply).  What differs between the routes stays in their entry points.
+// ------------------------------------------------------------------------------------------------
+// pixel range of one block of a streaming pass: ~2048 blocks over the `units` (pixels; 2x2 blocks of the pooled forward) of
+// each of n images, at least floor_ppb units each
+static void norm_stream_chunks(int n, int units, int floor_ppb, int* chunks2, int* ppb2) {
+  int ch = (2048 + n - 1) / n;
+  int pp = (units + ch - 1) / ch;
+  if (pp < floor_ppb) pp = floor_ppb;
+  *ppb2 = pp;
+  *chunks2 = (units + pp - 1) / pp;
+}
+
+// *vec: c runs on the vector path (one 16-byte channel vector per thread, the c / VN threads of a pixel adjacent lanes of one
+// wave), else on the scalar path; and what neither can run.  Pixel norm reduces over the lanes of a pixel: vector path only, and
+// it keeps its scale in pn_scale (no_scale_code: the forward calls a missing one a bad argument, the backward unsupported).
+// scalar_c_max: the widest row the caller's scalar kernel holds.
+template <typename T>
+static int norm_path(const char* who, int c, int flags, const float* pn_scale, int no_scale_code, int scalar_c_max, bool* vec) {
+  constexpr int VN = Vec16<T>::N;
+  *vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
+  if (flags & NF_PIXNORM) {
+    TG_CHECK(*vec, TG_ENOSUP, "%s: pixel norm needs c (%d) = %d * 2^k <= %d", who, c, VN, 64 * VN);
+    TG_CHECK(pn_scale, no_scale_code, "%s: pixel norm needs pn_scale", who);
+  }
+  TG_CHECK(*vec || c <= scalar_c_max, TG_ENOSUP, "%s: scalar path needs c <= %d (got %d)", who, scalar_c_max, c);
+  return TG_OK;
+}
+
+// f(V, FL): the kernels' template arguments of this call as std::integral_constant values.  Vector path: V = 16 bytes of T and
+// the LeakyReLU / pixel-norm bits of `flags` fixed at compile time; the scalar path and the fp32 exact-parity path keep all of
+// `flags` at run time, FL = -1 (see norm_act_bwd1_kernel).
+template <typename T, int FL>
+using NormFL = std::integral_constant<int, exact_path<T>() ? -1 : FL>;
+
+template <typename T, typename F>
+static void norm_variant(bool vec, int flags, F&& f) {
+  using V = std::integral_constant<int, Vec16<T>::N>;
+  if (!vec) return f(std::integral_constant<int, 1>(), std::integral_constant<int, -1>());
+  switch (flags & 3) {
+    case 0: f(V(), NormFL<T, 0>()); break;
+    case 1: f(V(), NormFL<T, 1>()); break;
+    case 2: f(V(), NormFL<T, 2>()); break;
+    default: f(V(), NormFL<T, 3>()); break;
+  }
+}
+
+// what every pass of the backward reads: an entry point's arguments
+struct NormBwd {
+  const void *gz, *gz_pooled, *y;
+  const float *pn_scale, *mean, *rstd, *gamma, *beta, *gamma2, *beta2;
+  int split, pstride, n, h, w, c, flags;
+  float alpha;
+  hipStream_t s;
+};
+
+// the checks the backward entry points share; outs_ok: the entry point's own buffers are there.  Settles a.split.
+static int norm_bwd_checks(const char* who, NormBwd& a, bool outs_ok, int accumulate) {
+  TG_CHECK((a.gz || a.gz_pooled) && a.y && a.mean && a.rstd && a.gamma && a.beta && outs_ok && a.n > 0 && a.h > 0 && a.w > 0 &&
+               a.c > 0,
+           TG_EINVAL, "%s: bad arguments", who);
+  TG_CHECK(!a.gz_pooled || (a.h % 2 == 0 && a.w % 2 == 0), TG_EINVAL, "%s: pooled gradient needs even h, w", who);
+  if (!a.gamma2 || !a.beta2) a.split = a.n;
+  TG_CHECK(a.split >= 0 && a.split <= a.n, TG_EINVAL, "%s: split %d outside [0, %d]", who, a.split, a.n);
+  TG_CHECK(!a.pstride || !accumulate, TG_EINVAL, "%s: per-image parameter gradients are written, not added", who);
+  return TG_OK;
+}
+
+// pass 1: sums[n][chunk][2][c], one row per block of norm_chunks; returns the chunks per image
+template <typename T>
+static int norm_bwd_pass1(const NormBwd& a, bool vec, float* sums) {
+  const int hw = a.h * a.w;
+  int chunks, ppb;
+  norm_chunks(a.n, hw, &chunks, &ppb);
+  norm_variant<T>(vec, a.flags, [&](auto v, auto fl) {
+    hipLaunchKernelGGL((norm_act_bwd1_kernel<T, decltype(v)::value, decltype(fl)::value>), dim3(chunks, a.n), dim3(256),
+                       2 * (size_t)a.c * sizeof(float), a.s, (const T*)a.gz, (const T*)a.gz_pooled, a.w, (const T*)a.y,
+                       a.pn_scale, a.mean, a.rstd, a.gamma, a.beta, a.gamma2, a.beta2, a.split, a.pstride, sums, hw, a.c,
+                       a.flags, a.alpha, ppb);
+  });
+  return chunks;
+}
+
+struct NormParamGrads {
+  float *ggamma, *gbeta, *ggamma2, *gbeta2;
+};
+
+// pass 2: gy from `rows` rows of sums per image.  SYNC = false: part = pass 1's sums, rows = its chunks; pg and `sink` as
+// norm_act_bwd2_part_kernel takes them.  SYNC: part = gathered[rows = replicas][n][2][c] over gcount pixels per group; the
+// parameter gradients are not this pass's (pg = {}, sink = 0).
+template <typename T, bool SYNC>
+static void norm_bwd_pass2(const NormBwd& a, bool vec, void* gy, const float* part, int rows, NormParamGrads pg, int sink,
+                           int gcount) {
+  const int hw = a.h * a.w;
+  int chunks2, ppb2;
+  norm_stream_chunks(a.n, hw, min_ppb(hw), &chunks2, &ppb2);
+  norm_variant<T>(vec, a.flags, [&](auto v, auto fl) {
+    hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, decltype(v)::value, decltype(fl)::value, SYNC>), dim3(chunks2, a.n),
+                       dim3(256), 2 * (size_t)a.c * sizeof(float), a.s, (const T*)a.gz, (const T*)a.gz_pooled, a.w,
+                       (const T*)a.y, a.pn_scale, a.mean, a.rstd, a.gamma, a.beta, a.gamma2, a.beta2, a.split, a.pstride,
+                       (T*)gy, part, rows, pg.ggamma, pg.gbeta, pg.ggamma2, pg.gbeta2, sink, hw, a.c, a.flags, a.alpha, ppb2,
+                       gcount);
+  });
+}
+
 extern "C" {
 
 int tg_norm_chunks(int n, int h, int w) {
@@ -1025,13 +1133,6 @@ int tg_instance_norm_partials(const void* y, float* partials, int n, int h, int 
   return TG_OK;
 }
 
-// the forward launch of the vector path with the LeakyReLU / pixel-norm bits FL_ fixed at compile time (uses the locals
-// of norm_act_fwd_partials_impl)
-#define TG_NF_LAUNCH(POOL_, FL_)                                                                                         \
-  hipLaunchKernelGGL((norm_act_fwd_part_kernel<T, VN, POOL_, exact_path<T>() ? -1 : FL_>), dim3(chunks2, n), dim3(256), lds, \
-                     (hipStream_t)stream, (const T*)y, partials, chunks, mean, rstd, gamma, beta, gamma2, beta2, split,  \
-                     (T*)z, (T*)z_pooled, w, pn_scale, hw, c, flags, alpha, in_eps, pn_eps, ppb)
-
 static int norm_act_fwd_partials_impl(const void* y, const float* partials, int part_chunks, float* mean, float* rstd,
                                       const float* gamma, const float* beta, const float* gamma2, const float* beta2,
                                       int split, void* z, void* z_pooled, float* pn_scale, int n, int h, int w, int c,
@@ -1046,42 +1147,21 @@ static int norm_act_fwd_partials_impl(const void* y, const float* partials, int 
   int chunks, ppb_s;
   norm_chunks(n, hw, &chunks, &ppb_s);
   if (part_chunks > 0) chunks = part_chunks;      // partial sums of a producer with its own chunking
-  const int units = z_pooled ? hw / 4 : hw;            // the pooled variant walks 2x2 blocks (4 pixels each)
-  int chunks2 = (2048 + n - 1) / n;                    // ~2048 blocks for the streaming pass
-  int ppb = (units + chunks2 - 1) / chunks2;
-  const int floor_ppb = z_pooled ? 16 : min_ppb(hw);
-  if (ppb < floor_ppb) ppb = floor_ppb;
-  chunks2 = (units + ppb - 1) / ppb;
-  const size_t lds = 2 * (size_t)c * sizeof(float);
+  int chunks2, ppb;      // the pooled variant walks 2x2 blocks (4 pixels each)
+  norm_stream_chunks(n, z_pooled ? hw / 4 : hw, z_pooled ? 16 : min_ppb(hw), &chunks2, &ppb);
   TG_DISPATCH_DTYPE(dtype, "tg_norm_act_fwd_partials", {
-    constexpr int VN = Vec16<T>::N;
-    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
-    if (flags & NF_PIXNORM) {
-      TG_CHECK(vec, TG_ENOSUP, "tg_norm_act_fwd_partials: pixel norm needs c (%d) = %d * 2^k <= %d", c, VN, 64 * VN);
-      TG_CHECK(pn_scale, TG_EINVAL, "tg_norm_act_fwd_partials: pixel norm needs pn_scale");
-    }
-    if (vec) {
-      switch ((flags & 3) | (z_pooled ? 4 : 0)) {
-        case 0: TG_NF_LAUNCH(false, 0); break;
-        case 1: TG_NF_LAUNCH(false, 1); break;
-        case 2: TG_NF_LAUNCH(false, 2); break;
-        case 3: TG_NF_LAUNCH(false, 3); break;
-        case 4: TG_NF_LAUNCH(true, 0); break;
-        case 5: TG_NF_LAUNCH(true, 1); break;
-        case 6: TG_NF_LAUNCH(true, 2); break;
-        default: TG_NF_LAUNCH(true, 3); break;
-      }
-    } else {
-      TG_CHECK(c <= 256, TG_ENOSUP, "tg_norm_act_fwd_partials: scalar path needs c <= 256 (got %d)", c);
-      if (z_pooled)
-        hipLaunchKernelGGL((norm_act_fwd_part_kernel<T, 1, true>), dim3(chunks2, n), dim3(256), lds, (hipStream_t)stream,
-                           (const T*)y, partials, chunks, mean, rstd, gamma, beta, gamma2, beta2, split, (T*)z,
-                           (T*)z_pooled, w, pn_scale, hw, c, flags, alpha, in_eps, pn_eps, ppb);
-      else
-        hipLaunchKernelGGL((norm_act_fwd_part_kernel<T, 1>), dim3(chunks2, n), dim3(256), lds, (hipStream_t)stream,
-                           (const T*)y, partials, chunks, mean, rstd, gamma, beta, gamma2, beta2, split, (T*)z,
-                           (T*)nullptr, w, pn_scale, hw, c, flags, alpha, in_eps, pn_eps, ppb);
-    }
+    bool vec;
+    if (int rc = norm_path<T>("tg_norm_act_fwd_partials", c, flags, pn_scale, TG_EINVAL, 256, &vec)) return rc;
+    norm_variant<T>(vec, flags, [&](auto v, auto fl) {
+      auto launch = [&](auto pool) {
+        hipLaunchKernelGGL((norm_act_fwd_part_kernel<T, decltype(v)::value, decltype(pool)::value, decltype(fl)::value>),
+                           dim3(chunks2, n), dim3(256), 2 * (size_t)c * sizeof(float), (hipStream_t)stream, (const T*)y,
+                           partials, chunks, mean, rstd, gamma, beta, gamma2, beta2, split, (T*)z, (T*)z_pooled, w, pn_scale,
+                           hw, c, flags, alpha, in_eps, pn_eps, ppb);
+      };
+      if (z_pooled) launch(std::true_type());
+      else launch(std::false_type());
+    });
   });
   TG_LAUNCH_CHECK("tg_norm_act_fwd_partials");
   return TG_OK;
@@ -1151,11 +1231,8 @@ int tg_norm_act_fwd(const void* y, const float* mean, const float* rstd, const f
   const int64_t npix = (int64_t)n * h * w;
   TG_DISPATCH_DTYPE(dtype, "tg_norm_act_fwd", {
     constexpr int VN = Vec16<T>::N;
-    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
-    if (flags & NF_PIXNORM) {
-      TG_CHECK(vec, TG_ENOSUP, "tg_norm_act_fwd: pixel norm needs c (%d) = %d * 2^k <= %d", c, VN, 64 * VN);
-      TG_CHECK(pn_scale, TG_EINVAL, "tg_norm_act_fwd: pixel norm needs pn_scale");
-    }
+    bool vec;      // the grid-stride kernel's scalar path takes any c
+    if (int rc = norm_path<T>("tg_norm_act_fwd", c, flags, pn_scale, TG_EINVAL, INT_MAX, &vec)) return rc;
     if (vec) {
       // grid stride must be a multiple of the group size so pixel groups stay in one wave: 256 % (c/VN) == 0 holds
       hipLaunchKernelGGL((norm_act_fwd_kernel<T, VN>), dim3(tg_grid_for(npix * (c / VN), 256)), dim3(256), 0,
@@ -1171,69 +1248,30 @@ int tg_norm_act_fwd(const void* y, const float* mean, const float* rstd, const f
   return TG_OK;
 }
 
-// the two backward launches of the vector path with the LeakyReLU / pixel-norm bits FL_ fixed at compile time (uses the
-// locals of tg_norm_act_bwd)
-#define TG_NB_LAUNCH(FL_)                                                                                                  \
-  do {                                                                                                                     \
-    hipLaunchKernelGGL((norm_act_bwd1_kernel<T, VN, exact_path<T>() ? -1 : FL_>), dim3(chunks, n), dim3(256), lds, s, (const T*)gz, \
-                       (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split,       \
-                       pstride, sums, hw, c, flags, alpha, ppb);                                                           \
-    hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, VN, exact_path<T>() ? -1 : FL_>), dim3(chunks2, n), dim3(256), lds, s, (const T*)gz, \
-                       (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split,       \
-                       pstride, (T*)gy, sums, chunks, ggamma, gbeta, ggamma2, gbeta2, sink, hw, c, flags, alpha, ppb2, 0); \
-  } while (0)
-
+// the fused route: pass 1, pass 2 over pass 1's sums, and the parameter gradients from the same sums
 int tg_norm_act_bwd(const void* gz, const void* gz_pooled, const void* y, const float* pn_scale, const float* mean,
                     const float* rstd,
                     const float* gamma, const float* beta, const float* gamma2, const float* beta2, int split, void* gy,
                     int per_image_params, float* ggamma, float* gbeta, float* ggamma2, float* gbeta2, float* sums, int n,
                     int h, int w, int c, int flags, float alpha, int accumulate, int dtype, void* stream) {
-  const int pstride = per_image_params ? c : 0;
-  TG_CHECK((gz || gz_pooled) && y && mean && rstd && gamma && beta && gy && sums && n > 0 && h > 0 && w > 0 && c > 0,
-           TG_EINVAL, "tg_norm_act_bwd: bad arguments");
-  TG_CHECK(!gz_pooled || (h % 2 == 0 && w % 2 == 0), TG_EINVAL, "tg_norm_act_bwd: pooled gradient needs even h, w");
-  if (!gamma2 || !beta2) split = n;
-  TG_CHECK(split >= 0 && split <= n, TG_EINVAL, "tg_norm_act_bwd: split %d outside [0, %d]", split, n);
-  hipStream_t s = (hipStream_t)stream;
-  const int hw = h * w;
-  const int64_t npix = (int64_t)n * hw;
-  int chunks, ppb;
-  norm_chunks(n, hw, &chunks, &ppb);
-  int chunks2 = (2048 + n - 1) / n;
-  int ppb2 = (hw + chunks2 - 1) / chunks2;
-  if (ppb2 < min_ppb(hw)) ppb2 = min_ppb(hw);
-  chunks2 = (hw + ppb2 - 1) / ppb2;
+  const char* who = "tg_norm_act_bwd";
+  NormBwd a = {gz, gz_pooled, y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, per_image_params ? c : 0, n, h, w, c,
+               flags, alpha, (hipStream_t)stream};
+  if (int rc = norm_bwd_checks(who, a, gy && sums, accumulate)) return rc;
   const bool want_params = ggamma || gbeta || ggamma2 || gbeta2;
-  TG_CHECK(!pstride || !accumulate, TG_EINVAL, "tg_norm_act_bwd: per-image parameter gradients are written, not added");
   int sink = (want_params && accumulate) ? 1 : 0;            // block (0, n) of pass 2 adds the image's sums
-  const size_t lds = 2 * (size_t)c * sizeof(float);
-  TG_DISPATCH_DTYPE(dtype, "tg_norm_act_bwd", {
+  int chunks = 0;
+  TG_DISPATCH_DTYPE(dtype, who, {
     if (sink && exact_grid<T>()) sink = 2;                   // ... in image order, by the domain's first image
-    constexpr int VN = Vec16<T>::N;
-    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
-    if (flags & NF_PIXNORM) {
-      TG_CHECK(vec && pn_scale, TG_ENOSUP, "tg_norm_act_bwd: pixel norm needs c (%d) = %d * 2^k and pn_scale", c, VN);
-    }
-    if (vec) {
-      switch (flags & 3) {
-        case 0: TG_NB_LAUNCH(0); break;
-        case 1: TG_NB_LAUNCH(1); break;
-        case 2: TG_NB_LAUNCH(2); break;
-        default: TG_NB_LAUNCH(3); break;
-      }
-    } else {
-      TG_CHECK(c <= 256, TG_ENOSUP, "tg_norm_act_bwd: scalar path needs c <= 256 (got %d)", c);
-      hipLaunchKernelGGL((norm_act_bwd1_kernel<T, 1>), dim3(chunks, n), dim3(256), lds, s, (const T*)gz,
-                         (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride, sums, hw, c, flags, alpha, ppb);
-      hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, 1>), dim3(chunks2, n), dim3(256), lds, s, (const T*)gz,
-                         (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split,
-                         pstride, (T*)gy, sums, chunks, ggamma, gbeta, ggamma2, gbeta2, sink, hw, c, flags, alpha, ppb2, 0);
-    }
+    bool vec;
+    if (int rc = norm_path<T>(who, c, flags, pn_scale, TG_ENOSUP, 256, &vec)) return rc;
+    chunks = norm_bwd_pass1<T>(a, vec, sums);
+    norm_bwd_pass2<T, false>(a, vec, gy, sums, chunks, NormParamGrads{ggamma, gbeta, ggamma2, gbeta2}, sink, 0);
   });
-  if (want_params && !sink && !pstride)
-    hipLaunchKernelGGL(norm_param_grads, dim3((c + 255) / 256, split < n ? 2 : 1), dim3(256), 0, s, sums, chunks, ggamma,
-                       gbeta, ggamma2, gbeta2, split, n, c, 0);
-  TG_LAUNCH_CHECK("tg_norm_act_bwd");
+  if (want_params && !sink && !a.pstride)
+    hipLaunchKernelGGL(norm_param_grads, dim3((c + 255) / 256, a.split < n ? 2 : 1), dim3(256), 0, a.s, sums, chunks, ggamma,
+                       gbeta, ggamma2, gbeta2, a.split, n, c, 0);
+  TG_LAUNCH_CHECK(who);
   return TG_OK;
 }
 
@@ -1265,112 +1303,58 @@ int tg_norm_moments_merge(const float* gathered, int replicas, int64_t count, fl
   return TG_OK;
 }
 
-// pass 1 of the vector path with the LeakyReLU / pixel-norm bits FL_ fixed at compile time (locals of tg_norm_act_bwd_sums)
-#define TG_NB1_LAUNCH(FL_)                                                                                                 \
-  hipLaunchKernelGGL((norm_act_bwd1_kernel<T, VN, exact_path<T>() ? -1 : FL_>), dim3(chunks, n), dim3(256), lds, s, (const T*)gz, \
-                     (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride,  \
-                     ws, hw, c, flags, alpha, ppb)
+// what only the cross-replica route refuses (after norm_bwd_checks: c > 0)
+static int norm_split_checks(const char* who, const NormBwd& a) {
+  TG_CHECK(!(a.flags & NF_NOSTATS), TG_EINVAL, "%s: constant statistics (NF_NOSTATS) have no sums to share", who);
+  TG_CHECK((int64_t)a.h * a.w < (1ll << 31) / a.c, TG_EINVAL, "%s: a group of %d x %d x %d elements does not fit 32-bit offsets",
+           who, a.h, a.w, a.c);
+  return TG_OK;
+}
 
+// the cross-replica route, first half: pass 1, this clone's sums per group (and its parameter gradients from them)
 int tg_norm_act_bwd_sums(const void* gz, const void* gz_pooled, const void* y, const float* pn_scale, const float* mean,
                          const float* rstd, const float* gamma, const float* beta, const float* gamma2, const float* beta2,
                          int split, int per_image_params, float* ggamma, float* gbeta, float* ggamma2, float* gbeta2,
                          float* ws, float* local, int n, int h, int w, int c, int flags, float alpha, int accumulate,
                          int dtype, void* stream) {
-  const int pstride = per_image_params ? c : 0;
-  TG_CHECK((gz || gz_pooled) && y && mean && rstd && gamma && beta && ws && local && n > 0 && h > 0 && w > 0 && c > 0,
-           TG_EINVAL, "tg_norm_act_bwd_sums: bad arguments");
-  TG_CHECK(!gz_pooled || (h % 2 == 0 && w % 2 == 0), TG_EINVAL, "tg_norm_act_bwd_sums: pooled gradient needs even h, w");
-  TG_CHECK(!(flags & NF_NOSTATS), TG_EINVAL, "tg_norm_act_bwd_sums: constant statistics (NF_NOSTATS) have no sums to share");
-  TG_CHECK((int64_t)h * w < (1ll << 31) / c, TG_EINVAL, "tg_norm_act_bwd_sums: a group of %d x %d x %d elements does not fit 32-bit offsets",
-           h, w, c);
-  TG_CHECK(!pstride || !accumulate, TG_EINVAL, "tg_norm_act_bwd_sums: per-image parameter gradients are written, not added");
-  if (!gamma2 || !beta2) split = n;
-  TG_CHECK(split >= 0 && split <= n, TG_EINVAL, "tg_norm_act_bwd_sums: split %d outside [0, %d]", split, n);
-  hipStream_t s = (hipStream_t)stream;
-  const int hw = h * w;
-  int chunks, ppb;
-  norm_chunks(n, hw, &chunks, &ppb);
-  const size_t lds = 2 * (size_t)c * sizeof(float);
-  TG_DISPATCH_DTYPE(dtype, "tg_norm_act_bwd_sums", {
-    constexpr int VN = Vec16<T>::N;
-    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
-    if (flags & NF_PIXNORM) {
-      TG_CHECK(vec && pn_scale, TG_ENOSUP, "tg_norm_act_bwd_sums: pixel norm needs c (%d) = %d * 2^k and pn_scale", c, VN);
-    }
-    if (vec) {
-      switch (flags & 3) {
-        case 0: TG_NB1_LAUNCH(0); break;
-        case 1: TG_NB1_LAUNCH(1); break;
-        case 2: TG_NB1_LAUNCH(2); break;
-        default: TG_NB1_LAUNCH(3); break;
-      }
-    } else {
-      TG_CHECK(c <= 256, TG_ENOSUP, "tg_norm_act_bwd_sums: scalar path needs c <= 256 (got %d)", c);
-      hipLaunchKernelGGL((norm_act_bwd1_kernel<T, 1>), dim3(chunks, n), dim3(256), lds, s, (const T*)gz, (const T*)gz_pooled, w,
-                         (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride, ws, hw, c, flags, alpha,
-                         ppb);
-    }
+  const char* who = "tg_norm_act_bwd_sums";
+  NormBwd a = {gz, gz_pooled, y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, per_image_params ? c : 0, n, h, w, c,
+               flags, alpha, (hipStream_t)stream};
+  if (int rc = norm_bwd_checks(who, a, ws && local, accumulate)) return rc;
+  if (int rc = norm_split_checks(who, a)) return rc;
+  int chunks = 0;
+  TG_DISPATCH_DTYPE(dtype, who, {
+    bool vec;
+    if (int rc = norm_path<T>(who, c, flags, pn_scale, TG_ENOSUP, 256, &vec)) return rc;
+    chunks = norm_bwd_pass1<T>(a, vec, ws);
   });
-  hipLaunchKernelGGL(norm_bwd_sums_final, dim3(n), dim3(1024), 2 * (size_t)c * sizeof(double), s, ws, chunks, local,
-                     pstride ? ggamma : nullptr, pstride ? gbeta : nullptr, c);
-  if (!pstride && (ggamma || gbeta || ggamma2 || gbeta2))
-    hipLaunchKernelGGL(norm_param_grads_local, dim3((c + 255) / 256, split < n ? 2 : 1), dim3(256), 0, s, local, ggamma, gbeta,
-                       ggamma2, gbeta2, split, n, c, accumulate ? 1 : 0);
-  TG_LAUNCH_CHECK("tg_norm_act_bwd_sums");
+  hipLaunchKernelGGL(norm_bwd_sums_final, dim3(n), dim3(1024), 2 * (size_t)c * sizeof(double), a.s, ws, chunks, local,
+                     a.pstride ? ggamma : nullptr, a.pstride ? gbeta : nullptr, c);
+  if (!a.pstride && (ggamma || gbeta || ggamma2 || gbeta2))
+    hipLaunchKernelGGL(norm_param_grads_local, dim3((c + 255) / 256, a.split < n ? 2 : 1), dim3(256), 0, a.s, local, ggamma,
+                       gbeta, ggamma2, gbeta2, a.split, n, c, accumulate ? 1 : 0);
+  TG_LAUNCH_CHECK(who);
   return TG_OK;
 }
 
-// pass 2 of the vector path in its SYNC form (locals of tg_norm_act_bwd_apply)
-#define TG_NB2S_LAUNCH(FL_)                                                                                                \
-  hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, VN, exact_path<T>() ? -1 : FL_, true>), dim3(chunks2, n), dim3(256), lds, s, \
-                     (const T*)gz, (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2,    \
-                     split, pstride, (T*)gy, gathered, replicas, nullptr, nullptr, nullptr, nullptr, 0, hw, c, flags, alpha, \
-                     ppb2, gcount)
-
+// second half: pass 2 over the gathered sums of all clones
 int tg_norm_act_bwd_apply(const void* gz, const void* gz_pooled, const void* y, const float* pn_scale, const float* mean,
                           const float* rstd, const float* gamma, const float* beta, const float* gamma2, const float* beta2,
                           int split, int per_image_params, void* gy, const float* gathered, int replicas, int n, int h,
                           int w, int c, int flags, float alpha, int dtype, void* stream) {
-  const int pstride = per_image_params ? c : 0;
-  TG_CHECK((gz || gz_pooled) && y && mean && rstd && gamma && beta && gy && gathered && n > 0 && h > 0 && w > 0 && c > 0,
-           TG_EINVAL, "tg_norm_act_bwd_apply: bad arguments");
-  TG_CHECK(!gz_pooled || (h % 2 == 0 && w % 2 == 0), TG_EINVAL, "tg_norm_act_bwd_apply: pooled gradient needs even h, w");
-  TG_CHECK(!(flags & NF_NOSTATS), TG_EINVAL, "tg_norm_act_bwd_apply: constant statistics (NF_NOSTATS) have no sums to share");
-  TG_CHECK((int64_t)h * w < (1ll << 31) / c, TG_EINVAL, "tg_norm_act_bwd_apply: a group of %d x %d x %d elements does not fit 32-bit offsets",
-           h, w, c);
-  TG_CHECK(replicas >= 1 && (int64_t)replicas * h * w < (1ll << 31), TG_EINVAL,
-           "tg_norm_act_bwd_apply: replicas %d x %d pixels outside [1, 2^31)", replicas, h * w);
-  if (!gamma2 || !beta2) split = n;
-  TG_CHECK(split >= 0 && split <= n, TG_EINVAL, "tg_norm_act_bwd_apply: split %d outside [0, %d]", split, n);
-  hipStream_t s = (hipStream_t)stream;
-  const int hw = h * w;
-  const int gcount = replicas * hw;
-  int chunks2 = (2048 + n - 1) / n;
-  int ppb2 = (hw + chunks2 - 1) / chunks2;
-  if (ppb2 < min_ppb(hw)) ppb2 = min_ppb(hw);
-  chunks2 = (hw + ppb2 - 1) / ppb2;
-  const size_t lds = 2 * (size_t)c * sizeof(float);
-  TG_DISPATCH_DTYPE(dtype, "tg_norm_act_bwd_apply", {
-    constexpr int VN = Vec16<T>::N;
-    const bool vec = (c % VN == 0) && pow2(c / VN) && c / VN <= 64;
-    if (flags & NF_PIXNORM) {
-      TG_CHECK(vec && pn_scale, TG_ENOSUP, "tg_norm_act_bwd_apply: pixel norm needs c (%d) = %d * 2^k and pn_scale", c, VN);
-    }
-    if (vec) {
-      switch (flags & 3) {
-        case 0: TG_NB2S_LAUNCH(0); break;
-        case 1: TG_NB2S_LAUNCH(1); break;
-        case 2: TG_NB2S_LAUNCH(2); break;
-        default: TG_NB2S_LAUNCH(3); break;
-      }
-    } else {
-      TG_CHECK(c <= 256, TG_ENOSUP, "tg_norm_act_bwd_apply: scalar path needs c <= 256 (got %d)", c);
-      hipLaunchKernelGGL((norm_act_bwd2_part_kernel<T, 1, -1, true>), dim3(chunks2, n), dim3(256), lds, s, (const T*)gz,
-                         (const T*)gz_pooled, w, (const T*)y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, pstride,
-                         (T*)gy, gathered, replicas, nullptr, nullptr, nullptr, nullptr, 0, hw, c, flags, alpha, ppb2, gcount);
-    }
+  const char* who = "tg_norm_act_bwd_apply";
+  NormBwd a = {gz, gz_pooled, y, pn_scale, mean, rstd, gamma, beta, gamma2, beta2, split, per_image_params ? c : 0, n, h, w, c,
+               flags, alpha, (hipStream_t)stream};
+  if (int rc = norm_bwd_checks(who, a, gy && gathered, 0)) return rc;
+  if (int rc = norm_split_checks(who, a)) return rc;
+  TG_CHECK(replicas >= 1 && (int64_t)replicas * h * w < (1ll << 31), TG_EINVAL, "%s: replicas %d x %d pixels outside [1, 2^31)",
+           who, replicas, h * w);
+  TG_DISPATCH_DTYPE(dtype, who, {
+    bool vec;
+    if (int rc = norm_path<T>(who, c, flags, pn_scale, TG_ENOSUP, 256, &vec)) return rc;
+    norm_bwd_pass2<T, true>(a, vec, gy, gathered, replicas, NormParamGrads{}, 0, replicas * h * w);
   });
-  TG_LAUNCH_CHECK("tg_norm_act_bwd_apply");
+  TG_LAUNCH_CHECK(who);
   return TG_OK;
 }
 
@@ -1412,11 +1396,7 @@ static int lrelu_bwd_launch(const char* who, const void* gz, const void* gzp, in
         hipLaunchKernelGGL((channel_sum_kernel<T, Vec16<T>::N>), dim3(1), dim3(256), lds, s, (const T*)gy, gbias, npix, c);
     }
   });
-  hipError_t e__ = hipGetLastError();
-  if (e__ != hipSuccess) {
-    tg_set_error("%s: launch failed: %s", who, hipGetErrorString(e__));
-    return TG_ELAUNCH;
-  }
+  TG_LAUNCH_CHECK(who);
   return TG_OK;
 }
 

@@ -1422,19 +1422,40 @@ def instance_stats(y, eps, replicas=None):
   return mean, rstd
 
 
+def _norm_act_fwd_given_stats(y, mean, rstd, gamma, beta, gamma2, beta2, split, per_image, z, s, flags, alpha, pn_eps):
+  """tg_norm_act_fwd: the forward on statistics that exist already (the caller's, the clones' merged ones, constants)."""
+  n, h, w, c = y.shape
+  call('tg_norm_act_fwd', _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2), _p(beta2), split,
+       1 if per_image else 0, _p(z), _p(s), n, h, w, c, flags, alpha, pn_eps, _dt(y), _stream(),
+       work=('norm_act_fwd' + _shape_tag(y), 0, 2 * y.numel() * _esize(y)))
+
+
+def _per_image_stats(stats, y, gamma, beta, gamma2):
+  """[n, c] parameter rows (batch renorm): the statistics come from the caller."""
+  n, c = y.shape[0], y.shape[3]
+  assert stats is not None and tuple(gamma.shape) == (n, c) and tuple(beta.shape) == (n, c) and gamma2 is None
+  return stats
+
+
+def _avg_pool2_of(z):
+  n, h, w, c = z.shape
+  zp = torch.empty((n, h // 2, w // 2, c), dtype=z.dtype, device=z.device)
+  call('tg_pool2x2_fwd', _p(z), _p(zp), n, h, w, c, 0.25, _dt(z), _stream(),
+       work=('pool_fwd' + _shape_tag(z), 0, int(1.25 * z.numel()) * _esize(z)))
+  return zp
+
+
 def _norm_act_forward(ctx, y, gamma, beta, gamma2, beta2, split, flags, in_eps, pn_eps, alpha, ema=None, stats=None,
                       zp=None, conv_stats=None):
   _chk(y, gamma, beta, gamma2, beta2)
   n, h, w, c = y.shape
   split = n if gamma2 is None else int(split)
-  per_image = gamma.dim() == 2          # [n, c] parameter rows (batch renorm): statistics come from the caller
+  per_image = gamma.dim() == 2
   z = torch.empty_like(y)
   s = torch.empty(n * h * w, dtype=torch.float32, device=y.device) if (flags & NF_PIXNORM) else None
   if per_image:
-    assert stats is not None and tuple(gamma.shape) == (n, c) and tuple(beta.shape) == (n, c) and gamma2 is None
-    mean, rstd = stats
-    call('tg_norm_act_fwd', _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), 0, 0, split, 1, _p(z), _p(s), n, h, w, c,
-         flags, alpha, pn_eps, _dt(y), _stream(), work=('norm_act_fwd' + _shape_tag(y), 0, 2 * y.numel() * _esize(y)))
+    mean, rstd = _per_image_stats(stats, y, gamma, beta, gamma2)
+    _norm_act_fwd_given_stats(y, mean, rstd, gamma, beta, None, None, split, True, z, s, flags, alpha, pn_eps)
   else:
     mean = torch.empty(n * c, dtype=torch.float32, device=y.device)
     rstd = torch.empty(n * c, dtype=torch.float32, device=y.device)
@@ -1458,6 +1479,25 @@ def _norm_act_forward(ctx, y, gamma, beta, gamma2, beta2, split, flags, in_eps, 
   return z
 
 
+def _norm_param_grad_outs(gamma, beta, gamma2, beta2, per_image, n, c, device):
+  """Where a normaliser backward leaves its parameter gradients -> (outs, accumulate, returned): the C call's four output
+  slots (None: not written), its accumulate flag, and what autograd gets back for (gamma, beta, gamma2, beta2).  Per-image
+  rows and parameters without a gradient sink: fresh tensors, written and returned; all sunk: added there, nothing returned."""
+  params = [gamma, beta] + ([gamma2, beta2] if gamma2 is not None else [])
+  sinks = [None if per_image else GradSink.get(q) for q in params]
+  sunk = all(t is not None for t in sinks)
+  if _State.skip_param_grads:
+    outs = [None] * 4
+  elif per_image:
+    outs = [torch.empty((n, c), dtype=torch.float32, device=device) for _ in params] + [None, None]
+  elif sunk:
+    outs = sinks + [None] * (4 - len(sinks))
+  else:
+    outs = [torch.empty(c, dtype=torch.float32, device=device) for _ in params] + [None] * (4 - len(params))
+  accumulate = 1 if (sunk and not _State.skip_param_grads) else 0
+  return outs, accumulate, (None,) * 4 if (sunk or _State.skip_param_grads) else tuple(outs)
+
+
 def _norm_act_backward(ctx, gz, gzp=None):
   y, mean, rstd, gamma, beta, gamma2, beta2, s = ctx.saved_tensors
   gz = gz.contiguous() if gz is not None else None
@@ -1465,28 +1505,13 @@ def _norm_act_backward(ctx, gz, gzp=None):
   n, h, w, c = y.shape
   gy = torch.empty_like(y)
   sums = torch.empty(n * _lib.load().tg_norm_chunks(n, h, w) * 2 * c, dtype=torch.float32, device=y.device)
-  two = gamma2 is not None
-  params = [gamma, beta] + ([gamma2, beta2] if two else [])
-  per_image = ctx.per_image
-  sinks = [None if per_image else GradSink.get(q) for q in params]
-  sunk = all(t is not None for t in sinks)
-  if _State.skip_param_grads:
-    outs = [None] * 4
-  elif per_image:
-    outs = [torch.empty((n, c), dtype=torch.float32, device=y.device) for _ in params] + [None, None]
-  elif sunk:
-    outs = sinks + [None] * (4 - len(sinks))
-  else:
-    outs = [torch.empty(c, dtype=torch.float32, device=y.device) for _ in params] + [None] * (4 - len(params))
+  outs, accumulate, returned = _norm_param_grad_outs(gamma, beta, gamma2, beta2, ctx.per_image, n, c, y.device)
   passes = 3 + (0.25 if gzp is not None else 0) - (0 if gz is not None else 1)
   call('tg_norm_act_bwd', _p(gz), _p(gzp), _p(y), _p(s), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2), _p(beta2),
-       ctx.split, _p(gy), 1 if per_image else 0, _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(sums), n, h, w, c,
-       ctx.flags, ctx.alpha,
-       1 if (sunk and not _State.skip_param_grads) else 0, _dt(y), _stream(),
+       ctx.split, _p(gy), 1 if ctx.per_image else 0, _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(sums), n, h, w, c,
+       ctx.flags, ctx.alpha, accumulate, _dt(y), _stream(),
        work=('norm_act_bwd' + _shape_tag(y), 0, int(passes * y.numel()) * _esize(y)))
-  if sunk or _State.skip_param_grads:
-    outs = [None] * 4
-  return gy, outs[0], outs[1], outs[2], outs[3], None, None, None, None, None, None
+  return (gy,) + returned + (None,) * 6
 
 
 class NormActFn(torch.autograd.Function):
@@ -1513,13 +1538,12 @@ class NormActPoolFn(torch.autograd.Function):
   @staticmethod
   def forward(ctx, y, gamma, beta, gamma2, beta2, split, flags, in_eps, pn_eps, alpha, ema, stats, conv_stats=None):
     n, h, w, c = y.shape
-    zp = torch.empty((n, h // 2, w // 2, c), dtype=y.dtype, device=y.device)
     fused = gamma.dim() == 1      # the partial-sums forward writes the pooled tensor itself
-    z = _norm_act_forward(ctx, y, gamma, beta, gamma2, beta2, split, flags, in_eps, pn_eps, alpha, ema, stats,
-                          zp if fused else None, conv_stats=conv_stats if fused else None)
+    zp = torch.empty((n, h // 2, w // 2, c), dtype=y.dtype, device=y.device) if fused else None
+    z = _norm_act_forward(ctx, y, gamma, beta, gamma2, beta2, split, flags, in_eps, pn_eps, alpha, ema, stats, zp,
+                          conv_stats=conv_stats if fused else None)
     if not fused:
-      call('tg_pool2x2_fwd', _p(z), _p(zp), n, h, w, c, 0.25, _dt(z), _stream(),
-           work=('pool_fwd' + _shape_tag(z), 0, int(1.25 * z.numel()) * _esize(z)))
+      zp = _avg_pool2_of(z)
     ctx.set_materialize_grads(False)
     return z, zp
 
@@ -1547,26 +1571,20 @@ class SyncNormActFn(torch.autograd.Function):
     split = n if gamma2 is None else int(split)
     per_image = gamma.dim() == 2
     if per_image:
-      assert stats is not None and tuple(gamma.shape) == (n, c) and tuple(beta.shape) == (n, c) and gamma2 is None
-      mean, rstd = stats
+      mean, rstd = _per_image_stats(stats, y, gamma, beta, gamma2)
     else:
       mean, rstd = _sync_stats(y, in_eps, replicas)
     z = torch.empty_like(y)
     s = torch.empty(n * h * w, dtype=torch.float32, device=y.device) if (flags & NF_PIXNORM) else None
-    call('tg_norm_act_fwd', _p(y), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2), _p(beta2), split,
-         1 if per_image else 0, _p(z), _p(s), n, h, w, c, flags, alpha, pn_eps, _dt(y), _stream(),
-         work=('norm_act_fwd' + _shape_tag(y), 0, 2 * y.numel() * _esize(y)))
+    _norm_act_fwd_given_stats(y, mean, rstd, gamma, beta, gamma2, beta2, split, per_image, z, s, flags, alpha, pn_eps)
     if ema is not None and not per_image:
       _ema_update(mean, rstd, n, c, split, in_eps, ema)
     ctx.flags, ctx.alpha, ctx.split, ctx.per_image, ctx.replicas = flags, alpha, split, per_image, replicas
     ctx.save_for_backward(y, mean, rstd, gamma, beta, gamma2, beta2, s)
     if not pool:
       return z
-    zp = torch.empty((n, h // 2, w // 2, c), dtype=y.dtype, device=y.device)
-    call('tg_pool2x2_fwd', _p(z), _p(zp), n, h, w, c, 0.25, _dt(z), _stream(),
-         work=('pool_fwd' + _shape_tag(z), 0, int(1.25 * z.numel()) * _esize(z)))
     ctx.set_materialize_grads(False)
-    return z, zp
+    return z, _avg_pool2_of(z)
 
   @staticmethod
   @torch.autograd.function.once_differentiable
@@ -1578,47 +1596,40 @@ class SyncNormActFn(torch.autograd.Function):
     gzp = gzp.contiguous() if gzp is not None else None
     n, h, w, c = y.shape
     dev = y.device
-    params = [gamma, beta] + ([gamma2, beta2] if gamma2 is not None else [])
     per_image = ctx.per_image
-    sinks = [None if per_image else GradSink.get(q) for q in params]
-    sunk = all(t is not None for t in sinks)
-    if _State.skip_param_grads:
-      outs = [None] * 4
-    elif per_image:
-      outs = [torch.empty((n, c), dtype=torch.float32, device=dev) for _ in params] + [None, None]
-    elif sunk:
-      outs = sinks + [None] * (4 - len(sinks))
-    else:
-      outs = [torch.empty(c, dtype=torch.float32, device=dev) for _ in params] + [None] * (4 - len(params))
+    outs, accumulate, returned = _norm_param_grad_outs(gamma, beta, gamma2, beta2, per_image, n, c, dev)
     ws = torch.empty(n * _lib.load().tg_norm_chunks(n, h, w) * 2 * c, dtype=torch.float32, device=dev)
     local = torch.empty((n, 2, c), dtype=torch.float32, device=dev)
     reads = 2 + (0.25 if gzp is not None else 0) - (0 if gz is not None else 1)
     call('tg_norm_act_bwd_sums', _p(gz), _p(gzp), _p(y), _p(s), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2), _p(beta2),
          ctx.split, 1 if per_image else 0, _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(ws), _p(local), n, h, w, c,
-         ctx.flags, ctx.alpha, 1 if (sunk and not _State.skip_param_grads) else 0, _dt(y), _stream(),
+         ctx.flags, ctx.alpha, accumulate, _dt(y), _stream(),
          work=('sync_bwd_sums' + _shape_tag(y), 0, int(reads * y.numel()) * _esize(y)))
     gathered = ctx.replicas.gather(local)
     gy = torch.empty_like(y)
     call('tg_norm_act_bwd_apply', _p(gz), _p(gzp), _p(y), _p(s), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(gamma2),
          _p(beta2), ctx.split, 1 if per_image else 0, _p(gy), _p(gathered), ctx.replicas.size, n, h, w, c, ctx.flags,
          ctx.alpha, _dt(y), _stream(), work=('sync_bwd_apply' + _shape_tag(y), 0, int((reads + 1) * y.numel()) * _esize(y)))
-    if sunk or _State.skip_param_grads:
-      outs = [None] * 4
-    return (gy, outs[0], outs[1], outs[2], outs[3]) + (None,) * 9
+    return (gy,) + returned + (None,) * 9
 
 
 _CONST = {}
+
+
+def _unit_rows(n, c, device):
+  """The cached constant rows (ones, zeros), fp32 [n * c]: unit statistics / parameters of the NF_NOSTATS calls."""
+  key = (n, c, device)
+  if key not in _CONST:
+    one = torch.ones(n * c, dtype=torch.float32, device=device)
+    _CONST[key] = (one, torch.zeros_like(one))
+  return _CONST[key]
 
 
 def pixel_norm(y, pn_eps=1e-6):
   """x / sqrt(mean_C(x^2) + eps) alone (nets/pggan_utils.py:330-331; --generator_norm_type none): the fused
   normalisation kernel with constant unit statistics and parameters; NF_NOSTATS makes its backward treat them so."""
   n, c = y.shape[0], y.shape[3]
-  key = (n, c, y.device)
-  if key not in _CONST:
-    one = torch.ones(n * c, dtype=torch.float32, device=y.device)
-    _CONST[key] = (one, torch.zeros_like(one))
-  one, zero = _CONST[key]
+  one, zero = _unit_rows(n, c, y.device)
   return NormActFn.apply(y, one.view(n, c), zero.view(n, c), None, None, None, NF_PIXNORM | NF_NOSTATS, 0.0, pn_eps,
                          LRELU_ALPHA, None, (zero, one))
 
@@ -1628,11 +1639,7 @@ def affine_act(y_hat, gamma_rows, beta_rows, lrelu=True, pixel_norm=True, pool=F
   differentiable tensors): the tail of the CONDITIONAL batch (re)norm layers, whose statistics belong to the whole pass
   and are applied before (libs/batch_norm.py:403-470) -- the fused kernel with constant unit statistics (NF_NOSTATS)."""
   n, c = y_hat.shape[0], y_hat.shape[3]
-  key = (n, c, y_hat.device)
-  if key not in _CONST:
-    one = torch.ones(n * c, dtype=torch.float32, device=y_hat.device)
-    _CONST[key] = (one, torch.zeros_like(one))
-  one, zero = _CONST[key]
+  one, zero = _unit_rows(n, c, y_hat.device)
   flags = (NF_LRELU if lrelu else 0) | (NF_PIXNORM if pixel_norm else 0) | NF_NOSTATS
   fn = NormActPoolFn if pool else NormActFn
   return fn.apply(y_hat, gamma_rows.contiguous(), beta_rows.contiguous(), None, None, None, flags, 0.0, pn_eps, alpha, None,
@@ -1640,14 +1647,6 @@ def affine_act(y_hat, gamma_rows, beta_rows, lrelu=True, pixel_norm=True, pool=F
 
 
 _MOMENT_EPS = 1e-12      # only keeps rsqrt finite for a constant channel; removed again from the variance
-
-
-def _unit_rows(n, c, device):
-  key = (n, c, device)
-  if key not in _CONST:
-    one = torch.ones(n * c, dtype=torch.float32, device=device)
-    _CONST[key] = (one, torch.zeros_like(one))
-  return _CONST[key]
 
 
 class ChannelMomentsFn(torch.autograd.Function):
@@ -1676,8 +1675,8 @@ class ChannelMomentsFn(torch.autograd.Function):
       b = b + gm.float() * inv
     one, zero = _unit_rows(n, c, y.device)
     gy = torch.empty_like(y)
-    call('tg_norm_act_fwd', _p(y), _p(zero), _p(one), _p(a.contiguous()), _p(b.contiguous()), 0, 0, n, 1, _p(gy), 0, n, h, w, c,
-         NF_NOSTATS, LRELU_ALPHA, 1e-6, _dt(y), _stream(), work=('norm_act_fwd' + _shape_tag(y), 0, 2 * y.numel() * _esize(y)))
+    _norm_act_fwd_given_stats(y, zero, one, a.contiguous(), b.contiguous(), None, None, n, True, gy, None, NF_NOSTATS,
+                              LRELU_ALPHA, 1e-6)
     return gy
 
 
