@@ -272,6 +272,57 @@ def gradient_penalty(interp_grad, lam=10.0):
   return np.mean(np.square(slopes - 1.0)) * lam
 
 
+# The backward of the loss tail.  The reference takes it from tf.gradients, which says nothing of a non-finite argument that
+# a piecewise-constant derivative ignores (relu'(NaN) is 0 there).  This project's rule, DESIGN.md section 7: the gradient of
+# an element whose argument is +-inf or NaN is NaN -- the loss scaler sees only the gradients, and a 0 would hide the overflow.
+def _nan_where_nonfinite(grad, arg):
+  return np.where(np.isfinite(arg), grad, np.nan)
+
+
+def pred_loss_term(x, mode, a=0.0, b=0.0):
+  """The per-prediction term of image_generation.py:331-400 -- mode 0: x (WGAN); 1: relu(a + b x) (hinge); 2: sigmoid cross
+  entropy against the label a; 3: x^2 (drift).  np.maximum keeps a NaN."""
+  x = np.asarray(x, F64)
+  with np.errstate(invalid='ignore', over='ignore'):
+    if mode == 1:
+      return np.maximum(a + b * x, 0.0)
+    if mode == 2:
+      return np.maximum(x, 0.0) - x * a + np.log1p(np.exp(-np.abs(x)))
+    return x * x if mode == 3 else x.copy()
+
+
+def pred_loss_term_grad(x, mode, a=0.0, b=0.0):
+  """d pred_loss_term / d x: 1; b where a + b x > 0 (0 at exactly 0, as tf.nn.relu's); sigmoid(x) - a; 2 x -- and NaN for a
+  non-finite x in every mode."""
+  x = np.asarray(x, F64)
+  with np.errstate(invalid='ignore', over='ignore'):
+    if mode == 1:
+      g = np.where(a + b * x > 0, b, 0.0)
+    elif mode == 2:
+      g = 1.0 / (1.0 + np.exp(-x)) - a
+    elif mode == 3:
+      g = 2.0 * x
+    else:
+      g = np.ones_like(x)
+    return _nan_where_nonfinite(g, x)
+
+
+def absolute_difference_grad(labels, predictions, weight=1.0):
+  """-> (d / d labels, d / d predictions) of absolute_difference: -+ sign(p - l) w / numel; NaN where p - l is not finite."""
+  with np.errstate(invalid='ignore'):
+    d = np.asarray(predictions, F64) - np.asarray(labels, F64)
+    g = _nan_where_nonfinite(np.sign(d), d) * (weight / d.size)
+  return -g, g
+
+
+def gradient_penalty_coef(sumsq, lam=10.0):
+  """d gradient_penalty / d g_b = coef_b g_b with coef_b = lambda 2 (slope_b - 1) / (slope_b batch), slope = sqrt(sumsq); a
+  zero sample has coef 0 (this project's choice: the literal formula divides 0 by 0); a non-finite slope gives NaN."""
+  s = np.sqrt(np.asarray(sumsq, F64))
+  with np.errstate(invalid='ignore', divide='ignore'):
+    return np.where(s == 0, 0.0, _nan_where_nonfinite(lam * 2.0 * (s - 1.0) / (s * s.size), s))
+
+
 # --------------------------------------------------------------------------------------------
 # optimiser (model/model_inheritor.py:537-542 -> tf.train.AdamOptimizer)
 # --------------------------------------------------------------------------------------------

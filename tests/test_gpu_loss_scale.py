@@ -618,3 +618,112 @@ def test_checkpoint_round_trip(eager, tmp_path):
     assert int(plain._adam_step_dev.item()) == applies
   fresh.close()
   plain.close()
+
+
+# ------------------------------------------------------------------------------------------------ 8. an overflow planted mid-network
+MID_CONV = 'discriminator_s/encoder_block_8x8x8/Conv/weights'      # the third of the discriminator's six 3x3 convs
+QUIET = 128.0                                                      # every unplanted run applies at this scale (asserted)
+
+
+def _run_and_read(tr, s, t):
+  """One run -> (group, its loss, tensors before, tensors after, skipped by this run)."""
+  group = 'g' if tr.n_critic_counter % tr.cfg.n_critic == 0 else 'd'
+  before = _tensors(tr)
+  loss, _ = tr.run(s, t)
+  torch.cuda.synchronize()
+  after = _tensors(tr)
+  return group, loss.detach().float().cpu(), before, after, \
+      int(_read_state(after['ls/' + group]).skipped) - int(_read_state(before['ls/' + group]).skipped)
+
+
+def _assert_applied(run, what):
+  group, loss, b, a, skipped = run
+  sb, sa = _read_state(b['ls/' + group]), _read_state(a['ls/' + group])
+  assert skipped == 0 and sa.scale == sb.scale and sa.found == 0 and bool(torch.isfinite(loss).all()), (what, skipped, sa.scale, loss)
+  assert int(a['step'].item()) == int(b['step'].item()) + 1 and not torch.equal(b['flat/' + group], a['flat/' + group]), what
+
+
+def _assert_skipped(run, what):
+  """skipped + 1, the scale halved (not below 1), found back at 0; parameters, moments, the device step and the rate keep
+  their bits; the other group is untouched."""
+  group, _, b, a, skipped = run
+  other = {'g': 'd', 'd': 'g'}[group]
+  sb, sa = _read_state(b['ls/' + group]), _read_state(a['ls/' + group])
+  assert skipped == 1 and sa.scale == max(sb.scale / 2.0, 1.0) and (sa.found, sa.skip, sa.good_steps) == (0, 1, 0), \
+      (what, skipped, sb.scale, sa.scale, sa.found, sa.skip)
+  changed = _differing({k: b[k] for k in ('flat/' + group, 'm/' + group, 'v/' + group, 'step', 'lr')}, a)
+  assert not changed, (what + ': a skipped run changed', changed)
+  touched = _differing({k: b[k] for k in ('flat/' + other, 'm/' + other, 'v/' + other, 'ls/' + other)}, a)
+  assert not touched, (what + ': the other group was touched', touched)
+
+
+@pytest.mark.parametrize('loss', ['hinge', 'wgan_gp'])
+@pytest.mark.parametrize('graph', [False, True], ids=['eager', 'graph_replay'])
+def test_mid_network_overflow_is_skipped(graph, loss):
+  """One element of the fp32 master kernel of a conv in the middle of discriminator_s is +inf during ONE discriminator run
+  (packs refreshed as the trainer refreshes them): every activation behind that conv is non-finite, the prediction with
+  them, and the run must be skipped on the evidence of the flat gradient alone -- and must REPORT a non-finite loss (the hinge
+  term relu(1 +- NaN) is NaN, np.maximum's rule; an fmaxf gives 0 and a finite loss over a broken network).  The runs before
+  it apply (the precondition: nothing but the plant overflows at this scale), the other group is untouched, and with the
+  element restored the next discriminator run applies.  The graph variant replays the decision from the captured graphs."""
+  from twingan_amd.ops import PackCache
+  from twingan_amd.twingan import Trainer
+  with _Deterministic():
+    tr = Trainer(_cfg(dynamic_loss_scale=True, loss_scale=QUIET, loss_scale_growth_interval=10 ** 6, loss_architecture=loss),
+                 device=DEV, seed=3, use_graph=graph)
+    s, t = _batch()
+    for i in range(3):      # g, d, g: an unplanted run of each group applies
+      _assert_applied(_run_and_read(tr, s, t), 'unplanted run %d' % i)
+    w = tr.P[MID_CONV]
+    assert w.dim() == 4 and w.dtype == torch.float32 and w.data_ptr() >= tr.store.flat['d'].data_ptr()
+    elem = w.detach().view(-1)[w.numel() // 2:w.numel() // 2 + 1]      # a view into the group's flat buffer
+    keep = elem.clone()
+    elem.fill_(INF)
+    PackCache.refresh(tr._group_weights['d'])
+    run = _run_and_read(tr, s, t)
+    assert run[0] == 'd'
+    _assert_skipped(run, 'the planted run')
+    assert not bool(torch.isfinite(run[1]).all()), 'the discriminator loss over a non-finite network reads %r' % (run[1],)
+    elem.copy_(keep)
+    PackCache.refresh(tr._group_weights['d'])
+    _assert_applied(_run_and_read(tr, s, t), 'the generator run after the plant')
+    run = _run_and_read(tr, s, t)
+    assert run[0] == 'd'
+    _assert_applied(run, 'the discriminator run after the restore')
+    assert not graph or (tr.use_graph and tr.graph_fallback_reason is None), tr.graph_fallback_reason
+    state = tr.loss_scale_state()
+    assert state['d'] == dict(scale=QUIET / 2, good_steps=1, skipped=1) and state['g']['skipped'] == 0, state
+  tr.close()
+
+
+def test_nonfinite_input_pixel_skips_both_groups():
+  """One NaN pixel in the source batch: the generator run and the discriminator run both skip; on the clean batch both then
+  apply, and parameters, moments, step and rate are bit-equal to those of a trainer that never saw the bad batch.  That
+  trainer starts at the scale the first one arrives at (QUIET / 2): a power-of-two scale is exact only above fp16's subnormal
+  range, so two scales are not bit-neutral; what differs between the two is then the `skipped` counters alone.  Hinge loss:
+  no random draw (gradient-penalty alphas) separates the trajectories."""
+  from twingan_amd.twingan import Trainer
+  kw = dict(dynamic_loss_scale=True, loss_scale_growth_interval=10 ** 6, loss_architecture='hinge')
+  with _Deterministic():
+    tr = Trainer(_cfg(loss_scale=QUIET, **kw), device=DEV, seed=3)
+    s, t = _batch()
+    bad = s.clone()
+    bad[1, HW // 2, HW // 2, 1] = float('nan')
+    for want in 'gd':
+      run = _run_and_read(tr, bad, t)
+      assert run[0] == want
+      _assert_skipped(run, 'the %s run on the NaN pixel' % want)
+    for want in 'gd':
+      run = _run_and_read(tr, s, t)
+      assert run[0] == want
+      _assert_applied(run, 'the %s run on the clean batch' % want)
+    ref = Trainer(_cfg(loss_scale=QUIET / 2, **kw), device=DEV, seed=3)
+    for _ in 'gd':
+      ref.run(s, t)
+    a, b = _tensors(tr), _tensors(ref)
+    differ = _differing({k: v for k, v in a.items() if not k.startswith('ls/')}, b)
+    assert not differ, ('the trainer that skipped a bad batch differs from one that never saw it', differ)
+    sa, sb = tr.loss_scale_state(), ref.loss_scale_state()
+    assert all(sa[g] == dict(sb[g], skipped=1) and sb[g]['skipped'] == 0 for g in 'gd') and sa['applies'] == sb['applies'] == 2, (sa, sb)
+  tr.close()
+  ref.close()

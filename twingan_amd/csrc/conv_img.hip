@@ -179,14 +179,14 @@ __global__ __launch_bounds__(256, 2) void conv_img_kernel(const bf16* __restrict
              red[(3 * 16 + r) * 64 + lane] + bq[j];
       if (g.epilogue & TG_EPI_LRELU) v[j] = lrelu_f(v[j], g.alpha);
     }
-    if (g.mask) {      // uniform: a positive bf16 / f16 is a positive int16 pattern
+    if (g.mask) {      // uniform; slope16: a NaN takes alpha
       typedef __attribute__((ext_vector_type(2))) unsigned iu32x2;
       const iu32x2 z = __builtin_bit_cast(iu32x2, __builtin_amdgcn_raw_buffer_load_b64(
           rmask, (unsigned)(((m * 32 + l31) * g.cout + n0 + q * 8 + kgrp * 4) * 2), 0, 0));
-      v[0] *= (short)(z[0] & 0xffffu) > 0 ? 1.f : g.alpha;
-      v[1] *= (short)(z[0] >> 16) > 0 ? 1.f : g.alpha;
-      v[2] *= (short)(z[1] & 0xffffu) > 0 ? 1.f : g.alpha;
-      v[3] *= (short)(z[1] >> 16) > 0 ? 1.f : g.alpha;
+      v[0] *= slope16<F16>(z[0] & 0xffffu, g.alpha);
+      v[1] *= slope16<F16>(z[0] >> 16, g.alpha);
+      v[2] *= slope16<F16>(z[1] & 0xffffu, g.alpha);
+      v[3] *= slope16<F16>(z[1] >> 16, g.alpha);
     }
     const unsigned p0 = pack16x2<F16>(v[0], v[1]), p1 = pack16x2<F16>(v[2], v[3]);
     if constexpr (STATS) {      // of the values as stored

@@ -94,8 +94,9 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const bf16* __restrict_
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[m][j] = 0.f;
 
-  // NOTE: a cin that is not a multiple of 16 (264) makes the last chunk read 8 channels of the next pixel;
-  // the weight pack is zero there.
+  // NOTE: a cin that is not a multiple of 16 (24, 264) leaves the upper 8 channels of the last chunk to the NEXT pixel's
+  // memory.  The weight pack is zero there, but 0 x (an Inf or NaN of that pixel) is NaN: those lanes load nothing
+  // (an out-of-range offset returns 0) -- masked by selection, not by the zero weights.
   //
   // K loop: wave w owns the chunk groups w, w+4, ... (a group = U consecutive 16-channel chunks).  The
   // fragments of group i+1 are requested before the MFMAs of group i run (two register stages), and a
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const bf16* __restrict_
 #pragma unroll
       for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) st.x[u][m][t] = s_load16(rx, in ? xoff[m][t] + c2 : SOOB);
+        for (int t = 0; t < NT; ++t) st.x[u][m][t] = s_load16(rx, ck * 16 + kgrp * 8 < g.cin ? xoff[m][t] + c2 : SOOB);
     }
   };
   auto compute = [&](const Stage& st) __attribute__((always_inline)) {
@@ -182,15 +183,15 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const bf16* __restrict_
       v[j] = red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane] + bq[j];
       if (g.epilogue & TG_EPI_LRELU) v[j] = lrelu_f(v[j], g.alpha);
     }
-    if (g.mask) {      // uniform: a positive bf16 / f16 is a positive int16 pattern
+    if (g.mask) {      // uniform; slope16: a NaN takes alpha
       typedef __attribute__((ext_vector_type(2))) unsigned su32x2;
       const int pm = pbase + m * 32, chq = n0 + q * 8 + kgrp * 4;
       const su32x2 z = __builtin_bit_cast(su32x2, __builtin_amdgcn_raw_buffer_load_b64(
           rmask, (pm < npix && chq + 4 <= g.cout) ? (unsigned)((pm * g.cout + chq) * 2) : SOOB, 0, 0));
-      v[0] *= (short)(z[0] & 0xffffu) > 0 ? 1.f : g.alpha;
-      v[1] *= (short)(z[0] >> 16) > 0 ? 1.f : g.alpha;
-      v[2] *= (short)(z[1] & 0xffffu) > 0 ? 1.f : g.alpha;
-      v[3] *= (short)(z[1] >> 16) > 0 ? 1.f : g.alpha;
+      v[0] *= slope16<F16>(z[0] & 0xffffu, g.alpha);
+      v[1] *= slope16<F16>(z[0] >> 16, g.alpha);
+      v[2] *= slope16<F16>(z[1] & 0xffffu, g.alpha);
+      v[3] *= slope16<F16>(z[1] >> 16, g.alpha);
     }
     const unsigned p0 = pack16x2<F16>(v[0], v[1]), p1 = pack16x2<F16>(v[2], v[3]);
     if constexpr (STATS) {

@@ -121,12 +121,13 @@ __device__ __forceinline__ bf16x8 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned 
 }
 
 // LeakyReLU derivative of 4 consecutive bf16 activations (8 bytes at `off`): z > 0 ? 1 : alpha
+template <bool F16>
 __device__ __forceinline__ void mask4(__amdgpu_buffer_rsrc_t r, unsigned off, float alpha, float (&f)[4]) {
   const u32x2 z = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
-  f[0] = (short)(z[0] & 0xffffu) > 0 ? 1.f : alpha;      // a positive bf16 is a positive int16 pattern
-  f[1] = (short)(z[0] >> 16) > 0 ? 1.f : alpha;
-  f[2] = (short)(z[1] & 0xffffu) > 0 ? 1.f : alpha;
-  f[3] = (short)(z[1] >> 16) > 0 ? 1.f : alpha;
+  f[0] = slope16<F16>(z[0] & 0xffffu, alpha);
+  f[1] = slope16<F16>(z[0] >> 16, alpha);
+  f[2] = slope16<F16>(z[1] & 0xffffu, alpha);
+  f[3] = slope16<F16>(z[1] >> 16, alpha);
 }
 
 
@@ -585,7 +586,7 @@ __global__ __launch_bounds__(256) void conv_tile_kernel(const bf16* __restrict__
         if (g.mask) {      // uniform
           const int chq = n0 + nt * 32 + q * 8 + kgrp * 4;
           float f[4];
-          mask4(rmask, chq + 4 <= g.cout ? (unsigned)(((oy * g.w + ox) * g.cout + chq) * 2) : OOB, g.alpha, f);
+          mask4<F16>(rmask, chq + 4 <= g.cout ? (unsigned)(((oy * g.w + ox) * g.cout + chq) * 2) : OOB, g.alpha, f);
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] *= f[j];
         }
@@ -1003,12 +1004,12 @@ __global__ __launch_bounds__(256) void conv_tile_wres_kernel(const bf16* __restr
           if (g.epilogue & TG_EPI_LRELU) a = lrelu_f(a, g.alpha);
           v[j] = a;
         }
-        if (HAS_MASK && g.mask) {      // uniform: a positive bf16 is a positive int16 pattern
+        if (HAS_MASK && g.mask) {      // uniform; slope16: a NaN takes alpha
           const u32x2 z = zm[HAS_MASK ? nt : 0][q];
-          v[0] *= (short)(z[0] & 0xffffu) > 0 ? 1.f : g.alpha;
-          v[1] *= (short)(z[0] >> 16) > 0 ? 1.f : g.alpha;
-          v[2] *= (short)(z[1] & 0xffffu) > 0 ? 1.f : g.alpha;
-          v[3] *= (short)(z[1] >> 16) > 0 ? 1.f : g.alpha;
+          v[0] *= slope16<F16>(z[0] & 0xffffu, g.alpha);
+          v[1] *= slope16<F16>(z[0] >> 16, g.alpha);
+          v[2] *= slope16<F16>(z[1] & 0xffffu, g.alpha);
+          v[3] *= slope16<F16>(z[1] >> 16, g.alpha);
         }
         p[q][0] = pack16x2<F16>(v[0], v[1]);
         p[q][1] = pack16x2<F16>(v[2], v[3]);
@@ -1250,12 +1251,12 @@ __global__ __launch_bounds__(256) void conv_thin16_kernel(const bf16* __restrict
         if (g.epilogue & TG_EPI_LRELU) a = lrelu_f(a, g.alpha);
         v[j] = a;
       }
-      if (HAS_MASK && g.mask) {      // uniform: a positive bf16 / f16 is a positive int16 pattern
+      if (HAS_MASK && g.mask) {      // uniform; slope16: a NaN takes alpha
         const u32x2 z = zm[pb];
-        v[0] *= (short)(z[0] & 0xffffu) > 0 ? 1.f : g.alpha;
-        v[1] *= (short)(z[0] >> 16) > 0 ? 1.f : g.alpha;
-        v[2] *= (short)(z[1] & 0xffffu) > 0 ? 1.f : g.alpha;
-        v[3] *= (short)(z[1] >> 16) > 0 ? 1.f : g.alpha;
+        v[0] *= slope16<F16>(z[0] & 0xffffu, g.alpha);
+        v[1] *= slope16<F16>(z[0] >> 16, g.alpha);
+        v[2] *= slope16<F16>(z[1] & 0xffffu, g.alpha);
+        v[3] *= slope16<F16>(z[1] >> 16, g.alpha);
       }
       u32x2 o;
       o[0] = pack16x2<F16>(v[0], v[1]);

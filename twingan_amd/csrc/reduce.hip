@@ -463,13 +463,23 @@ __global__ void ordered_scalar_sum_kernel(const float* __restrict__ part, int n,
   out[0] = accumulate ? out[0] + t * scale : t * scale;
 }
 
+// An fp32 value is +-inf or NaN exactly when its exponent bits are all ones.
+__device__ __forceinline__ int nonfinite_bits(float x) {
+  return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u;
+}
+// The loss gradients' rule: a piecewise-constant derivative says nothing about a non-finite argument,
+// and a 0 there would hide the overflow from tg_nonfinite_check -- the gradient of such an element is NaN, by selection.
+__device__ __forceinline__ float nan_where_nonfinite(float grad, float arg) {
+  return nonfinite_bits(arg) ? __builtin_nanf("") : grad;
+}
+
 template <typename T>
 __global__ void abs_diff_bwd_kernel(const T* __restrict__ a, const T* __restrict__ b, const float* __restrict__ gscale,
                                     T* __restrict__ ga, T* __restrict__ gb, int64_t numel, float scale) {
   const float g = (gscale ? gscale[0] : 1.f) * scale;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x) {
     const float d = ld(a + i) - ld(b + i);
-    const float s = d > 0.f ? g : (d < 0.f ? -g : 0.f);
+    const float s = nan_where_nonfinite(d > 0.f ? g : (d < 0.f ? -g : 0.f), d);
     if (ga) st(ga + i, s);
     if (gb) st(gb + i, -s);
   }
@@ -506,7 +516,8 @@ __global__ void gp_penalty_kernel(const float* __restrict__ ss, float* __restric
     const float slope = sqrtf(ss[b]);
     const float d = slope - 1.f;
     acc += d * d;
-    if (coef) coef[b] = slope > 0.f ? lambda * 2.f * d / (slope * (float)batch) : 0.f;
+    // slope == 0: coef = 0, this project's choice; a NaN or infinite slope takes the formula and stays non-finite
+    if (coef) coef[b] = slope == 0.f ? 0.f : lambda * 2.f * d / (slope * (float)batch);
   }
   const float tot = block_sum(acc, red);
   if (threadIdx.x == 0 && loss) loss[0] = lambda * tot / (float)batch;
@@ -518,16 +529,22 @@ __global__ void gp_penalty_kernel(const float* __restrict__ ss, float* __restric
 //   mode 2: sigmoid cross entropy against label a in {0,1}: max(x,0) - x*a + log(1 + exp(-|x|))
 //   mode 3: x^2                    (WGAN drift term)
 __device__ __forceinline__ float pred_loss_f(float x, int mode, float a, float b) {
-  if (mode == 1) return fmaxf(a + b * x, 0.f);
+  if (mode == 1) {      // not fmaxf: a NaN stays a NaN (np.maximum's rule)
+    const float z = a + b * x;
+    return z < 0.f ? 0.f : z;
+  }
   if (mode == 2) return fmaxf(x, 0.f) - x * a + log1pf(expf(-fabsf(x)));
   if (mode == 3) return x * x;
   return x;
 }
-__device__ __forceinline__ float pred_loss_df(float x, int mode, float a, float b) {
+__device__ __forceinline__ float pred_loss_df_finite(float x, int mode, float a, float b) {
   if (mode == 1) return (a + b * x) > 0.f ? b : 0.f;
   if (mode == 2) return 1.f / (1.f + expf(-x)) - a;       // sigmoid(x) - label
   if (mode == 3) return 2.f * x;
   return 1.f;
+}
+__device__ __forceinline__ float pred_loss_df(float x, int mode, float a, float b) {
+  return nan_where_nonfinite(pred_loss_df_finite(x, mode, a, b), x);
 }
 __global__ void pred_loss_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int n, int mode, float a,
                                      float b, float scale, int accumulate) {
@@ -655,7 +672,8 @@ __global__ void var_from_sums_kernel(const float* __restrict__ s1, const float* 
   const float tot = block_sum(acc, red);
   if (threadIdx.x == 0) {
     const float m = s1[0] * inv_numel;
-    out[0] = fmaxf(tot * inv_numel - m * m, 0.f);
+    const float v = tot * inv_numel - m * m;
+    out[0] = v < 0.f ? 0.f : v;      // not fmaxf: a NaN stays a NaN
   }
 }
 
@@ -986,10 +1004,7 @@ __global__ void adam_tick_kernel(int64_t* step, float* lr_t, float lr, float b1,
 
 // ---- dynamic loss scaling (Config.dynamic_loss_scale; this project's own rule): the scale, the skip
 // decision and their bookkeeping live in a TgLossScaleState on the device, so a captured apply graph replays the decision.
-// An fp32 value is +-inf or NaN exactly when its exponent bits are all ones.
-__device__ __forceinline__ int nonfinite_bits(float x) {
-  return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u;
-}
+// (nonfinite_bits: above, with the loss gradients that share it)
 
 // found |= any x[i] non-finite, i < numel: 4 bytes per element.  VEC (x 16-byte aligned): TG_NF_U 16-byte loads per lane in
 // flight per trip, the numel % 4 elements behind the last whole vector one by one; otherwise element by element.  A wave that

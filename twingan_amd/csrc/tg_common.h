@@ -144,6 +144,15 @@ __device__ __forceinline__ f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
   else
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
+
+// LeakyReLU slope selected by the 16-bit pattern of a mask-source element: 1 for a positive number (+inf included), alpha for
+// everything else -- a NaN of either sign too, as `z > 0 ? 1 : alpha` decides it (a positive int16 pattern alone would take a
+// positive NaN for a positive number).  p - 1 wraps a zero to 0xffff, and every negative pattern stays above the bound.
+template <bool F16>
+__device__ __forceinline__ float slope16(unsigned p, float alpha) {
+  return (unsigned short)((p & 0xffffu) - 1u) < (F16 ? 0x7c00u : 0x7f80u) ? 1.f : alpha;
+}
+
 template <bool F16>
 __device__ __forceinline__ unsigned pack16x2(float lo, float hi) {
   if constexpr (F16) {
