@@ -1,5 +1,5 @@
 """ctypes binding of libtwingan_hip.so (include/twingan_hip.h, include/twingan_hip_optim.h, include/twingan_hip_summary.h,
-include/twingan_hip_knn.h, include/twingan_hip_syncnorm.h).
+include/twingan_hip_knn.h, include/twingan_hip_syncnorm.h, include/twingan_hip_mmd.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a kernel call returns
 an error, this module raises.  (``oracle/`` is test infrastructure and is never imported here.)
@@ -249,6 +249,15 @@ SYNCNORM_SIGNATURES = {
     'tg_norm_act_bwd_apply': (c_int, [_P, _P, _P] + [_FP] * 7 + [c_int, c_int, _P, _FP] + [c_int] * 6 + [c_float, c_int, _P]),
 }
 
+# include/twingan_hip_mmd.h, one to one as above.
+MMD_MAX_DEGREE = 4      # TG_MMD_MAX_DEGREE
+
+MMD_SIGNATURES = {
+    'tg_mmd_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    'tg_mmd_block_sums': (c_int, [_P, c_int64, _P, c_int64, c_int, c_int, c_int, c_float, c_float, c_int, c_int64, c_int64, c_int, _P, _P,
+                                  c_size_t, _P]),
+}
+
 _lib = None
 
 
@@ -262,7 +271,7 @@ def load():
                   '(make -C twingan_amd/csrc). There is no CPU fallback.' % LIB_PATH)
   lib = ctypes.CDLL(LIB_PATH)
   for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(SUMMARY_SIGNATURES.items()) + \
-      list(KNN_SIGNATURES.items()) + list(SYNCNORM_SIGNATURES.items()):
+      list(KNN_SIGNATURES.items()) + list(SYNCNORM_SIGNATURES.items()) + list(MMD_SIGNATURES.items()):
     fn = getattr(lib, name)       # AttributeError if a declared symbol is missing
     fn.restype = res
     fn.argtypes = args

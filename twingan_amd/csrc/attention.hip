@@ -13,6 +13,7 @@
 // Replaces tf.matmul x2, tf.nn.softmax, tf.nn.tanh and the gamma * o + layer arithmetic of libs/self_attention.py:57-69.
 #include "tg_common.h"
 #include "../../include/twingan_hip_knn.h"
+#include "../../include/twingan_hip_mmd.h"
 
 namespace {
 
@@ -353,6 +354,75 @@ __device__ __forceinline__ bf16x8 knn_load8(const bf16* base, int row, int col, 
   return v;
 }
 
+// The staged 16-bit dot products that the search and the kernel two-sample sums (include/twingan_hip_mmd.h) share: the 32 QB
+// rows q0 .. of Q [q][d] against the 128 rows g0 .. of G [n][d], 32 of d per step from 0 upwards through sA / sB (rows of
+// KNN_ROW bytes, the next step's vectors in flight), rows and columns outside the matrices and the tail of d zero-filled.
+// On return acc[qb][r] of wave w, lane (i32, kg) is row 32 qb + (r & 3) + 8 (r >> 2) + 4 kg against column 32 w + i32, and
+// with GN accn holds the wave's 32 columns against themselves (their squared norms on the diagonal).  Every thread of the
+// workgroup of 256 calls it; the first barrier of the loop is also the one that ends the caller's previous use of sA / sB.
+template <int QB, bool F16, bool GN>
+__device__ __forceinline__ void pair_tile_dots(const bf16* __restrict__ Q, const bf16* __restrict__ G, int q0, int g0, int q, int n,
+                                               int d, bool vec, unsigned char* sA, unsigned char* sB, f32x16 (&acc)[QB], f32x16& accn) {
+  constexpr int BM = 32 * QB;
+  constexpr int AV = (BM * 4 + 255) / 256;      // 16-byte vectors of the query tile per thread
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, kg = lane >> 5;
+  const int a_frag = i32 * KNN_ROW + kg * 16, b_frag = (wid * 32 + i32) * KNN_ROW + kg * 16;
+#pragma unroll
+  for (int i = 0; i < QB; ++i)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[i][j] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) accn[j] = 0.f;
+
+  bf16x8 ra[AV], rb[2];
+  auto load_tiles = [&](int k0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int s = 0; s < AV; ++s) {
+      const int v = tid + s * 256;
+      if (v < BM * 4) ra[s] = knn_load8(Q, q0 + (v >> 2), k0 + (v & 3) * 8, q, d, vec);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int v = tid + s * 256;
+      rb[s] = knn_load8(G, g0 + (v >> 2), k0 + (v & 3) * 8, n, d, vec);
+    }
+  };
+  load_tiles(0);
+  for (int k0 = 0; k0 < d; k0 += 32) {
+    __syncthreads();      // the previous step's fragment reads (or the caller's previous use of the tiles) are done with
+#pragma unroll
+    for (int s = 0; s < AV; ++s) {
+      const int v = tid + s * 256;
+      if (v < BM * 4) *reinterpret_cast<bf16x8*>(sA + (v >> 2) * KNN_ROW + (v & 3) * 16) = ra[s];
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int v = tid + s * 256;
+      *reinterpret_cast<bf16x8*>(sB + (v >> 2) * KNN_ROW + (v & 3) * 16) = rb[s];
+    }
+    __syncthreads();
+    if (k0 + 32 < d) load_tiles(k0 + 32);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(sB + b_frag + ks * 32);
+      if constexpr (GN) accn = mfma_32x32x16<F16>(bfr, bfr, accn);
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) {
+        const bf16x8 af = *reinterpret_cast<const bf16x8*>(sA + a_frag + qb * 32 * KNN_ROW + ks * 32);
+        acc[qb] = mfma_32x32x16<F16>(af, bfr, acc[qb]);
+      }
+    }
+  }
+}
+
+// the fp32 dot product of two rows: one fmaf chain over d, shared likewise
+template <typename T>
+__device__ __forceinline__ float pair_dot_chain(const T* __restrict__ qp, const T* __restrict__ gp, int d) {
+  float dot = 0.f;
+  for (int i = 0; i < d; ++i) dot = fmaf(ld(qp + i), ld(gp + i), dot);
+  return dot;
+}
+
 template <int BM>
 __device__ __forceinline__ void knn_write_partial(const KnnGeom& g, const float* listD, const int* listI, int q0, int split) {
   for (int i = threadIdx.x; i < g.k * BM; i += 256) {
@@ -369,7 +439,6 @@ __global__ __launch_bounds__(256, 2) void knn_mfma_kernel(const bf16* __restrict
   constexpr int BM = 32 * QB;
   constexpr int A_BYTES = BM * KNN_ROW, B_BYTES = KNN_GT * KNN_ROW, STAGE_BYTES = BM * KNN_SW * 4;
   constexpr int S_BYTES = A_BYTES + B_BYTES > STAGE_BYTES ? A_BYTES + B_BYTES : STAGE_BYTES;
-  constexpr int AV = (BM * 4 + 255) / 256;      // 16-byte vectors of the query tile per thread
   __shared__ __attribute__((aligned(16))) unsigned char smem[S_BYTES];      // operand tiles; the staged distances after the k loop
   __shared__ float listD[KNN_K * BM];
   __shared__ int listI[KNN_K * BM];
@@ -401,58 +470,10 @@ __global__ __launch_bounds__(256, 2) void knn_mfma_kernel(const bf16* __restrict
   }
   __syncthreads();
 
-  const int a_frag = i32 * KNN_ROW + kg * 16, b_frag = (wid * 32 + i32) * KNN_ROW + kg * 16;
   for (int t = t_lo; t < t_hi; ++t) {
     const int g0 = t * KNN_GT;
-    f32x16 acc[QB];
-#pragma unroll
-    for (int i = 0; i < QB; ++i)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[i][j] = 0.f;
-
-    f32x16 accn;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) accn[j] = 0.f;
-
-    bf16x8 ra[AV], rb[2];
-    auto load_tiles = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < AV; ++s) {
-        const int v = tid + s * 256;
-        if (v < BM * 4) ra[s] = knn_load8(Q, q0 + (v >> 2), k0 + (v & 3) * 8, g.q, g.d, vec);
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int v = tid + s * 256;
-        rb[s] = knn_load8(G, g0 + (v >> 2), k0 + (v & 3) * 8, g.n, g.d, vec);
-      }
-    };
-    load_tiles(0);
-    for (int k0 = 0; k0 < g.d; k0 += 32) {
-      __syncthreads();      // the previous step's fragment reads (or the previous tile's staged distances) are done with
-#pragma unroll
-      for (int s = 0; s < AV; ++s) {
-        const int v = tid + s * 256;
-        if (v < BM * 4) *reinterpret_cast<bf16x8*>(sA + (v >> 2) * KNN_ROW + (v & 3) * 16) = ra[s];
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int v = tid + s * 256;
-        *reinterpret_cast<bf16x8*>(sB + (v >> 2) * KNN_ROW + (v & 3) * 16) = rb[s];
-      }
-      __syncthreads();
-      if (k0 + 32 < g.d) load_tiles(k0 + 32);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bfr = *reinterpret_cast<const bf16x8*>(sB + b_frag + ks * 32);
-        if constexpr (GN) accn = mfma_32x32x16<F16>(bfr, bfr, accn);
-#pragma unroll
-        for (int qb = 0; qb < QB; ++qb) {
-          const bf16x8 af = *reinterpret_cast<const bf16x8*>(sA + a_frag + qb * 32 * KNN_ROW + ks * 32);
-          acc[qb] = mfma_32x32x16<F16>(af, bfr, acc[qb]);
-        }
-      }
-    }
+    f32x16 acc[QB], accn;
+    pair_tile_dots<QB, F16, GN>(Q, G, q0, g0, g.q, g.n, g.d, vec, sA, sB, acc, accn);
 
     // acc[qb][r]: query row 32 qb + (r & 3) + 8 (r >> 2) + 4 kg, gallery column g0 + 32 wid + i32.  The waves take turns to
     // stage their 32 columns of distances (NaN: no such gallery row); each query's thread filters and inserts.  Eight
@@ -525,9 +546,7 @@ __global__ __launch_bounds__(256) void knn_valu_kernel(const T* __restrict__ Q, 
       float dv = NAN;
       if (qin && gcol < g.n && gcol != skip) {
         const T* gp = G + (size_t)gcol * g.d;
-        float dot = 0.f;
-        for (int i = 0; i < g.d; ++i) dot = fmaf(ld(qp + i), ld(gp + i), dot);
-        dv = knn_distance(g.metric, qnv, g.gn[gcol], dot);
+        dv = knn_distance(g.metric, qnv, g.gn[gcol], pair_dot_chain(qp, gp, g.d));
       }
       stage[qr * KNN_SW + c] = dv;
       __syncthreads();
@@ -623,6 +642,128 @@ void knn_sqnorm_launch(const void* x, int64_t rows, int d, int dtype, float* out
     hipLaunchKernelGGL(knn_sqnorm_mfma_kernel<true>, grid, dim3(256), 0, s, (const bf16*)x, out, (int)rows, d, vec);
   else
     hipLaunchKernelGGL(knn_sqnorm_mfma_kernel<false>, grid, dim3(256), 0, s, (const bf16*)x, out, (int)rows, d, vec);
+}
+
+// ---- kernel two-sample block sums (include/twingan_hip_mmd.h) --------------------------------------------------------------
+// The search's sibling: the same staged dot products (pair_tile_dots / pair_dot_chain), and an epilogue that turns each into
+// the polynomial kernel's value and adds it up instead of selecting.  The unit of summation is 32 x 32 pairs -- one wave's
+// MFMA block, and since a block of the result is a multiple of 32 rows on either side a unit never straddles two blocks.
+// Every pair value is widened to fp64 as it is added: lane, then the unit's lanes in lane order through LDS, one fp64 per
+// unit to the workspace; mmd_merge_kernel adds a block's units in a fixed order.  No atomics, nothing depends on arrival.
+struct MmdGeom {
+  int m, n, d, degree, vec, skip, tm, tn;      // tm x tn units
+  float gamma, coef0;
+  int64_t delta;      // b_index0 - a_index0: with `skip` the pair (i, j) with i - j == delta is left out
+  double* unit;       // [tm][tn]
+};
+
+__device__ __forceinline__ float mmd_pair(const MmdGeom& g, float s) {
+  const float t = fmaf(g.gamma, s, g.coef0);
+  float p = t;
+  for (int k = 1; k < g.degree; ++k) p = p * t;
+  return p;
+}
+
+__device__ __forceinline__ bool mmd_takes(const MmdGeom& g, int row, int col) {
+  return row < g.m && col < g.n && !(g.skip && (int64_t)row - (int64_t)col == g.delta);
+}
+
+constexpr int MMD_QB = 4;        // 128 rows of `a` per workgroup, as the search's widest tile
+constexpr int MMD_RW = 17;       // doubles per lane of the reduction buffer (16 units of a workgroup + 1: no bank conflicts)
+
+template <bool F16>
+__global__ __launch_bounds__(256, 2) void mmd_mfma_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B, const MmdGeom g) {
+  constexpr int A_BYTES = 32 * MMD_QB * KNN_ROW, B_BYTES = KNN_GT * KNN_ROW;
+  static_assert(64 * MMD_RW * 8 <= A_BYTES + B_BYTES, "the reduction buffer reuses the operand tiles");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[A_BYTES + B_BYTES];      // operand tiles; the lanes' sums afterwards
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, i32 = lane & 31, kg = lane >> 5;
+  const int a0 = blockIdx.x * (32 * MMD_QB), b0 = blockIdx.y * KNN_GT;
+  f32x16 acc[MMD_QB], accn;
+  pair_tile_dots<MMD_QB, F16, false>(A, B, a0, b0, g.m, g.n, g.d, g.vec != 0, smem, smem + A_BYTES, acc, accn);
+
+  // acc[qb][r]: row a0 + 32 qb + (r & 3) + 8 (r >> 2) + 4 kg of `a`, row b0 + 32 wid + i32 of `b`; unit (qb, wid)
+  double* red = reinterpret_cast<double*>(smem);
+  const int col = b0 + wid * 32 + i32;
+  __syncthreads();      // every fragment read of smem is done
+#pragma unroll
+  for (int qb = 0; qb < MMD_QB; ++qb) {
+    double sum = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = a0 + qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
+      const float p = mmd_pair(g, acc[qb][r]);
+      sum += mmd_takes(g, row, col) ? (double)p : 0.0;      // a select: what a zero-filled row made of a NaN stays out
+    }
+    red[lane * MMD_RW + qb * 4 + wid] = sum;
+  }
+  __syncthreads();
+  if (tid < 4 * MMD_QB) {
+    const int ur = a0 / 32 + (tid >> 2), uc = b0 / 32 + (tid & 3);
+    if (ur < g.tm && uc < g.tn) {
+      double sum = 0.0;
+      for (int l = 0; l < 64; ++l) sum += red[l * MMD_RW + tid];
+      g.unit[(size_t)ur * g.tn + uc] = sum;
+    }
+  }
+}
+
+// fp32, the exact-parity path: a workgroup per unit, thread (r8, c) takes rows r8, r8 + 8, r8 + 16, r8 + 24 against column c
+__global__ __launch_bounds__(256) void mmd_valu_kernel(const float* __restrict__ A, const float* __restrict__ B, const MmdGeom g) {
+  __shared__ double red[256 + 16];
+  const int tid = threadIdx.x, c = tid & 31, r8 = tid >> 5;
+  const int col = blockIdx.y * 32 + c;
+  double sum = 0.0;
+  if (col < g.n) {
+    const float* bp = B + (size_t)col * g.d;
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+      const int row = blockIdx.x * 32 + r8 + 8 * k;
+      if (mmd_takes(g, row, col)) sum += (double)mmd_pair(g, pair_dot_chain(A + (size_t)row * g.d, bp, g.d));
+    }
+  }
+  red[tid] = sum;
+  __syncthreads();
+  if (tid < 16) {
+    double part = 0.0;
+    for (int i = 0; i < 16; ++i) part += red[tid * 16 + i];
+    red[256 + tid] = part;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double total = 0.0;
+    for (int i = 0; i < 16; ++i) total += red[256 + i];
+    g.unit[(size_t)blockIdx.x * g.tn + blockIdx.y] = total;
+  }
+}
+
+// block (I, J) of the result: its bu x bu units (fewer at the edges), row-major, dealt to 64 threads, the threads' sums in order
+__global__ __launch_bounds__(64) void mmd_merge_kernel(const MmdGeom g, int bu, int nbj, double* __restrict__ sums) {
+  __shared__ double red[64];
+  const int t = threadIdx.x;
+  const int r_lo = blockIdx.x * bu, c_lo = blockIdx.y * bu;
+  const int rows = (g.tm - r_lo < bu ? g.tm - r_lo : bu), cols = (g.tn - c_lo < bu ? g.tn - c_lo : bu);
+  const int64_t count = (int64_t)rows * cols;
+  double sum = 0.0;
+  for (int64_t u = t; u < count; u += 64) sum += g.unit[(size_t)(r_lo + u / cols) * g.tn + (c_lo + u % cols)];
+  red[t] = sum;
+  __syncthreads();
+  if (t == 0) {
+    double total = 0.0;
+    for (int i = 0; i < 64; ++i) total += red[i];
+    sums[(size_t)blockIdx.x * nbj + blockIdx.y] = total;
+  }
+}
+
+constexpr int64_t MMD_MAX_ROWS = 1ll << 20;
+
+int mmd_plan(int64_t m, int64_t n, int d, int block, int* tm, int* tn) {
+  TG_CHECK(m >= 1 && m <= MMD_MAX_ROWS, TG_EINVAL, "tg_mmd: m = %lld outside 1 .. 2^20", (long long)m);
+  TG_CHECK(n >= 1 && n <= MMD_MAX_ROWS, TG_EINVAL, "tg_mmd: n = %lld outside 1 .. 2^20", (long long)n);
+  TG_CHECK(d >= 1 && d <= (1 << 30), TG_EINVAL, "tg_mmd: d = %d outside 1 .. 2^30", d);
+  TG_CHECK(block >= 32 && block % 32 == 0, TG_EINVAL, "tg_mmd: block = %d is not a multiple of 32 that is >= 32", block);
+  *tm = (int)((m + 31) / 32);
+  *tn = (int)((n + 31) / 32);
+  return TG_OK;
 }
 
 }  // namespace
@@ -824,6 +965,52 @@ int tg_knn_topk(const void* queries, int64_t q, const void* gallery, int64_t n, 
   }
   hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((q + 63) / 64)), dim3(64), 0, s, g, dist, idx);
   TG_LAUNCH_CHECK("tg_knn_topk");
+  return TG_OK;
+}
+
+// ---- include/twingan_hip_mmd.h ---------------------------------------------------------------------------------------------
+size_t tg_mmd_workspace_bytes(int64_t m, int64_t n, int d, int block) {
+  int tm = 0, tn = 0;
+  if (mmd_plan(m, n, d, block, &tm, &tn) != TG_OK) return 0;
+  return (size_t)tm * tn * sizeof(double);
+}
+
+int tg_mmd_block_sums(const void* a, int64_t m, const void* b, int64_t n, int d, int dtype, int degree, float gamma, float coef0,
+                      int block, int64_t a_index0, int64_t b_index0, int skip_same_index, double* sums, void* ws, size_t ws_bytes,
+                      void* stream) {
+  MmdGeom g;
+  const int rc = mmd_plan(m, n, d, block, &g.tm, &g.tn);
+  if (rc != TG_OK) return rc;
+  TG_CHECK(a && b && sums && ws, TG_EINVAL, "tg_mmd_block_sums: NULL pointer");
+  TG_CHECK(dtype == TG_F32 || dtype == TG_BF16 || dtype == TG_F16, TG_EINVAL, "tg_mmd_block_sums: dtype %d", dtype);
+  TG_CHECK(degree >= 1 && degree <= TG_MMD_MAX_DEGREE, TG_EINVAL, "tg_mmd_block_sums: degree = %d outside 1 .. %d", degree,
+           TG_MMD_MAX_DEGREE);
+  TG_CHECK(a_index0 >= 0, TG_EINVAL, "tg_mmd_block_sums: a_index0 %lld < 0", (long long)a_index0);
+  TG_CHECK(b_index0 >= 0, TG_EINVAL, "tg_mmd_block_sums: b_index0 %lld < 0", (long long)b_index0);
+  const size_t need = (size_t)g.tm * g.tn * sizeof(double);
+  TG_CHECK((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, TG_EINVAL, "tg_mmd_block_sums: workspace not 8-byte aligned");
+  TG_CHECK(ws_bytes >= need, TG_EINVAL, "tg_mmd_block_sums: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  g.m = (int)m; g.n = (int)n; g.d = d; g.degree = degree;
+  g.gamma = gamma; g.coef0 = coef0;
+  g.skip = skip_same_index ? 1 : 0;
+  g.delta = b_index0 - a_index0;
+  g.unit = (double*)ws;
+  g.vec = d % 8 == 0 && tg_aligned16(a) && tg_aligned16(b) ? 1 : 0;
+  if (dtype == TG_F32) {
+    tg_note_kernel("mmd_valu_kernel");
+    hipLaunchKernelGGL(mmd_valu_kernel, dim3(g.tm, g.tn), dim3(256), 0, s, (const float*)a, (const float*)b, g);
+  } else {
+    const dim3 grid((g.tm + MMD_QB - 1) / MMD_QB, (g.tn + 3) / 4);
+    tg_note_kernel("mmd_mfma_kernel");
+    if (dtype == TG_F16)
+      hipLaunchKernelGGL(mmd_mfma_kernel<true>, grid, dim3(256), 0, s, (const bf16*)a, (const bf16*)b, g);
+    else
+      hipLaunchKernelGGL(mmd_mfma_kernel<false>, grid, dim3(256), 0, s, (const bf16*)a, (const bf16*)b, g);
+  }
+  const int bu = block / 32, nbi = (g.tm + bu - 1) / bu, nbj = (g.tn + bu - 1) / bu;
+  hipLaunchKernelGGL(mmd_merge_kernel, dim3(nbi, nbj), dim3(64), 0, s, g, bu, nbj, sums);
+  TG_LAUNCH_CHECK("tg_mmd_block_sums");
   return TG_OK;
 }
 

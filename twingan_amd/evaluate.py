@@ -12,10 +12,21 @@ evaluate_translation scores a TwinGAN checkpoint: the diversity of what it gener
 s -> t' -> s_cyc to its source (the quantity the L1 cycle loss trains) and, given target-domain images, the SWD between them
 and the translations (real = targets, fake = t_prime_output: twingan.py:762-763).  Images stay on the device in the model's
 dtype; nothing synchronises before the final read-out.  Which weights are scored is the caller's choice of state dict: the
-raw iterate or, under Config.moving_average_decay, the moving averages (ParamStore.averaged_state_dict).  The Inception score needs a pretrained classifier and is out of scope."""
+raw iterate or, under Config.moving_average_decay, the moving averages (ParamStore.averaged_state_dict).  The Inception score needs a pretrained classifier and is out of scope.
+
+KernelDistance is the feature-space metric that needs no classifier: the unbiased kernel two-sample distance (MMD^2) of
+Binkowski et al., "Demystifying MMD GANs", over [N, D] feature rows -- with the cubic polynomial kernel the KID -- from the
+block sums of ops.mmd_block_sums (include/twingan_hip_mmd.h).  Fed with the model's own content embeddings
+(evaluate_translation(latent=True)) it measures how far apart the two domains lie in the shared latent space; fed with any
+other rows (embed.read_embeddings of Inception features computed elsewhere) it is KID proper.  This project's own definition:
+kid_mean / kid_std are taken over DISJOINT consecutive subsets of subset_size rows (1024), not the literature's 100 random
+subsets of 1000."""
+import dataclasses
+
+import numpy as np
 import torch
 
-from . import ops
+from . import ops, pggan
 from .config import Config
 from .params import ParamStore, declare_twingan
 from .twingan import encode_style, translate
@@ -139,7 +150,110 @@ def write_swd_result(path, result, num_images):
     f.write('Average\t%f\t%f\n' % tuple(result['average']))
 
 
-def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cuda', translate_fn=None, targets=None):
+def kernel_distance_from_sums(xx, yy, xy, m, n, block, subset_size):
+  """The host arithmetic of KernelDistance.end(), float64: ``xx`` [ceil(m / block), ceil(m / block)] and ``yy`` (n likewise) are
+  the block sums of the two sets against themselves WITHOUT the diagonal pairs, ``xy`` [ceil(m / block), ceil(n / block)] those
+  of one against the other.  -> the dict KernelDistance.end() documents."""
+  xx, yy, xy = (np.asarray(v, dtype=np.float64) for v in (xx, yy, xy))
+  m, n, block, subset_size = int(m), int(n), int(block), int(subset_size)
+  if m < 2 or n < 2:
+    raise ValueError('KernelDistance: the unbiased estimate needs at least 2 rows on each side (got %d and %d)' % (m, n))
+  if block < 32 or block % 32 or subset_size < block or subset_size % block:
+    raise ValueError('KernelDistance: block = %d must be a multiple of 32, subset_size = %d a multiple of block' % (block, subset_size))
+  bm, bn = -(-m // block), -(-n // block)
+  if xx.shape != (bm, bm) or yy.shape != (bn, bn) or xy.shape != (bm, bn):
+    raise ValueError('KernelDistance: block sums of shapes %s, %s, %s do not belong to %d and %d rows in blocks of %d'
+                     % (xx.shape, yy.shape, xy.shape, m, n, block))
+
+  def estimate(sxx, syy, sxy, rows_x, rows_y):
+    return float(sxx.sum()) / (rows_x * (rows_x - 1)) + float(syy.sum()) / (rows_y * (rows_y - 1)) - 2.0 * float(sxy.sum()) / (rows_x * rows_y)
+
+  out = {'mmd2': estimate(xx, yy, xy, m, n), 'm': m, 'n': n, 'subset_size': subset_size}
+  per, subsets = subset_size // block, min(m, n) // subset_size
+  vals = [estimate(xx[k * per:(k + 1) * per, k * per:(k + 1) * per], yy[k * per:(k + 1) * per, k * per:(k + 1) * per],
+                   xy[k * per:(k + 1) * per, k * per:(k + 1) * per], subset_size, subset_size) for k in range(subsets)]
+  out['num_subsets'] = subsets
+  out['kid_mean'] = float(np.mean(vals)) if vals else None
+  out['kid_std'] = float(np.std(vals)) if vals else None
+  return out
+
+
+class KernelDistance:
+  """begin() / feed(x_rows, y_rows) / end() like MsSsim and SlicedWasserstein, for feature rows: feed copies [*, dim] device
+  tensors (one dtype for everything fed: fp32 / bf16 / fp16; either argument may be None) behind what was fed before into
+  buffers preallocated for ``capacity`` rows a side -- no synchronisation, and more rows than the buffers hold are refused;
+  end() launches three ops.mmd_block_sums (X against X and Y against Y without the diagonal, X against Y), makes ONE
+  device-to-host copy, the only synchronisation, and returns, all in float64 on the host,
+    {'mmd2':        the unbiased estimate over everything fed, sumXX / (m (m - 1)) + sumYY / (n (n - 1)) - 2 sumXY / (m n),
+     'kid_mean', 'kid_std', 'num_subsets', 'subset_size':
+                    the same estimator on each of the min(m, n) // subset_size DISJOINT CONSECUTIVE subsets (rows
+                    k subset_size .. of either side), read off the same block sums: their mean and their standard deviation
+                    (the population one, numpy.std); None / None / 0 when fewer rows than one subset were fed,
+     'm', 'n':      rows fed on each side}.
+  The kernel is (gamma x.y + coef0) ** degree; ``gamma`` None = float32(1 / dim): at the defaults the KID's cubic kernel.
+  This project's own definition: the literature's KID averages 100 RANDOM subsets of 1000; this one takes disjoint subsets of
+  1024 in feed order -- or, with ``shuffle_seed``, in the order of one permutation per side drawn at end() from a CPU
+  torch.Generator seeded with it (X's first), so a seed fixes the result bit for bit.  ``subset_size`` must be a multiple of
+  ``block`` (itself a multiple of 32); fewer than 2 rows on a side are refused."""
+
+  def __init__(self, dim, capacity, subset_size=1024, block=32, degree=3, gamma=None, coef0=1.0, shuffle_seed=None):
+    self.dim, self.capacity, self.subset_size, self.block = int(dim), int(capacity), int(subset_size), int(block)
+    if self.dim < 1 or self.capacity < 2:
+      raise ValueError('KernelDistance: dim = %d, capacity = %d' % (self.dim, self.capacity))
+    if self.block < 32 or self.block % 32 or self.subset_size < self.block or self.subset_size % self.block:
+      raise ValueError('KernelDistance: block = %d must be a multiple of 32, subset_size = %d a multiple of block'
+                       % (self.block, self.subset_size))
+    if not 1 <= int(degree) <= ops.MMD_MAX_DEGREE:
+      raise ValueError('KernelDistance: degree = %d outside 1 .. %d' % (degree, ops.MMD_MAX_DEGREE))
+    self.kernel = dict(block=self.block, degree=int(degree), gamma=gamma, coef0=float(coef0))
+    self.shuffle_seed = shuffle_seed
+    self.buf = None
+    self.count = [0, 0]
+
+  def begin(self, mode=None):
+    self.count = [0, 0]
+
+  def feed(self, x_rows, y_rows, mode=None):
+    for side, rows in enumerate((x_rows, y_rows)):
+      if rows is None:
+        continue
+      if rows.dim() != 2 or rows.shape[1] != self.dim:
+        raise ops._lib.TgError('KernelDistance.feed: rows [*, %d] are needed (got %s)' % (self.dim, tuple(rows.shape)))
+      if self.buf is None:
+        self.buf = [torch.empty(self.capacity, self.dim, dtype=rows.dtype, device=rows.device) for _ in range(2)]
+      if rows.dtype != self.buf[0].dtype or rows.device != self.buf[0].device:
+        raise ops._lib.TgError('KernelDistance.feed: rows of %s on %s, the buffers hold %s on %s'
+                               % (rows.dtype, rows.device, self.buf[0].dtype, self.buf[0].device))
+      k = int(rows.shape[0])
+      if self.count[side] + k > self.capacity:
+        raise ops._lib.TgError('KernelDistance.feed: %d rows fed, the buffers hold %d' % (self.count[side] + k, self.capacity))
+      self.buf[side][self.count[side]:self.count[side] + k].copy_(rows)
+      self.count[side] += k
+
+  def block_sums(self):
+    """-> (xx, yy, xy) device fp64 block sums of what was fed; no synchronisation."""
+    m, n = self.count
+    if m < 2 or n < 2:
+      raise ops._lib.TgError('KernelDistance.end: the unbiased estimate needs at least 2 rows on each side (got %d and %d)' % (m, n))
+    x, y = self.buf[0][:m], self.buf[1][:n]
+    if self.shuffle_seed is not None:
+      gen = torch.Generator().manual_seed(int(self.shuffle_seed))
+      x, y = (t.index_select(0, torch.randperm(t.shape[0], generator=gen).to(t.device)) for t in (x, y))
+    with torch.cuda.device(x.device):
+      return (ops.mmd_block_sums(x, x, skip_same_index=True, **self.kernel), ops.mmd_block_sums(y, y, skip_same_index=True, **self.kernel),
+              ops.mmd_block_sums(x, y, **self.kernel))
+
+  def end(self, mode=None):
+    m, n = self.count
+    xx, yy, xy = self.block_sums()
+    host = torch.cat([xx.reshape(-1), yy.reshape(-1), xy.reshape(-1)]).cpu().numpy()      # the only synchronisation
+    a, b = xx.numel(), xx.numel() + yy.numel()
+    return kernel_distance_from_sums(host[:a].reshape(xx.shape), host[a:b].reshape(yy.shape), host[b:].reshape(xy.shape), m, n,
+                                     self.block, self.subset_size)
+
+
+def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cuda', translate_fn=None, targets=None, latent=False,
+                         encode_fn=None):
   """Scores a TwinGAN stage on ``sources`` (float [N, hw, hw, 3] in [0, 1], N even; tensor or array):
     ms_ssim_diversity: MS-SSIM between consecutive generated images translate(source, to) (pairs 0-1, 2-3, ...; lower =
                        more diverse, the reference's use of the metric);
@@ -151,17 +265,35 @@ def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cud
   fed (targets, translate(sources)) batch by batch.
   ``state_dict`` names the weights that are scored: ParamStore.state_dict(include_state=True) for the last optimiser
   iterate, ParamStore.averaged_state_dict() for the moving averages of a run under Config.moving_average_decay -- the
-  weights the reference's eval branch restores (model/model_inheritor.py:1150-1155) and the PGGAN paper scores."""
+  weights the reference's eval branch restores (model/model_inheritor.py:1150-1155) and the PGGAN paper scores.
+  ``latent`` (True, or a dict of KernelDistance keyword arguments such as subset_size; needs ``targets``) adds
+  out['latent'] = {'domains': ..., 'translation': ..., 'floor': ...}, three KernelDistance.end() dicts over content
+  embeddings E_d(x) = pggan.encoder_before_classification under is_training=False, flattened as
+  embed.ContentEncoder.encode does, all fed batch by batch in the same loop:
+    domains      E_from(sources) against E_to(targets): the alignment of the shared latent space;
+    translation  E_to(translate(sources, to)) against E_to(targets): fakes against reals;
+    floor        the first against the second half of E_to(targets) in feed order: the estimator's noise at half the sample,
+                 as SWD's ``real`` column.
+  ``encode_fn(x, domain) -> [B, D]`` replaces the encoder as translate_fn replaces the model."""
   assert to in ('s', 't'), to
+  if latent and targets is None:
+    raise ValueError('evaluate_translation: latent=True compares with the target domain: targets are needed')
   cfg = cfg if isinstance(cfg, Config) else Config(**cfg)
   device = torch.device(device)
   dtype = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}[cfg.precision]
   frm = 's' if to == 't' else 't'
   store = None
-  if translate_fn is None:
+  if translate_fn is None or (latent and encode_fn is None):
     store = declare_twingan(ParamStore(device), cfg).build(0)
     store.load_state_dict(state_dict)
+  if latent and encode_fn is None:
+    cfg_infer = dataclasses.replace(cfg, is_training=False)
 
+    def encode_fn(x, domain):
+      net, _ = pggan.encoder_before_classification(store.P, x.contiguous(), domain, cfg_infer)
+      return net.contiguous().reshape(x.shape[0], -1)
+
+  if translate_fn is None:
     def translate_fn(x, to_):
       style = encode_style(store.P, x, cfg, 's' if to_ == 't' else 't') if cfg.use_style_embedding else None
       return translate(store.P, x, cfg, to_, style)
@@ -177,6 +309,7 @@ def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cud
     assert tuple(t_all.shape) == tuple(x_all.shape), 'targets: as many images as sources, of the same size'
     swd = SlicedWasserstein(x_all.shape[1], x_all.shape[0])
     swd.begin()
+  kd, total, half = None, x_all.shape[0], x_all.shape[0] // 2
   with torch.cuda.device(device), torch.no_grad():
     for i in range(0, x_all.shape[0], batch):
       x = x_all[i:i + batch].to(device).to(dtype).contiguous()
@@ -185,11 +318,24 @@ def evaluate_translation(cfg, state_dict, sources, to='t', batch=16, device='cud
       diversity.feed(y)
       cycle.feed_pairs(x, back)
       if swd is not None:
-        swd.feed(t_all[i:i + batch].to(device).to(dtype).contiguous(), y)
+        t = t_all[i:i + batch].to(device).to(dtype).contiguous()
+        swd.feed(t, y)
+        if latent:
+          e_src, e_fake, e_tgt = encode_fn(x, frm), encode_fn(y, to), encode_fn(t, to)
+          if kd is None:
+            kw = dict(latent) if isinstance(latent, dict) else {}
+            kd = {'domains': KernelDistance(e_tgt.shape[1], total, **kw), 'translation': KernelDistance(e_tgt.shape[1], total, **kw),
+                  'floor': KernelDistance(e_tgt.shape[1], max(half, 2), **kw)}
+          kd['domains'].feed(e_src, e_tgt)
+          kd['translation'].feed(e_fake, e_tgt)
+          first = min(max(half - i, 0), e_tgt.shape[0])      # rows of this batch that belong to the first half
+          kd['floor'].feed(e_tgt[:first] if first else None, e_tgt[first:] if first < e_tgt.shape[0] else None)
     out = {'ms_ssim_diversity': diversity.end(), 'ms_ssim_cycle': cycle.end()}
     if swd is not None:
       res = swd.end()
       out.update(swd_real=res['real'], swd_fake=res['fake'], swd_resolutions=res['resolutions'])
+    if kd is not None:
+      out['latent'] = {k: v.end() for k, v in kd.items()}
   if store is not None:
     store.close()
   return out

@@ -3467,3 +3467,37 @@ def knn_topk(queries, gallery, k, metric='l2', out=None, index_offset=0, query_i
        _p(query_ids), _p(dist), _p(idx), _p(ws), ws_bytes, _stream(),
        work=('knn_topk:%dx%dx%d' % (q, n, d), 2 * q * n * d, (q + n) * d * queries.element_size()))
   return dist, idx      # the workspace was allocated on this stream: its memory is not reused before the launches have run
+
+
+# ------------------------------------------------------------------------------------------------
+# kernel two-sample block sums over embeddings (include/twingan_hip_mmd.h)
+# ------------------------------------------------------------------------------------------------
+MMD_MAX_DEGREE = _lib.MMD_MAX_DEGREE
+
+
+def mmd_block_sums(a, b, block=32, degree=3, gamma=None, coef0=1.0, a_index0=0, b_index0=0, skip_same_index=False, out=None):
+  """fp64 [ceil(m / block), ceil(n / block)] on the device: entry (I, J) is the sum over the rows i of block I of ``a`` [m, d]
+  and j of block J of ``b`` [n, d] (one dtype: fp32 / bf16 / fp16; ``a`` may be ``b``) of the polynomial kernel
+  (gamma a_i.b_j + coef0) ** degree, each value computed in fp32 and added in fp64.  ``gamma`` None: float32(1 / d).
+  ``skip_same_index`` leaves out the pairs with a_index0 + i == b_index0 + j.  The Gram matrix is never written; the same
+  call twice gives the same bits.  tg_mmd_block_sums; no synchronisation."""
+  m, d = _knn_rows(a, 'mmd_block_sums')
+  n, db = _knn_rows(b, 'mmd_block_sums')
+  if db != d or b.dtype != a.dtype:
+    raise _lib.TgError('mmd_block_sums: a is %s [., %d], b %s [., %d]' % (a.dtype, d, b.dtype, db))
+  block = int(block)
+  ws_bytes = int(_lib.load().tg_mmd_workspace_bytes(m, n, d, block))      # 0: the launch below names what it refuses
+  nbi, nbj = (-(-m // block), -(-n // block)) if block > 0 else (0, 0)
+  if out is None:
+    out = torch.empty(nbi, nbj, dtype=torch.float64, device=a.device)
+  else:
+    _chk(out)
+    if out.dtype != torch.float64 or tuple(out.shape) != (nbi, nbj):
+      raise _lib.TgError('mmd_block_sums: out must be fp64 [%d, %d]' % (nbi, nbj))
+  if gamma is None:
+    gamma = ctypes.c_float(1.0 / max(d, 1)).value
+  ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=a.device)
+  call('tg_mmd_block_sums', _p(a), m, _p(b), n, d, _dt(a), int(degree), float(gamma), float(coef0), block, int(a_index0), int(b_index0),
+       1 if skip_same_index else 0, _p(out), _p(ws), ws_bytes, _stream(),
+       work=('mmd_block_sums:%dx%dx%d' % (m, n, d), 2 * m * n * d, (m + n) * d * a.element_size()))
+  return out      # the workspace was allocated on this stream: its memory is not reused before the launches have run
