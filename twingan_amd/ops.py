@@ -1275,11 +1275,16 @@ class PointwiseConvFn(torch.autograd.Function):
     (tg_pointwise_conv_fwd_masked) and the producer, flagged ``tg_v_premasked`` by the caller, skips its launch."""
     z = _pw_fwd_raw(x, w, bias, wt, epilogue, alpha)
     ctx.wt, ctx.epilogue, ctx.alpha = wt, epilogue, alpha
+    # no gradient, no work (see Conv2dFn): the gradient penalty's second backward reaches fromRGB with an undefined gradient;
+    # the default would run its filter gradient and bias sum over the full-resolution input on a tensor of zeros
+    ctx.set_materialize_grads(False)
     ctx.save_for_backward(x, w, z if (epilogue & TG_EPI_LRELU) else None, bias, out_act)
     return z
 
   @staticmethod
   def backward(ctx, gz):
+    if gz is None:
+      return None, None, None, None, None, None, None
     x, w, z, bias, out_act = ctx.saved_tensors
     gz = gz.contiguous()
     params = not _State.skip_param_grads
@@ -1879,10 +1884,16 @@ class Pool2Fn(torch.autograd.Function):
     call('tg_pool2x2_fwd', _p(x), _p(y), n, h, w, c, scale, _dt(x), _stream(),
          work=('pool_fwd' + _shape_tag(x), 0, _nb(x, y)))
     ctx.scale, ctx.hw = scale, (h, w)
+    # no gradient, no work (see Conv2dFn): the second backward of the gradient penalty reaches a stand-alone pool of the
+    # forward pass (the residual blocks, the fade-in's shrink path) with an undefined gradient; the default turns it into
+    # zeros, and every layer below then runs its whole backward -- LeakyReLU masks, backward-data, filter gradients -- on zeros
+    ctx.set_materialize_grads(False)
     return y
 
   @staticmethod
   def backward(ctx, gy):
+    if gy is None:
+      return None, None
     return Pool2BwdFn.apply(gy.contiguous(), ctx.scale, ctx.hw), None
 
 
@@ -1897,10 +1908,13 @@ class Pool2BwdFn(torch.autograd.Function):
     call('tg_pool2x2_bwd', _p(gy), _p(gx), n, hw[0], hw[1], c, scale, _dt(gy), _stream(),
          work=('pool_bwd' + _shape_tag(gx), 0, _nb(gy, gx)))
     ctx.scale = scale
+    ctx.set_materialize_grads(False)
     return gx
 
   @staticmethod
   def backward(ctx, v):
+    if v is None:
+      return None, None, None
     return Pool2Fn.apply(v.contiguous(), ctx.scale), None, None
 
 
